@@ -30,6 +30,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 # Cache -- profiles/r05/README.md section 2) and the guide's own float4 copy figure (MI355X_MICROARCH.md: 6.29 TB/s); both are quoted
 HBM_COPY_CEILING_GBS = 5950.0
 HBM_GUIDE_COPY_GBS = 6290.0
+DUMP_ELEMENTS = 1 << 21        # --dump-outputs: output elements kept over all ranks (fp64: 32 MiB of values + 16 MiB of indices)
 
 
 def parse_size(s: str):
@@ -127,6 +128,26 @@ def cpu_baseline():
     dt = time.perf_counter() - t
     return {"value": 5.0 * n ** 3 * math.log2(n ** 3) * 1e-9 / dt, "unit": "GFlops/s", "cores": 1, "kind": "port",
             "sample": f"oracle/slab_oracle.c (scalar C restatement), {n}^3 fp64 forward, 1 thread, {dt:.3f} s"}
+
+
+def dump_outputs(dirname: str, out, count: int, rank: int, P: int) -> None:
+    """--dump-outputs: this rank's forward output as the timed path left it, as (elements, 2) re / im pairs in the transform's own
+    precision -- whole when it has at most DUMP_ELEMENTS / P elements, otherwise one seeded element from each of that many equal
+    stretches of it, with the element indices (float64, exact) in a second file.  Names carry the rank when P > 1."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "forward_output" if P == 1 else f"forward_output_rank{rank}"
+    vals = torch.view_as_real(out[:count])
+    keep = max(1, DUMP_ELEMENTS // P)
+    if count <= keep:
+        np.save(d / f"{name}.npy", vals.cpu().numpy())
+        return
+    stride = count // keep
+    idx = np.arange(keep, dtype=np.int64) * stride + np.random.default_rng(4242 + rank).integers(0, stride, size=keep)
+    np.save(d / f"{name}_sample.npy", vals[torch.from_numpy(idx).to(vals.device)].cpu().numpy())
+    np.save(d / f"{name}_sample_index.npy", idx.astype(np.float64))
 
 
 def is_forward_zy_kernel(name: str) -> bool:
@@ -266,7 +287,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="control-plane check only (CPU tests): rendezvous, id broadcast, slab bookkeeping; no GPU work")
     ap.add_argument("--unfused", action="store_true", help="reference stage structure (separate pack / transpose)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (each rank's forward output, a fixed seeded "
+                         "sample of it when large) as DIR/<name>.npy; the input is seeded, so runs can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries exactly ONE line (the JSON): RCCL prints a version banner to stdout when a communicator is created,
     # so everything else this process (and the libraries it loads) writes to fd 1 is sent to stderr instead
@@ -533,6 +559,8 @@ def main():
         elapsed = float(t.item())
     sec_per_step = elapsed / args.steps
     gflops = 5.0 * N * math.log2(N) * 1e-9 / sec_per_step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, b, count, rank, P)  # before any untimed execute below touches b
 
     # ---- per-stage / per-kernel breakdown from HIP events on the plan's stream (separate, untimed executes) ----
     stage, kern = [], []

@@ -342,6 +342,7 @@ api.Plan = StubPlan
 api.Comm.rccl_unique_id = staticmethod(lambda: bytes(range(128)))
 api.Comm.rccl = staticmethod(lambda uid, P, r: StubComm(P, r))
 sys.argv = ["bench.py", "--gpus", os.environ["WORLD_SIZE"], "--size", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+sys.argv += os.environ.get("STUB_EXTRA_ARGS", "").split()
 runpy.run_path(os.path.join(os.environ["DFFT_ROOT"], "bench.py"), run_name="__main__")
 '''
 
@@ -389,3 +390,53 @@ def test_bench_falls_back_to_serial_pipeline_when_overlap_result_differs(native_
     assert "overlap_fallback" in d and "serial pipeline" in d["overlap_fallback"]
     assert d["stages_ms"]["t2"] == 2.0 and "stages_ms_without_overlap" not in d   # the serial plan's stage times
     assert "overlapped" not in d["config"]["exchange"] and d["value"] > 0
+
+
+def test_bench_dumps_the_timed_output_of_every_rank(native_lib, tmp_path):
+    """--dump-outputs DIR: each rank writes the output of the last timed step (the stub plan copies its seeded input) as float
+    re / im pairs; a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    world = 2
+    got = []
+    for run in range(2):
+        port, out = _free_port(), tmp_path / f"run{run}"
+        procs = []
+        for r in range(world):
+            env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                       MASTER_PORT=str(port), DFFT_ROOT=str(ROOT), STUB_EXTRA_ARGS=f"--dump-outputs {out}")
+            procs.append(subprocess.Popen([sys.executable, "-c", STUB_WORKER], env=env, stdout=subprocess.PIPE,
+                                          stderr=subprocess.PIPE, text=True))
+        for p in procs:
+            o, e = p.communicate(timeout=300)
+            assert p.returncode == 0, e[-3000:]
+        assert sorted(f.name for f in out.iterdir()) == [f"forward_output_rank{r}.npy" for r in range(world)]
+        got.append([np.load(out / f"forward_output_rank{r}.npy") for r in range(world)])
+    for r in range(world):
+        a = got[0][r]
+        assert a.dtype == np.float64 and a.shape == (16 ** 3 // world, 2)
+        assert np.abs(a).max() > 0 and np.abs(a).max() <= np.sqrt(2.0)   # the seeded uniform [-1, 1) input, copied by the stub
+        assert np.array_equal(a, got[1][r])
+    assert not np.array_equal(got[0][0], got[0][1])   # each rank its own slab
+
+
+def test_bench_dump_samples_a_large_output(tmp_path):
+    """An output larger than the dump budget is stored as a fixed, seeded sample with its element indices, under 64 MB."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 3 * bench.DUMP_ELEMENTS + 5
+    out = torch.complex(torch.arange(n, dtype=torch.float64), -torch.arange(n, dtype=torch.float64))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, n - 3, 0, 1)
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["forward_output_sample.npy", "forward_output_sample_index.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 * 10 ** 6
+    vals, idx = np.load(tmp_path / "a" / files[0]), np.load(tmp_path / "a" / files[1])
+    assert vals.dtype == np.float64 and idx.dtype == np.float64 and vals.shape == (bench.DUMP_ELEMENTS, 2)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n - 3
+    assert np.array_equal(vals[:, 0], idx) and np.array_equal(vals[:, 1], -idx)   # each value is the element at its index
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

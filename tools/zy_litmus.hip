@@ -15,6 +15,12 @@
 //   mode 3  the part counter of the overlapped pipeline (round 6, SIG launches): a persistent producer writes with `sc1 nt` stores and
 //           counts; on ANOTHER stream a one-wave kernel waits for the count and a kernel launched behind it reads with PLAIN loads,
 //           as an exchange would (kernel-boundary acquire)                          -> expected: 0 stale reads
+//           The two streams must run side by side.  The HIP runtime maps streams onto at most GPU_MAX_HW_QUEUES hardware queues PER
+//           PRIORITY, and two streams on one queue run one kernel after the other (the readers would wait for the producer to end), so
+//           the producer's stream gets the lowest priority and the readers' stream the highest: two queues under any cap.  The producer
+//           waits for the readers' ack before it overwrites a payload, but only for ACK_WAIT_TICKS, so a run that cannot overlap ends
+//           in seconds instead of hanging; a step without the ack fails the run (the hand-off was not exercised), and a reader then
+//           accepts a NEWER sequence number than the count promised -- only an older one is counted as stale.
 //
 // usage: zy_litmus <iterations> <mode> [payload KiB per hand-off, default 16]      exit 0 = the expectation held
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/zy_litmus.hip -o tools/bin/zy_litmus
@@ -38,8 +44,10 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int THREADS = 512;
 
 struct Stats {
-    unsigned long long handoffs, stale, same_xcd_pairs, timeouts;
+    unsigned long long handoffs, stale, same_xcd_pairs, timeouts, unpaced;
 };
+// mode 3 time limits in wall_clock64() ticks (100 MHz): the producer's wait for an ack, a wait kernel's wait for the count
+constexpr unsigned long long ACK_WAIT_TICKS = 2000000ull, COUNT_WAIT_TICKS = 1000000000ull;
 
 __device__ __forceinline__ unsigned xcc_id() {
     unsigned v;
@@ -130,34 +138,37 @@ __global__ void __launch_bounds__(THREADS) pingpong_kernel(char* bufs, unsigned*
 }
 
 // mode 3: persistent producer (one workgroup per pair), `sc1 nt` stores like store_cols of a SIG launch, counts, waits for the reader's ack
-__global__ void __launch_bounds__(THREADS) part_producer_kernel(char* bufs, unsigned* counters, unsigned* acks, unsigned iters, unsigned elems) {
-    __shared__ unsigned shw[1];
-    char*               buf = bufs + (size_t)blockIdx.x * elems * 16;
+__global__ void __launch_bounds__(THREADS) part_producer_kernel(char* bufs, unsigned* counters, unsigned* acks, Stats* st, unsigned iters, unsigned elems) {
+    char* buf = bufs + (size_t)blockIdx.x * elems * 16;
     for (unsigned t = 0; t < iters; ++t) {
         for (unsigned i = threadIdx.x; i < elems; i += THREADS) store16<18>(buf, elems * 16u, i * 16u, u32x4{t + 1, blockIdx.x, i, ~(t + 1)}, false);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
             __hip_atomic_fetch_add(&counters[blockIdx.x * 32], 1u, __ATOMIC_RELAXED, AGENT);
-            unsigned ok = 0;
-            for (unsigned polls = 0; polls < (64u << 20); ++polls) {  // the payload is overwritten only after it has been read
-                if (__hip_atomic_load(&acks[blockIdx.x * 32], __ATOMIC_RELAXED, AGENT) >= t + 1) {
-                    ok = 1;
+            const unsigned long long t0 = wall_clock64();
+            while (__hip_atomic_load(&acks[blockIdx.x * 32], __ATOMIC_RELAXED, AGENT) < t + 1) {  // overwrite after the read, if it comes
+                if (wall_clock64() - t0 > ACK_WAIT_TICKS) {
+                    atomicAdd(&st->unpaced, 1ull);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(2);
             }
-            shw[0] = ok;
         }
-        __syncthreads();
-        if (!shw[0]) return;
         __syncthreads();
     }
 }
-__global__ void part_wait_kernel(const unsigned* counters, unsigned npairs, unsigned target) {  // (zy_part_wait_kernel)
+// (zy_part_wait_kernel) a wait that runs out of time is a time-out of the run and makes every later wait return at once
+__global__ void part_wait_kernel(const unsigned* counters, unsigned npairs, unsigned target, unsigned* gave_up, Stats* st) {
     if (threadIdx.x >= npairs) return;
-    for (unsigned polls = 0; polls < (64u << 20); ++polls) {
-        if ((int)(__hip_atomic_load(&counters[threadIdx.x * 32], __ATOMIC_RELAXED, AGENT) - target) >= 0) return;
+    const unsigned long long t0 = wall_clock64();
+    while ((int)(__hip_atomic_load(&counters[threadIdx.x * 32], __ATOMIC_RELAXED, AGENT) - target) < 0) {
+        if (__hip_atomic_load(gave_up, __ATOMIC_RELAXED, AGENT) != 0u) return;
+        if (wall_clock64() - t0 > COUNT_WAIT_TICKS) {
+            __hip_atomic_store(gave_up, 1u, __ATOMIC_RELAXED, AGENT);
+            atomicAdd(&st->timeouts, 1ull);
+            return;
+        }
         __builtin_amdgcn_s_sleep(8);
     }
 }
@@ -168,8 +179,8 @@ __global__ void __launch_bounds__(THREADS) part_reader_kernel(const char* bufs, 
     for (unsigned p = 0; p < npairs; ++p) {
         const u32x4* b = reinterpret_cast<const u32x4*>(bufs + (size_t)p * elems * 16);
         for (unsigned i = threadIdx.x; i < elems; i += THREADS) {
-            const u32x4 v = b[i];
-            if (v.x != seq || v.y != p || v.z != i || v.w != ~seq) ++bad;
+            const u32x4 v = b[i];  // older than the count promised = stale; newer = a step that went on without the ack
+            if (v.y != p || v.z != i || v.x < seq || (v.x == seq && v.w != ~seq)) ++bad;
         }
     }
     __shared__ unsigned total;
@@ -192,15 +203,20 @@ int main(int argc, char** argv) {
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const unsigned cus = (unsigned)prop.multiProcessorCount, npairs = cus / 2;
+    const unsigned np = 32;  // mode 3: producers (persistent), readers: 16 workgroups per launch
+    // payloads and flag words of both layouts: modes 0-2 use 2 x npairs payloads and 64 words per pair; mode 3 np payloads,
+    // counters / acks (32 words apart), the readers' done count and the wait kernels' give-up word
+    const size_t   buf_bytes = (size_t)(npairs * 2 > np ? npairs * 2 : np) * elems * 16;
+    const size_t   flag_words = (size_t)npairs * 64 > (size_t)2 * np * 32 + 64 ? (size_t)npairs * 64 : (size_t)2 * np * 32 + 64;
     char*          bufs = nullptr;
     unsigned *     flags = nullptr, *xcds = nullptr;
     Stats*         st = nullptr;
-    CHECK(hipMalloc((void**)&bufs, (size_t)npairs * 2 * elems * 16));
-    CHECK(hipMalloc((void**)&flags, (size_t)npairs * 64 * sizeof(unsigned) + 1024));
+    CHECK(hipMalloc((void**)&bufs, buf_bytes));
+    CHECK(hipMalloc((void**)&flags, flag_words * sizeof(unsigned) + 1024));
     CHECK(hipMalloc((void**)&xcds, cus * sizeof(unsigned)));
     CHECK(hipMalloc((void**)&st, sizeof(Stats)));
-    CHECK(hipMemset(bufs, 0, (size_t)npairs * 2 * elems * 16));
-    CHECK(hipMemset(flags, 0, (size_t)npairs * 64 * sizeof(unsigned) + 1024));
+    CHECK(hipMemset(bufs, 0, buf_bytes));
+    CHECK(hipMemset(flags, 0, flag_words * sizeof(unsigned) + 1024));
     CHECK(hipMemset(st, 0, sizeof(Stats)));
     CHECK(hipDeviceSynchronize());
     hipEvent_t e0, e1;
@@ -220,15 +236,20 @@ int main(int argc, char** argv) {
         for (unsigned p = 0; p < npairs; ++p) cross += hx[2 * p] != hx[2 * p + 1];
     } else {
         hipStream_t sa, sb;
-        CHECK(hipStreamCreateWithFlags(&sa, hipStreamNonBlocking));
-        CHECK(hipStreamCreateWithFlags(&sb, hipStreamNonBlocking));
-        const unsigned np = 32;  // producers (persistent), readers: 16 workgroups per launch
-        unsigned *     counters = flags, *acks = flags + np * 32, *done = flags + 2 * np * 32;
+        int least = 0, greatest = 0;
+        CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        if (least == greatest) {
+            fprintf(stderr, "zy_litmus: one stream priority only, the producer and the readers could share a hardware queue\n");
+            return 2;
+        }
+        CHECK(hipStreamCreateWithPriority(&sa, hipStreamNonBlocking, least));
+        CHECK(hipStreamCreateWithPriority(&sb, hipStreamNonBlocking, greatest));
+        unsigned *     counters = flags, *acks = flags + np * 32, *done = flags + 2 * np * 32, *gave_up = done + 32;
         CHECK(hipEventRecord(e0, sb));
-        hipLaunchKernelGGL(part_producer_kernel, dim3(np), dim3(THREADS), 0, sa, bufs, counters, acks, iters, elems);
+        hipLaunchKernelGGL(part_producer_kernel, dim3(np), dim3(THREADS), 0, sa, bufs, counters, acks, st, iters, elems);
         CHECK(hipGetLastError());
         for (unsigned t = 0; t < iters; ++t) {
-            hipLaunchKernelGGL(part_wait_kernel, dim3(1), dim3(64), 0, sb, counters, np, t + 1);
+            hipLaunchKernelGGL(part_wait_kernel, dim3(1), dim3(64), 0, sb, counters, np, t + 1, gave_up, st);
             hipLaunchKernelGGL(part_reader_kernel, dim3(16), dim3(THREADS), 0, sb, bufs, acks, done, st, np, elems, t + 1);
         }
         CHECK(hipGetLastError());
@@ -240,13 +261,14 @@ int main(int argc, char** argv) {
     CHECK(hipEventElapsedTime(&ms, e0, e1));
     CHECK(hipMemcpy(&h, st, sizeof(Stats), hipMemcpyDeviceToHost));
     const bool expect_clean = mode == 0 || mode == 3;
-    const bool held = h.timeouts == 0 && (expect_clean ? h.stale == 0 : h.stale > 0) && h.handoffs > 0;
-    printf("zy_litmus mode %d (%s): %llu hand-offs of %u KiB, %llu stale 16-byte reads, %llu time-outs, %llu of %u pairs across XCDs, %.1f ms -- %s\n", mode,
+    const bool held = h.timeouts == 0 && h.unpaced == 0 && (expect_clean ? h.stale == 0 : h.stale > 0) && h.handoffs > 0;
+    printf("zy_litmus mode %d (%s): %llu hand-offs of %u KiB, %llu stale 16-byte reads, %llu time-outs, %llu of %u pairs across XCDs, %.1f ms, "
+           "%llu producer steps without the ack -- %s\n", mode,
            mode == 0 ? "shipped pattern: sc1 stores, vmcnt(0), relaxed agent increment | relaxed poll, sc1 loads"
            : mode == 1 ? "negative control: plain loads on the consumer side"
            : mode == 2 ? "negative control: plain stores on the producer side"
                        : "part counter: sc1 nt stores + count | wait kernel, reader kernel with plain loads on another stream",
-           h.handoffs, kib, h.stale, h.timeouts, cross, mode <= 2 ? npairs : 32u, ms,
+           h.handoffs, kib, h.stale, h.timeouts, cross, mode <= 2 ? npairs : np, ms, h.unpaced,
            held ? (expect_clean ? "PASS (no stale read)" : "PASS (the control fails as it must)") : "FAIL");
     return held ? 0 : 1;
 }
