@@ -54,6 +54,7 @@ SIGNATURES = {
     "dfft_plan_stream": (_VP, [_VP]),
     "dfft_plan_workbuf": (_VP, [_VP, _LLP]),
     "dfft_fft2d_batch": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_fft2d_batch_status": (C.c_int, [_VP]),
     "dfft_execute": (C.c_int, [_VP, C.c_uint]),
     "dfft_plan_sync": (C.c_int, [_VP]),
     "dfft_plan_tune": (C.c_int, [_VP]),

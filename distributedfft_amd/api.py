@@ -283,11 +283,21 @@ def fft_mpi_destroy_plan(plan: Plan) -> None:
 
 
 # ---- batched 1D building blocks ---------------------------------------------------------------------------------------------
+def _check_out(x, out):
+    """`out` (None: a fresh tensor) must have x's shape, dtype and device and be contiguous: the C entry points take bare pointers."""
+    import torch
+    if out is None:
+        return torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.device == x.device and out.is_contiguous(), \
+        f"out must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}"
+    return out
+
+
 def fft1d_rows(x, direction: int = FORWARD, out=None):
     """Length-n FFT of every contiguous row of a (batch, n) complex device tensor."""
     import torch
     assert x.is_cuda and x.is_contiguous() and x.dim() == 2
-    out = torch.empty_like(x) if out is None else out
+    out = _check_out(x, out)
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_fft1d_rows(x.data_ptr(), out.data_ptr(), x.shape[1], x.shape[0], _dtype_code(x), direction,
                                          None), "dfft_fft1d_rows")
@@ -299,7 +309,7 @@ def fft1d_cols(x, direction: int = FORWARD, out=None):
     """Length-n FFT down the columns of every (n, width) matrix of a (batch, n, width) complex device tensor."""
     import torch
     assert x.is_cuda and x.is_contiguous() and x.dim() == 3
-    out = torch.empty_like(x) if out is None else out
+    out = _check_out(x, out)
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_fft1d_cols(x.data_ptr(), out.data_ptr(), x.shape[1], x.shape[2], x.shape[0], _dtype_code(x),
                                          direction, None), "dfft_fft1d_cols")
@@ -312,9 +322,10 @@ def fft2d_batch(x, direction: int = FORWARD, out=None):
     (dfft_fft2d_batch; templateFFT's FFTDim = 2 application, templateFFT.cpp:5767).  out=x transforms in place."""
     import torch
     assert x.is_cuda and x.is_contiguous() and x.dim() == 3
-    out = torch.empty_like(x) if out is None else out
+    out = _check_out(x, out)
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_fft2d_batch(x.data_ptr(), out.data_ptr(), x.shape[1], x.shape[2], x.shape[0], _dtype_code(x), direction,
                                           None), "dfft_fft2d_batch")
         torch.cuda.synchronize()
+        L.check(L.load().dfft_fft2d_batch_status(None), "dfft_fft2d_batch")  # a one-launch stage that gave up: reported on this call
     return out

@@ -1988,6 +1988,7 @@ struct Zy2dCtx {
     ZyCtl*    ctl = nullptr;
     unsigned* err = nullptr;
     unsigned  ticket = 0, execs = 0;
+    long long batch = 0;    // planes of the last launch on this context (0: none since the control block was zeroed)
     bool      off = false;  // a launch gave up: this context stays on two launches per chunk
 };
 struct Zy2dKey {
@@ -2090,6 +2091,19 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
             }();
             L.spin_polls = polls;
             if (hipHostGetDevicePointer((void**)&L.err_host, c.err, 0) != hipSuccess) return fail(DFFT_EHIP, "dfft_fft2d_batch: no device pointer for the error word");
+            // done_base = execs x producers holds only while every earlier launch on this block covered planes [0, batch): each one
+            // added `producers` to done[p] of exactly those planes.  A plan always launches all of its planes, so its counters never
+            // drift; this entry point takes any batch, so when the batch changes the control block is zeroed on the caller's stream
+            // (stream order puts that behind every earlier launch of this context) and the host counters restart from 0.
+            if (c.batch != batch) {
+                if (c.batch != 0 && hipMemsetAsync(c.ctl, 0, sizeof(ZyCtl), s) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(DFFT_EHIP, "dfft_fft2d_batch: cannot reset the control block of the one-launch YZ stage");
+                }
+                c.ticket = 0;
+                c.execs = 0;
+                c.batch = batch;
+            }
             unsigned producers = 0;
             (void)zy_units_per_plane(L.n1, L.n2, L.dir, 0, &producers);
             L.ticket_base = c.ticket;
@@ -2128,6 +2142,24 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
         L.a_first = x0;
         L.ncols = (int)n2;
         DFFT_TRY(check_launch(launch_fft(L, s), "dfft_fft2d_batch (columns)"));
+    }
+    return DFFT_OK;
+}
+
+// Did a one-launch stage of dfft_fft2d_batch on (current device, stream) give up?  Meant for after the caller has waited for the stream:
+// it reads the pinned error words the kernels write.  A failure reported here is reported once -- the context then stays on two
+// launches per chunk, and the next call on it does not report it again.
+int dfft_fft2d_batch_status(void* stream) {
+    int dev = 0;
+    DFFT_HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_zy2d_mutex);
+    for (auto& kv : g_zy2d) {
+        Zy2dCtx& c = kv.second;
+        if (kv.first.dev != dev || kv.first.stream != (hipStream_t)stream || c.off || !c.err || *(volatile unsigned*)c.err == 0u) continue;
+        c.off = true;
+        return fail(DFFT_EHIP, "dfft_fft2d_batch: a one-launch YZ stage on this stream gave up (" + std::string(*c.err == ZY_ERR_DESYNC ? "control block out of step" : "timed out") +
+                                   ", " + std::to_string(kv.first.n1) + "x" + std::to_string(kv.first.n2) + "); the results of that call and of every call queued "
+                                   "behind it are invalid, later calls use two launches per chunk");
     }
     return DFFT_OK;
 }

@@ -24,7 +24,8 @@ enum { ZY_MAX_PLANES = 4096 };
 
 // why a launch gave up (ZyCtl::error and the host-visible word)
 enum { ZY_ERR_TIMEOUT = 1,   // a consumer unit polled spin_polls times for its plane's producers
-       ZY_ERR_DESYNC = 2 };  // the first ticket of a launch did not fit its ticket_base: counters out of step with the host
+       ZY_ERR_DESYNC = 2 };  // the first ticket of a launch did not fit its ticket_base, or a plane's done count lay outside
+                             // [done_base, done_base + need]: counters out of step with the host
 
 // control block in device memory, zeroed once when the plan is created (launches count on from where the last one stopped)
 struct alignas(128) ZyCtl {

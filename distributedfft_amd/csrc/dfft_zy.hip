@@ -182,16 +182,27 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
         __hip_atomic_store(&ctl->error, code, __ATOMIC_RELAXED, DFFT_ZY_AGENT);
         __hip_atomic_store(err_host, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     };
+    // A legal count done[plane] - done_base lies in [0, UA] and need >= UA, so a count above `need` (in wrapping arithmetic: a plane
+    // whose counter lags done_base, too) means the control block is out of step with the host's done_base -- refuse loudly
+    // (ZY_ERR_DESYNC) instead of reading rows that have not been published.
     auto ready = [&](const Item& it, bool wait) -> bool {
         if (it.kind != CONS) return true;
         if (tid == 0) {
-            unsigned ok = __hip_atomic_load(&ctl->done[it.plane], __ATOMIC_RELAXED, DFFT_ZY_AGENT) - done_base >= need ? 1u : 0u;
-            if (!ok && wait) {
+            unsigned d = __hip_atomic_load(&ctl->done[it.plane], __ATOMIC_RELAXED, DFFT_ZY_AGENT) - done_base;
+            unsigned ok = d == need ? 1u : 0u;
+            if (d > need) {
+                raise(ZY_ERR_DESYNC);
+            } else if (!ok && wait) {
                 // bounded by polls this wave actually makes, not by elapsed time: a preempted process does not time out
                 for (unsigned polls = 0;; ++polls) {
                     __builtin_amdgcn_s_sleep(1);
-                    if (__hip_atomic_load(&ctl->done[it.plane], __ATOMIC_RELAXED, DFFT_ZY_AGENT) - done_base >= need) {
+                    d = __hip_atomic_load(&ctl->done[it.plane], __ATOMIC_RELAXED, DFFT_ZY_AGENT) - done_base;
+                    if (d == need) {
                         ok = 1u;
+                        break;
+                    }
+                    if (d > need) {
+                        raise(ZY_ERR_DESYNC);
                         break;
                     }
                     if (__hip_atomic_load(&ctl->error, __ATOMIC_RELAXED, DFFT_ZY_AGENT) != 0u) break;

@@ -214,9 +214,14 @@ int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long
  * groups that fit the 256 MiB Infinity Cache (the column pass reads what the row pass wrote from the cache), and the plane
  * shapes the one-launch stage is built for (fp64; n1 = 256 / 512 with n2 = 256 / 512, n1 = 768 with n2 = 512) run as ONE
  * persistent launch per call.  Un-normalised in both directions.  The one-launch form keeps a small control block per (device,
- * stream, plane shape, direction), freed by dfft_trim(); a launch that gives up (see dfft_zy.hip) is reported by the next call
- * on that stream, which -- like every later one -- runs on two launches per chunk. */
+ * stream, plane shape, direction), freed by dfft_trim(); calls on one stream may change batch, direction, placement and dtype
+ * freely (a batch change re-zeroes the block on that stream).  A launch that gives up (see dfft_zy.hip) is reported by
+ * dfft_fft2d_batch_status() once the stream has been waited for, or else by the next call on that stream, which -- like every
+ * later one -- runs on two launches per chunk. */
 int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream);
+/* DFFT_EHIP (with a message) if a one-launch stage of dfft_fft2d_batch on (current device, stream) gave up; call it after waiting
+ * for the stream.  Each failure is reported once, here or by the next dfft_fft2d_batch call on that stream. */
+int dfft_fft2d_batch_status(void* stream);
 
 /* Frees the scratch buffers the 1-D entry points cache per (device, stream) for lengths above 4096 (four-step transforms) and the
  * control blocks of dfft_fft2d_batch.

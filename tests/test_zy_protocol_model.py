@@ -8,7 +8,11 @@ than the resident set does) drives them.  Checked under many interleavings:
   * every producer has published when the launch ends (the next execute's done_base arithmetic relies on it);
   * the ticket counter ends at exactly items + 2 * workgroups -- zy_tickets(), what the host adds to its running ticket base.
 Negative controls: the lazy loop WITHOUT the flush in front of its blocking wait deadlocks; a loop that prefetches without the
-dependency poll loads a consumer unit too early.  (Test infrastructure: a model of the protocol, not the kernel's arithmetic --
+dependency poll loads a consumer unit too early.
+Across launches, the host bookkeeping of dfft_fft2d_batch (distributedfft_amd/csrc/dfft_plan.cpp): calls on one cached control block
+with changing batch sizes must start every launch with done[p] == done_base on each of its planes; the rule before the fix
+(done_base = execs x producers, no reset) breaks that at batch 1 -> 2, and the kernel's range check then raises ZY_ERR_DESYNC.
+(Test infrastructure: a model of the protocol, not the kernel's arithmetic --
 that is what the -m gpu parity tests are for.)"""
 import random
 
@@ -188,3 +192,93 @@ def test_prefetch_without_the_dependency_poll_is_caught():
         run(L, False, seed, poll_before_prefetch=False)
         bad += bool(L.violations)
     assert bad > 0
+
+
+# ---- bookkeeping across launches on one cached control block (dfft_fft2d_batch) -----------------------------------------------
+M32 = 1 << 32
+MAX_PLANES = 64  # (ZY_MAX_PLANES in the library; the rule does not depend on it)
+
+
+class Ctx:
+    """Zy2dCtx and its ZyCtl: done[] per plane, the ticket counter, the host's running ticket base / execute count / last batch."""
+
+    def __init__(self):
+        self.done = [0] * MAX_PLANES
+        self.ctl_ticket = 0
+        self.ticket = self.execs = self.batch = 0
+
+
+def host_launch(c, batch, ua, tickets, fixed=True):
+    """The host side of one call: (ticket_base, done_base) of its launch.  fixed: a batch change zeroes the control block
+    (hipMemsetAsync on the caller's stream, ordered after every earlier launch) and restarts the host counters."""
+    if fixed and c.batch != batch:
+        if c.batch != 0:
+            c.done = [0] * MAX_PLANES
+            c.ctl_ticket = 0
+        c.ticket = c.execs = 0
+        c.batch = batch
+    base = (c.ticket, (c.execs * ua) % M32)
+    c.execs += 1
+    c.ticket = (c.ticket + tickets) % M32
+    return base
+
+
+def device_launch(c, batch, ua, tickets):
+    """What a launch does to the control block once it has finished: every plane of it gains its ua producer units."""
+    for p in range(batch):
+        c.done[p] = (c.done[p] + ua) % M32
+    c.ctl_ticket = (c.ctl_ticket + tickets) % M32
+
+
+def guard(done, done_base, need):
+    """The kernel's ready() on a plane nothing of this launch has published yet: 'wait', 'ready' or 'desync'."""
+    d = (done - done_base) % M32
+    return "desync" if d > need else ("ready" if d == need else "wait")
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_batch_changes_keep_every_plane_in_step_with_done_base(seed):
+    rng = random.Random(seed)
+    ua = rng.choice([8, 16, 32, 64])
+    c = Ctx()
+    for _ in range(200):
+        batch = rng.choice([1, 2, 3, rng.randint(1, MAX_PLANES)])
+        tickets = batch * (ua + rng.randint(1, 64)) + 2 * rng.randint(1, 256)
+        ticket_base, done_base = host_launch(c, batch, ua, tickets)
+        assert c.ctl_ticket == ticket_base  # the kernel's first-ticket check passes
+        for p in range(batch):
+            assert c.done[p] == done_base, (p, batch)
+            assert guard(c.done[p], done_base, ua) == "wait"  # consumers wait for this launch's producers
+        device_launch(c, batch, ua, tickets)
+        assert all(guard(c.done[p], done_base, ua) == "ready" for p in range(batch))
+
+
+def test_old_rule_breaks_at_batch_1_then_2_and_the_guard_catches_it():
+    """Negative control: done_base = execs x producers with no reset.  At batch 1 -> 2, plane 1 still counts 0 while done_base is UA:
+    the old unsigned test (done - done_base >= need) wraps to 'ready' before any producer has published; the range check raises."""
+    ua, tickets = 16, 100
+    c = Ctx()
+    for batch in (1, 2):
+        _, done_base = host_launch(c, batch, ua, tickets, fixed=False)
+        if batch == 2:
+            assert c.done[0] == done_base
+            assert c.done[1] != done_base                               # the invariant is broken ...
+            assert (c.done[1] - done_base) % M32 >= ua                  # ... the old test calls plane 1 ready at once ...
+            assert guard(c.done[1], done_base, ua) == "desync"          # ... the range check refuses instead
+        device_launch(c, batch, ua, tickets)
+    # shrink then grow (8 -> 2 -> 8): planes 2..7 lag one execute behind, caught the same way
+    c = Ctx()
+    for batch in (8, 2, 8):
+        _, done_base = host_launch(c, batch, ua, tickets, fixed=False)
+        lagging = [p for p in range(batch) if c.done[p] != done_base]
+        if lagging:
+            assert lagging == list(range(2, 8))
+            assert all(guard(c.done[p], done_base, ua) == "desync" for p in lagging)
+        device_launch(c, batch, ua, tickets)
+    # the fixed rule on the same sequences
+    for seq in ((1, 2), (8, 2, 8), (1, 2, 8, 3)):
+        c = Ctx()
+        for batch in seq:
+            _, done_base = host_launch(c, batch, ua, tickets)
+            assert c.done[:batch] == [done_base] * batch
+            device_launch(c, batch, ua, tickets)
