@@ -49,6 +49,8 @@ SIGNATURES = {
     "dfft_alloc": (_VP, [_LL, C.c_int, C.c_int]),
     "dfft_free": (C.c_int, [_VP, C.c_int]),
     "dfft_plan_create": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
+    "dfft_plan_create_r2c": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
+    "dfft_r2c_counts": (C.c_int, [_LL, _LL, _LL, C.c_int, C.c_int, _LLP, _LLP]),
     "dfft_plan_buffer1": (_VP, [_VP]),
     "dfft_plan_result": (_VP, [_VP]),
     "dfft_plan_stream": (_VP, [_VP]),

@@ -269,6 +269,83 @@ class Plan:
             pass
 
 
+def r2c_counts(n0, n1, n2, total_devices: int, global_idx: int) -> Tuple[int, int]:
+    """(reals, complex elements) the real-side / complex-side buffers of an r2c plan must hold on device global_idx (dfft_r2c_counts)."""
+    lib = L.load()
+    r, c = C.c_longlong(), C.c_longlong()
+    L.check(lib.dfft_r2c_counts(n0, n1, n2, total_devices, global_idx, C.byref(r), C.byref(c)), "dfft_r2c_counts")
+    return int(r.value), int(c.value)
+
+
+_R2C_PAIRS = {"float64": "complex128", "float32": "complex64"}
+
+
+class PlanR2C(Plan):
+    """Real-to-complex (FORWARD) / complex-to-real (BACKWARD) slab plan (dfft_plan_create_r2c).  Real side: float64 / float32
+    [x_local][N1][N2]; complex side: complex128 / complex64 [y_local][N2/2+1][N0].  FORWARD: inp real, out complex; BACKWARD: inp complex,
+    out real.  Shares Plan's execute / sync / set_scale / stage_times / describe / destroy; bufferDev1 holds the real slab (FORWARD) or
+    the bins (BACKWARD)."""
+
+    def __init__(self, n0, n1, n2, inp, out, comm: Optional[Comm], global_idx: int, total_devices: int, direction: int,
+                 flags: int = PLAN_DEFAULT):
+        import torch
+        lib = L.load()
+        if inp is None or out is None:
+            raise ValueError("PlanR2C: real-to-complex plans are out of place (inp and out are both required)")
+        if not inp.is_cuda or not out.is_cuda:
+            raise DfftError(L.ENOGPU, "PlanR2C", "buffers must live on a HIP device (no CPU fallback)")
+        if inp.device != out.device:
+            raise ValueError(f"PlanR2C: inp is on {inp.device}, out on {out.device}")
+        real, cplx = (inp, out) if direction == FORWARD else (out, inp)
+        rname, cname = str(real.dtype).replace("torch.", ""), str(cplx.dtype).replace("torch.", "")
+        if _R2C_PAIRS.get(rname) != cname:
+            raise TypeError(f"PlanR2C: the real / complex buffers must be float64 / complex128 or float32 / complex64, got {rname} / {cname}")
+        self.N = (int(n0), int(n1), int(n2))
+        self.dtype = F64 if rname == "float64" else F32
+        self.direction = direction
+        self.total_devices, self.global_idx = total_devices, global_idx
+        self.real_count, self.complex_count = r2c_counts(n0, n1, n2, total_devices, global_idx)
+        if real.numel() < self.real_count or cplx.numel() < self.complex_count:
+            raise ValueError(f"PlanR2C: the real buffer must hold {self.real_count} elements and the complex one {self.complex_count} "
+                             f"(r2c_counts), got {real.numel()} / {cplx.numel()}")
+        # bufferDev1 holds the input side
+        self.max_count = self.real_count if direction == FORWARD else self.complex_count
+        self._in, self._out, self._comm = inp, out, comm  # keep alive
+        self.handle = C.c_void_p()
+        torch.cuda.synchronize(inp.device)
+        with torch.cuda.device(inp.device):
+            L.check(lib.dfft_plan_create_r2c(C.byref(self.handle), n0, n1, n2, self.dtype, direction, inp.data_ptr(), out.data_ptr(),
+                                             comm.handle if comm is not None else None, global_idx, total_devices, flags),
+                    "dfft_plan_create_r2c")
+        self.device = inp.device
+
+    def load_input(self, src) -> None:
+        """Copy the next input (real slab for FORWARD, bins for BACKWARD) into bufferDev1."""
+        import torch
+        view = self.buffer1_tensor(src.numel())
+        assert src.numel() <= self.max_count and src.dtype == view.dtype
+        view.copy_(src.reshape(-1))
+        torch.cuda.synchronize(self.device)
+
+    def buffer1_tensor(self, count: Optional[int] = None):
+        """A torch view of bufferDev1 (no copy): real elements for FORWARD plans, complex ones for BACKWARD plans."""
+        import torch
+        count = self.max_count if count is None else count
+        if self.direction == FORWARD:
+            typestr, tdtype = ("<f8", torch.float64) if self.dtype == F64 else ("<f4", torch.float32)
+        else:
+            typestr, tdtype = ("<c16", torch.complex128) if self.dtype == F64 else ("<c8", torch.complex64)
+
+        class _Raw:
+            pass
+
+        r = _Raw()
+        r.__cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (self.bufferDev1, False), "version": 2}
+        t = torch.as_tensor(r, device=self.device)
+        assert t.dtype == tdtype
+        return t
+
+
 def fft_mpi_plan_dft_c2c_3d(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags=PLAN_DEFAULT) -> Plan:
     return Plan(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags)
 

@@ -86,6 +86,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     units = []  # (source, object, extra flags)
     for g in range(NUM_INST_GROUPS):
         units.append((CSRC / "dfft_fft_inst.hip", OBJ / f"dfft_fft_inst_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-to-complex / complex-to-real rows: the same groups of lengths, plus the dispatcher (group NUM_INST_GROUPS)
+    for g in range(NUM_INST_GROUPS + 1):
+        units.append((CSRC / "dfft_real.hip", OBJ / f"dfft_real_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
     units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
     units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))

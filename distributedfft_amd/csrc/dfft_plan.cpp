@@ -28,6 +28,7 @@
 
 #include "dfft_internal.h"
 #include "dfft_long.h"
+#include "dfft_real.h"
 #include "dfft_zy.h"
 
 namespace dfft {
@@ -255,6 +256,13 @@ struct dfft_plan_s {
     // Rows of the exchange buffers rotated by rot_elems elements per X plane (RotMap, dfft_kernels.h): P > 1 fused plans whose
     // received planes are a power-of-two distance apart.  0 = off.
     int                     rot_elems = 0;
+    // real-to-complex / complex-to-real plans (dfft_plan_create_r2c): N[2] is the COMPLEX width n2/2 + 1 -- what the Y pass, the exchange
+    // and the X pass see -- and n2r the real length.  The Z rows run into / out of the plan's own complex intermediate cbuf ([xs][N1][cl.pitch],
+    // rows padded to whole cache lines; also the send buffer of the backward exchange): an R2C row is wider on output than on input.
+    bool                    r2c = false;
+    long long               n2r = 0;
+    void*                   cbuf = nullptr;
+    SlabLayout              cl{0, 0};
     std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
     int                     w_kept = -1;
     float                   w_final_ms = 0.f;  // the kept candidate re-timed after the others were freed
@@ -851,6 +859,70 @@ static int execute_backward(dfft_plan_s* p, bool sync) {
         if (!sync && p->timed && cp >= p->xs) DFFT_HIP_TRY(hipEventRecord(p->ev[5], p->stream));
         if (fused && p->wbuf) DFFT_TRY(fft_rows(ydst, ybuf, (int)n2, nx * n1, p->dtype, p->direction, p->stream, x0 * n1, 0, 1.0, ly, lnat, n1));
         else DFFT_TRY(fft_rows(ybuf, ybuf, (int)n2, nx * n1, p->dtype, p->direction, p->stream, x0 * n1));
+    }
+    DFFT_TRY(clk.end_stage());
+    return DFFT_OK;
+}
+
+// ---- real-to-complex / complex-to-real plans -------------------------------------------------------------------------------------
+// The Z rows of planes [x0, x0 + nx): R2C real slab `in` ([x][N1][n2r] reals) -> intermediate, or C2R intermediate -> real slab `out`.
+static int real_rows(dfft_plan_s* p, const void* in, void* out, int dir, long long x0, long long nx) {
+    const long long n1 = p->N[1];
+    const size_t    cs = elem_bytes(p->dtype), rs = cs / 2;
+    RealLaunch      L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = p->dtype;
+    L.n2 = (int)p->n2r;
+    L.dir = dir;
+    const size_t roff = (size_t)x0 * n1 * p->n2r * rs, coff = (size_t)x0 * p->cl.plane * cs;
+    L.in = (const char*)in + (dir > 0 ? roff : coff);
+    L.out = (char*)out + (dir > 0 ? coff : roff);
+    L.rows = nx * n1;
+    L.rows_per_plane = n1;
+    L.rpitch = p->n2r;
+    L.rplane = n1 * p->n2r;
+    L.cpitch = p->cl.pitch;
+    L.cplane = p->cl.plane;
+    L.scale = 1.0;  // dfft_plan_set_scale: folded into the X pass, as in C2C plans
+    return check_launch(launch_real_rows(L, p->stream), dir > 0 ? "R2C rows" : "C2R rows");
+}
+
+// Forward: R2C rows -> intermediate, Y columns (in place, or packing into the send buffer `out`) per cache chunk | exchange into
+// bufferDev1 | X pass -> out.  Backward: inverse X pass (into the intermediate, or the send buffer = the intermediate) | exchange into
+// bufferDev1 | per cache chunk: Y columns (in place, or unpacking bufferDev1 into the intermediate), then C2R rows -> out -- Z last, as
+// numpy's irfftn (inverse C2C along X and Y, then C2R along Z).
+static int execute_r2c(dfft_plan_s* p, bool sync) {
+    StageClock      clk{p, sync};
+    DFFT_TRY(clk.begin());
+    const void*     src = (p->flags & DFFT_PLAN_INPUT_FROM_IN) ? p->in : p->buf1;
+    const long long cp = p->chunk_planes > 0 ? p->chunk_planes : p->xs;
+    const bool      chunked = cp < p->xs;
+    const SlabLayout* lc = &p->cl;
+    if (p->direction == DFFT_FORWARD) {
+        for (long long x0 = 0; x0 < p->xs; x0 += cp) {
+            const long long nx = std::min(cp, p->xs - x0);
+            DFFT_TRY(real_rows(p, src, p->cbuf, +1, x0, nx));
+            if (p->exch) DFFT_TRY(launch_y(p, p->cbuf, p->buf2, true, true, x0, nx, chunked ? FFT_HINT_STREAM_OUT : 0, lc));
+            else DFFT_TRY(launch_y(p, p->cbuf, p->cbuf, true, false, x0, nx, 0, lc, lc));
+        }
+        DFFT_TRY(clk.end_stage());
+        DFFT_TRY(clk.end_stage());  // t1 folded into t0
+        if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
+        DFFT_TRY(clk.end_stage());
+        DFFT_TRY(launch_x(p, p->exch ? p->buf1 : p->cbuf, p->buf2, false, 0, p->exch ? nullptr : lc));
+        DFFT_TRY(clk.end_stage());
+        return DFFT_OK;
+    }
+    DFFT_TRY(launch_x(p, src, p->cbuf, false, 0, p->exch ? nullptr : lc));
+    DFFT_TRY(clk.end_stage());
+    if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
+    DFFT_TRY(clk.end_stage());
+    DFFT_TRY(clk.end_stage());  // unpack folded into the Y pass
+    for (long long x0 = 0; x0 < p->xs; x0 += cp) {
+        const long long nx = std::min(cp, p->xs - x0);
+        if (p->exch) DFFT_TRY(launch_y(p, p->buf1, p->cbuf, false, true, x0, nx, chunked ? FFT_HINT_STREAM_IN : 0, nullptr, lc));
+        else DFFT_TRY(launch_y(p, p->cbuf, p->cbuf, false, false, x0, nx, 0, lc, lc));
+        DFFT_TRY(real_rows(p, p->cbuf, p->buf2, -1, x0, nx));
     }
     DFFT_TRY(clk.end_stage());
     return DFFT_OK;
@@ -1579,6 +1651,161 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     return DFFT_OK;
 }
 
+int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices, int global_idx, long long* real_count, long long* complex_count) {
+    if (n0 < 1 || n1 < 1 || n2 < 2 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices)
+        return fail(DFFT_EINVAL, "dfft_r2c_counts: bad arguments");
+    const Slab      sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
+    const long long nh = n2 / 2 + 1, xs = sx.size(global_idx), ys = sy.size(global_idx);
+    if (xs < 0 || sy.size(total_devices - 1) < 1 || sx.size(total_devices - 1) < 1)
+        return fail(DFFT_EINVAL, "dfft_r2c_counts: slab decomposition leaves the last device empty");
+    // complex side: the transposed result [ys][nh][N0], and -- forward plans with an exchange -- the packed send layout [d][xs][yl_d][nh]
+    // the Y pass writes into the same buffer (the offsets of dfft_exchange_layout at width nh)
+    const long long send = (long long)(total_devices - 1) * xs * sy.blk * nh + xs * sy.size(total_devices - 1) * nh;
+    if (real_count) *real_count = xs * n1 * n2;
+    if (complex_count) *complex_count = std::max(ys * nh * n0, total_devices > 1 ? send : 0ll);
+    return DFFT_OK;
+}
+
+int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
+                         dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: null plan/in");
+    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: sizes must be positive");
+    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: dtype");
+    if (direction != DFFT_FORWARD && direction != DFFT_BACKWARD) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: direction");
+    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: device index");
+    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: a communicator is required for P > 1");
+    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: communicator size != P");
+    if (out == nullptr || out == in) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: real-to-complex plans are out of place (out != NULL, out != in)");
+    if (flags & ~DFFT_PLAN_INPUT_FROM_IN)
+        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: only DFFT_PLAN_DEFAULT and DFFT_PLAN_INPUT_FROM_IN are supported "
+                                       "(no OVERLAP, NATURAL or UNFUSED real-to-complex plans)");
+    if (!real_length_supported(n2))
+        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: N2 = " + std::to_string(n2) +
+                                           " -- the real axis must be even with N2/2 a supported length of at most 4096");
+    for (long long n : {n0, n1})
+        if (n > 4096 || !dfft_length_supported(n))
+            return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: FFT length " + std::to_string(n) +
+                                               " -- N0 and N1 must be single-pass lengths (products of 2, 3, 5, 7 up to 4096)");
+    long long rc_n = 0, cc_n = 0, rc_last = 0, cc_last = 0;
+    if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, global_idx, &rc_n, &cc_n)) return rc;
+    if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, total_devices - 1, &rc_last, &cc_last)) return rc;
+    long long rc0 = 0, cc0 = 0;
+    (void)dfft_r2c_counts(n0, n1, n2, total_devices, 0, &rc0, &cc0);
+    if (std::max(cc0, cc_last) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: more than 2^31 complex elements per device");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_plan_create_r2c: no HIP device visible (no CPU fallback)");
+
+    const long long nh = n2 / 2 + 1;
+    trace("dfft_plan_create_r2c", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
+    dfft_plan_s* p = new dfft_plan_s;
+    p->r2c = true;
+    p->n2r = n2;
+    p->N[0] = n0;
+    p->N[1] = n1;
+    p->N[2] = nh;
+    p->dtype = dtype;
+    p->direction = direction;
+    p->P = total_devices;
+    p->me = global_idx;
+    p->flags = flags;
+    p->is_last = (global_idx == total_devices - 1);
+    p->exch = total_devices > 1;
+    p->sx = make_slab(n0, total_devices);
+    p->sy = make_slab(n1, total_devices);
+    p->xs = p->sx.size(global_idx);
+    p->ys = p->sy.size(global_idx);
+    p->comm = comm;
+    p->grid_x = env_grid("DFFT_X_GRID");
+    p->grid_y = env_grid("DFFT_Y_GRID");
+    p->grid_z = env_grid("DFFT_Z_GRID");
+    p->host_timed = false;
+    for (double& t : p->host_t) t = 0;
+    p->max_count = cc_n;
+    p->in = in;
+    p->out = out;
+    p->inplace = false;
+    p->buf2 = out;
+    p->buf1 = nullptr;
+    p->stream = nullptr;
+    p->chunk_planes = 0;
+    for (auto& e : p->ev) e = nullptr;
+    const size_t cs = elem_bytes(dtype), rs = cs / 2;
+    // the intermediate: rows of nh bins padded to whole 128-byte lines (a pitch of nh alone puts the rows off line alignment)
+    const long long line = 128 / (long long)cs;
+    p->cl.pitch = (nh + line - 1) / line * line;
+    p->cl.plane = n1 * p->cl.pitch;
+    hipError_t e = hipGetDevice(&p->device);
+    if (e == hipSuccess && comm && comm_kind(comm) == 0 && total_devices > 1) {  // as dfft_plan_create: direct pushes to the peers
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess) {
+            for (int d = 0; d < ndev; ++d) {
+                int can = 0;
+                if (d == p->device || hipDeviceCanAccessPeer(&can, p->device, d) != hipSuccess || !can) continue;
+                if (hipDeviceEnablePeerAccess(d, 0) != hipSuccess) (void)hipGetLastError();
+            }
+        }
+    }
+    // bufferDev1: the real slab (R2C) or the complex input (C2R), and the receive buffer of the exchange -- the same size on every rank
+    // (pooled receive buffers of IPC communicators are matched by key and size)
+    const size_t b1 = (size_t)std::max({rc0 * rs, cc0 * cs, rc_last * rs, cc_last * cs});
+    const std::string rkey = "r2c:" + std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" + std::to_string(dtype) + ":" +
+                             std::to_string(total_devices);
+    if (e == hipSuccess && comm_recv_alloc(comm, rkey + ":b1", b1, &p->buf1) != DFFT_OK) e = hipErrorOutOfMemory;
+    // the intermediate, also the send buffer of the backward exchange ([N0][ys][nh])
+    const size_t cbytes = (size_t)std::max(p->xs * p->cl.plane, n0 * p->ys * nh) * cs;
+    if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    // input captured at plan time, on the plan's stream (see dfft_plan_create); exactly the caller's elements, nothing beyond them
+    const size_t ibytes = direction == DFFT_FORWARD ? (size_t)rc_n * rs : (size_t)(p->ys * nh * n0) * cs;
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyAsync(p->buf1, in, ibytes, hipMemcpyDeviceToDevice, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    for (auto& ev : p->ev)
+        if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) {
+        dfft_plan_destroy(p);
+        return fail(DFFT_EHIP, std::string("dfft_plan_create_r2c: ") + hipGetErrorString(e));
+    }
+    fill_exchange(p, p->xd, direction);  // at width nh
+    p->xd.sendbuf = direction == DFFT_FORWARD ? p->buf2 : p->cbuf;
+    p->xd.recvbuf = p->buf1;
+    p->xd.slot = p->xd2.slot = -1;
+    if (comm) {
+        const int rc = comm_register(comm, global_idx, p->xd.recvbuf, p->device, &p->xd.slot);
+        if (rc) {
+            dfft_plan_destroy(p);
+            return rc;
+        }
+    }
+    {
+        // Z+Y blocking for the 256 MiB Infinity Cache, sized on the intermediate's planes (the rule of two-launch C2C plans); DFFT_CHUNK_MB /
+        // DFFT_CHUNK_PLANES as there
+        long long   mb = 256;
+        const char* ce = getenv("DFFT_CHUNK_MB");
+        if (ce) mb = atoll(ce);
+        if (mb > 0) {
+            const long long plane_b = p->cl.plane * (long long)cs;
+            long long       fit = std::max(1ll, (mb << 20) / plane_b);
+            if (plane_b >= (8ll << 20) && fit > 1) --fit;
+            const long long nchunks = std::max(1ll, (p->xs + fit - 1) / fit);
+            p->chunk_planes = (p->xs + nchunks - 1) / nchunks;
+        }
+        const char* cpe = getenv("DFFT_CHUNK_PLANES");
+        if (cpe && atoll(cpe) > 0) p->chunk_planes = atoll(cpe);
+        if (p->chunk_planes >= p->xs) p->chunk_planes = 0;
+    }
+    // warm the twiddle caches so execute never allocates
+    for (long long n : {n0, n1, n2 / 2, n2}) {
+        const void* tw;
+        const int   rc = get_twiddles((int)n, dtype, &tw);
+        if (rc) {
+            dfft_plan_destroy(p);
+            return rc;
+        }
+    }
+    *plan = p;
+    return DFFT_OK;
+}
+
 int dfft_plan_set_scale(dfft_plan_t plan, double s) {
     if (!plan || !(s == s) || s == 0.0) return fail(DFFT_EINVAL, "dfft_plan_set_scale: bad arguments");
     plan->scale = s;
@@ -1610,7 +1837,8 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
     auto run = [&]() {
         t_plan_scratch = plan->lbuf;
         t_plan_zgrid = plan->grid_z;
-        const int r = (plan->flags & DFFT_PLAN_NATURAL) ? execute_natural(plan, sync)
+        const int r = plan->r2c ? execute_r2c(plan, sync)
+                      : (plan->flags & DFFT_PLAN_NATURAL) ? execute_natural(plan, sync)
                       : plan->direction == DFFT_FORWARD ? execute_forward(plan, sync)
                                                         : execute_backward(plan, sync);
         t_plan_scratch = nullptr;
@@ -1854,6 +2082,12 @@ int dfft_plan_tune(dfft_plan_t plan) {
 int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
     if (!plan || !buf || len < 64) return fail(DFFT_EINVAL, "dfft_plan_describe: bad arguments");
     const dfft_plan_s* p = plan;
+    if (p->r2c) {
+        snprintf(buf, (size_t)len, "pipeline=%s n2=%lld bins=%lld chunks=%lldx%lld intermediate_pitch=%lld", p->direction == DFFT_FORWARD ? "r2c" : "c2r",
+                 p->n2r, p->N[2], p->chunk_planes > 0 ? (p->xs + p->chunk_planes - 1) / p->chunk_planes : 1ll, p->chunk_planes > 0 ? p->chunk_planes : p->xs,
+                 p->cl.pitch);
+        return DFFT_OK;
+    }
     const bool         one = p->zy_on && !(p->flags & DFFT_PLAN_UNFUSED);
     const long long    cp = one ? zy_phase_planes(p, p->xs, p->exch && p->direction == DFFT_FORWARD) : (p->chunk_planes > 0 ? p->chunk_planes : p->xs);
     const long long    nch = cp > 0 ? (p->xs + cp - 1) / cp : 1;
@@ -1919,6 +2153,7 @@ int dfft_kernel_times(dfft_plan_t plan, double t[3]) {
     if (plan->host_timed || !plan->timed)
         return fail(DFFT_EINVAL, "dfft_kernel_times: needs an execute without DFFT_EXEC_SYNC_STAGES / DFFT_EXEC_NO_TIMING");
     if (plan->flags & DFFT_PLAN_UNFUSED) return fail(DFFT_EINVAL, "dfft_kernel_times: fused plans only");
+    if (plan->r2c) return fail(DFFT_EUNSUPPORTED, "dfft_kernel_times: not available for real-to-complex / complex-to-real plans");
     if (plan->zy_on)
         return fail(DFFT_EINVAL, "dfft_kernel_times: not available -- this plan runs its Z and Y passes inside ONE launch (no event between them); "
                                  "create it with DFFT_T0_ONE_LAUNCH=0 to time the passes separately");
@@ -1964,6 +2199,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     (void)comm_recv_free(plan->comm, plan->rbuf);
     if (plan->wbuf) slab_free(plan->wbuf);
     if (plan->lbuf) hipFree(plan->lbuf);
+    if (plan->cbuf) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
     if (plan->zy_err) hipHostFree(plan->zy_err);

@@ -148,6 +148,27 @@ int dfft_free(void* p, int flag);
  * total_devices == 1.  The calling thread's current HIP device is the plan's device. */
 int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                      void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* Real-to-complex (direction DFFT_FORWARD) / complex-to-real (DFFT_BACKWARD) slab plan: the C2C contract above with the last axis
+ * halved on the complex side, Nh = N2/2 + 1 (no counterpart in the reference, which is C2C only; heFFTe's fft3d_r2c).
+ *   R2C input : real    [x_local][N1][N2]   element (xi*N1 + y)*N2 + z
+ *   R2C output: complex [y_local][Nh][N0]   element (yy*Nh + kz)*N0 + kx  = numpy.fft.rfftn(x)[kx, y0 + yy, kz]
+ *   C2R       : the R2C output layout -> the R2C input layout, unnormalised: N0*N1*N2 * numpy.fft.irfftn(X, s=(N0, N1, N2)) for ANY input
+ *               (inverse C2C along X, then Y, then C2R along Z; the imaginary parts of the kz = 0 and kz = N2/2 bins are ignored).
+ * DFFT_F64: double reals / double[2] bins; DFFT_F32: float / float[2].  `in` and `out` hold at least the counts of dfft_r2c_counts
+ * (real side / complex side); the plan touches nothing beyond them.  Out of place only (out == NULL or out == in: DFFT_EINVAL).
+ * Supported: N2 even with N2/2 a length dfft_length_supported accepts, at most 4096 (so N2 <= 8192); N0, N1 single-pass lengths
+ * (<= 4096); flags DFFT_PLAN_DEFAULT or DFFT_PLAN_INPUT_FROM_IN; everything else DFFT_EUNSUPPORTED.  Arguments are checked before
+ * the device is queried.  Returns an ordinary plan: dfft_execute, dfft_plan_sync, dfft_plan_set_scale, dfft_stage_times,
+ * dfft_plan_buffer1 (the captured real slab of an R2C plan, the captured bins of a C2R plan), dfft_plan_result, dfft_plan_describe
+ * ("pipeline=r2c" / "pipeline=c2r") and dfft_plan_destroy work on it with the C2C semantics; dfft_plan_tune is a no-op (no hand-over
+ * buffer to place) and dfft_kernel_times returns DFFT_EUNSUPPORTED. */
+int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
+                         void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* Elements the caller's buffers of an r2c plan must hold on device global_idx: *real_count reals on the real side (R2C input / C2R
+ * output), *complex_count complex elements on the complex side (R2C output / C2R input) -- the result [y_local][Nh][N0] and, for P > 1,
+ * the packed send layout of the forward exchange, which the R2C plan writes into `out` before its result.  Pure host arithmetic. */
+int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices, int global_idx, long long* real_count,
+                    long long* complex_count);
 /* plan->bufferDev1, which the reference driver writes directly (fftSpeed3d_c2c.cpp:78). */
 void* dfft_plan_buffer1(dfft_plan_t plan);
 /* the buffer holding the result after execute (bufferDev2 = out, or in when in-place). */
