@@ -18,7 +18,7 @@ DRIVER_PATH = _PKG / "lib" / "distFFTOpt"
 FORWARD, BACKWARD = 1, -1
 ALLOC_HOST, ALLOC_DEV = 1, -1
 F64, F32 = 0, 1
-PLAN_DEFAULT, PLAN_UNFUSED, PLAN_INPUT_FROM_IN, PLAN_OVERLAP, PLAN_NATURAL = 0, 1, 2, 4, 8
+PLAN_DEFAULT, PLAN_UNFUSED, PLAN_INPUT_FROM_IN, PLAN_OVERLAP, PLAN_NATURAL, PLAN_ANY_LENGTH = 0, 1, 2, 4, 8, 16
 EXEC_ASYNC, EXEC_SYNC_STAGES, EXEC_PRINT, EXEC_NO_TIMING = 0, 1, 2, 4
 OK, EINVAL, EHIP, ERCCL, ENOGPU, ECOMM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -33,6 +33,8 @@ SIGNATURES = {
     "dfft_device_count": (C.c_int, []),
     "dfft_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "dfft_length_supported": (C.c_int, [_LL]),
+    "dfft_length_kind": (C.c_int, [_LL]),
+    "dfft_bluestein_length": (_LL, [_LL]),
     "dfft_proper_device_count": (C.c_int, [_LLP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dfft_local_count": (_LL, [_LLP, C.c_int, C.c_int]),
     "dfft_max_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
@@ -68,6 +70,7 @@ SIGNATURES = {
     "dfft_plan_destroy": (C.c_int, [_VP]),
     "dfft_fft1d_rows": (C.c_int, [_VP, _VP, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_fft1d_cols": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_fft1d_any": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_scale": (C.c_int, [_VP, _LL, C.c_int, C.c_double, _VP]),
     "dfft_trim": (C.c_int, []),
     "dfft_boot_init": (C.c_int, []),

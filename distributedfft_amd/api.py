@@ -12,8 +12,8 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import _lib as L
-from ._lib import (BACKWARD, EXEC_ASYNC, EXEC_NO_TIMING, EXEC_PRINT, EXEC_SYNC_STAGES, F32, F64, FORWARD, PLAN_DEFAULT,  # noqa: F401
-                   PLAN_INPUT_FROM_IN, PLAN_NATURAL, PLAN_OVERLAP, PLAN_UNFUSED, DfftError)
+from ._lib import (BACKWARD, EXEC_ASYNC, EXEC_NO_TIMING, EXEC_PRINT, EXEC_SYNC_STAGES, F32, F64, FORWARD, PLAN_ANY_LENGTH,  # noqa: F401
+                   PLAN_DEFAULT, PLAN_INPUT_FROM_IN, PLAN_NATURAL, PLAN_OVERLAP, PLAN_UNFUSED, DfftError)
 
 
 def _ll3(N: Sequence[int]):
@@ -390,6 +390,35 @@ def fft1d_cols(x, direction: int = FORWARD, out=None):
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_fft1d_cols(x.data_ptr(), out.data_ptr(), x.shape[1], x.shape[2], x.shape[0], _dtype_code(x),
                                          direction, None), "dfft_fft1d_cols")
+        torch.cuda.synchronize()
+    return out
+
+
+def length_kind(n: int) -> int:
+    """How length n is computed (dfft_length_kind): 1 single-pass, 2 four-step, 3 Bluestein (fft1d_any, PLAN_ANY_LENGTH), 0 none."""
+    return int(L.load().dfft_length_kind(int(n)))
+
+
+def bluestein_length(n: int) -> int:
+    """The padded length M >= 2n - 1 of a Bluestein transform of length n (dfft_bluestein_length); 0 if n is not of kind 3."""
+    return int(L.load().dfft_bluestein_length(int(n)))
+
+
+def fft1d_any(x, dim: int = -1, direction: int = FORWARD, out=None):
+    """Length-n FFT along dimension `dim` of a contiguous complex device tensor, for any n up to 2^23 (dfft_fft1d_any): the tensor is
+    seen as [batch][n][s] (batch = the dimensions before `dim`, s = those after it).  Kind 1 and 2 lengths give exactly the results of
+    fft1d_rows / fft1d_cols; other lengths run Bluestein's algorithm.  Unnormalised; out=x transforms in place."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1
+    out = _check_out(x, out)
+    d = dim % x.dim()
+    n = int(x.shape[d])
+    batch = math.prod(int(v) for v in x.shape[:d])
+    s = math.prod(int(v) for v in x.shape[d + 1:])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_fft1d_any(x.data_ptr(), out.data_ptr(), n, s, batch, _dtype_code(x), direction, None), "dfft_fft1d_any")
         torch.cuda.synchronize()
     return out
 

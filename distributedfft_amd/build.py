@@ -89,6 +89,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     # real-to-complex / complex-to-real rows: the same groups of lengths, plus the dispatcher (group NUM_INST_GROUPS)
     for g in range(NUM_INST_GROUPS + 1):
         units.append((CSRC / "dfft_real.hip", OBJ / f"dfft_real_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # Bluestein (any-length) transforms: the fused kernels of the same groups of padded lengths, plus the dispatcher (group NUM_INST_GROUPS)
+    for g in range(NUM_INST_GROUPS + 1):
+        units.append((CSRC / "dfft_bluestein.hip", OBJ / f"dfft_bluestein_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
     units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
     units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))

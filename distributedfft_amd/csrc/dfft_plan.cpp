@@ -26,6 +26,7 @@
 #include <tuple>
 #include <thread>
 
+#include "dfft_bluestein.h"
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
@@ -131,10 +132,60 @@ struct SlabLayout {
 static thread_local void* t_plan_scratch = nullptr;
 static thread_local int   t_plan_zgrid = 0;  // the executing plan's cap on its row launches' grids (dfft_plan_s::grid_z)
 
+// Bluestein axes of the plan that is executing on this thread (set by dfft_execute): the tables of its kind-3 axes, built when the
+// plan was created, and the plan's scratch for the multi-pass form -- so that an execute allocates nothing
+struct PlanBluestein {
+    std::vector<BluesteinTablesPtr> tables;
+    void*                           scratch = nullptr;
+    size_t                          bytes = 0;
+    bool                            fused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
+};
+static thread_local const PlanBluestein* t_plan_bs = nullptr;
+
+// dfft_length_kind without the range checks' cost on the hot path: single-pass lengths answer at the first test
+static int length_kind(long long n) {
+    if (n >= 1 && n <= 4096 && fft_length_supported((int)n)) return 1;
+    if (n < 1 || n >= (1ll << 30)) return 0;
+    int a, b;
+    if (long_split(n, &a, &b)) return 2;
+    return n <= kBluesteinMaxLength ? 3 : 0;
+}
+
+// Length-n Bluestein transforms of data[batch][n][s] (dfft_bluestein.hip): with the executing plan's tables and scratch, or -- plan-less
+// callers -- the cached tables and the per-(device, stream) scratch lease of the four-step transforms
+static int bluestein_pass(const void* in, void* out, long long n, long long s, long long batch, int dtype, int dir, double scale,
+                          hipStream_t st) {
+    if (const PlanBluestein* pb = t_plan_bs) {
+        for (const auto& t : pb->tables)
+            if (t->n == n && t->dtype == dtype && t->dir == dir) return bluestein_fft(*t, in, out, s, batch, scale, pb->fused, pb->scratch, pb->bytes, st);
+        return fail(DFFT_EINVAL, "Bluestein pass: the plan has no tables for length " + std::to_string(n));
+    }
+    BluesteinTablesPtr t;
+    int                rc = bluestein_tables(n, dtype, dir, &t);
+    if (rc) return rc;
+    const bool       fused = bluestein_fused_env();
+    const size_t     need = bluestein_scratch_bytes(*t, s, batch, fused);
+    LongScratchLease lease = nullptr;
+    void*            scr = nullptr;
+    if (need) {
+        scr = long_scratch(need, st, &lease);
+        if (!scr) return fail(DFFT_EHIP, "Bluestein pass: cannot allocate the scratch buffer");
+    }
+    rc = bluestein_fft(*t, in, out, s, batch, scale, fused, scr, need, st);
+    long_scratch_release(lease);
+    return rc;
+}
+
 // contiguous rows: `rows` FFTs of length n; row pitch n, or (lin/lout given) rows_per_plane rows per plane in the given layouts
 static int fft_rows(const void* in, void* out, int n, long long rows, int dtype, int dir, hipStream_t s,
                     long long first_row = 0, int hints = 0, double scale = 1.0, const SlabLayout* lin = nullptr,
                     const SlabLayout* lout = nullptr, long long rows_per_plane = 0, void* long_scratch_buf = nullptr, int grid_limit = 0) {
+    if (length_kind(n) == 3) {  // Bluestein (DFFT_PLAN_ANY_LENGTH plans, which run un-fused): plain contiguous rows only
+        if (lin || lout) return fail(DFFT_EINVAL, "fft_rows: Bluestein axes use the natural layout");
+        if (rows <= 0) return DFFT_OK;
+        const size_t off = (size_t)first_row * n * elem_bytes(dtype);
+        return bluestein_pass((const char*)in + off, (char*)out + off, n, 1, rows, dtype, dir, scale, s);
+    }
     if (n > 4096) {  // beyond the single-pass range: four-step decomposition (dfft_long.hip), plain contiguous rows only
         if (lin || lout) return fail(DFFT_EINVAL, "fft_rows: long axes use the natural layout");
         if (rows <= 0) return DFFT_OK;
@@ -227,6 +278,8 @@ struct dfft_plan_s {
     // contiguous rows and natural-layout columns need the four-step form then) and owns the scratch slab it needs
     bool                    long_axis = false;
     void*                   lbuf = nullptr;
+    // axes of dfft_length_kind 3 (DFFT_PLAN_ANY_LENGTH): Bluestein transforms on the un-fused structure, tables and scratch owned here
+    PlanBluestein           bs;
     // Placement of the hand-over buffer (dfft_plan_tune).  The X pass runs 5-8 % faster when the buffer it reads and the
     // buffer it writes lie in different regions of the device's physical memory (regions are 4 ... 70 GiB long, consecutive
     // allocations usually share one; profiles/r03/README.md section 1, tools/xprobe.hip), so tuning times the X-pass kernel
@@ -330,6 +383,12 @@ static int launch_y(dfft_plan_s* p, const void* in, void* out, bool packed_side_
                     long long nx, int hints = 0, const SlabLayout* lay_in = nullptr, const SlabLayout* lay_out = nullptr) {
     const int       n1 = (int)p->N[1];
     const long long n2 = p->N[2];
+    if (length_kind(n1) == 3) {  // Bluestein: natural layout on both sides only (such plans run un-fused)
+        auto natural = [&](const SlabLayout* l) { return !l || (l->pitch == n2 && l->plane == (long long)n1 * n2); };
+        if (use_packed || !natural(lay_in) || !natural(lay_out)) return fail(DFFT_EINVAL, "Y pass: a Bluestein axis needs the natural layout");
+        const size_t off = (size_t)x0 * n1 * n2 * elem_bytes(p->dtype);
+        return bluestein_pass((const char*)in + off, (char*)out + off, n1, n2, nx, p->dtype, p->direction, 1.0, p->stream);
+    }
     if (n1 > 4096) {  // four-step form: natural layout on both sides only (long-axis plans run un-fused)
         auto natural = [&](const SlabLayout* l) { return !l || (l->pitch == n2 && l->plane == (long long)n1 * n2); };
         if (use_packed || !natural(lay_in) || !natural(lay_out)) return fail(DFFT_EINVAL, "Y pass: a long axis needs the natural layout");
@@ -1107,6 +1166,10 @@ int dfft_length_supported(long long n) {
     return long_split(n, &a, &b) ? 1 : 0;  // two-pass (four-step) plans above 4096
 }
 
+int dfft_length_kind(long long n) { return length_kind(n); }
+
+long long dfft_bluestein_length(long long n) { return length_kind(n) == 3 ? bluestein_padded_length(n) : 0; }
+
 int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,
                              int* new_total, int* new_in_rank) {
     if (!N || !new_total || !new_in_rank || nranks < 1 || rank < 0 || rank >= nranks || ini_devices_in_rank < 1)
@@ -1262,14 +1325,24 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, "dfft_plan_create: a communicator is required for P > 1");
     if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, "dfft_plan_create: communicator size != P");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_plan_create: no HIP device visible (no CPU fallback)");
-    for (long long n : {n0, n1, n2})
+    bool bluestein_axis = false;
+    for (long long n : {n0, n1, n2}) {
+        if ((flags & DFFT_PLAN_ANY_LENGTH) && length_kind(n) == 3) {
+            bluestein_axis = true;
+            continue;
+        }
         if (!dfft_length_supported(n))
-            return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: FFT length " + std::to_string(n) + " has no gfx950 plan");
+            return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: FFT length " + std::to_string(n) + " has no gfx950 plan" +
+                                               ((flags & DFFT_PLAN_ANY_LENGTH) ? "" : " (DFFT_PLAN_ANY_LENGTH accepts any length up to 2^23)"));
+    }
 
-    const bool long_axis = n0 > 4096 || n1 > 4096 || n2 > 4096;
+    const bool long_axis = (n0 > 4096 && length_kind(n0) == 2) || (n1 > 4096 && length_kind(n1) == 2) || (n2 > 4096 && length_kind(n2) == 2);
     if (long_axis && (flags & DFFT_PLAN_NATURAL))
         return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: natural-order plans need single-pass axis lengths (<= 4096)");
-    if (long_axis) flags = (flags | DFFT_PLAN_UNFUSED) & ~DFFT_PLAN_OVERLAP;  // the four-step axes run in the reference's stage structure
+    if (bluestein_axis && (flags & DFFT_PLAN_NATURAL))
+        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: natural-order plans need 7-smooth axis lengths (no Bluestein axis)");
+    // the four-step and Bluestein axes run in the reference's stage structure
+    if (long_axis || bluestein_axis) flags = (flags | DFFT_PLAN_UNFUSED) & ~DFFT_PLAN_OVERLAP;
     trace("dfft_plan_create", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
     dfft_plan_s* p = new dfft_plan_s;
     p->long_axis = long_axis;
@@ -1637,9 +1710,36 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
             return fail(DFFT_EHIP, std::string("dfft_plan_create: ") + hipGetErrorString(e));
         }
     }
+    if (bluestein_axis) {
+        // the tables of every Bluestein axis, and the scratch of the passes that use the multi-pass form: Z rows (xs * N1 of them), Y columns
+        // (N2 wide, xs planes), X rows of the un-fused X pass (ys * N2)
+        p->chunk_planes = 0;
+        p->bs.fused = bluestein_fused_env();
+        const long long passes[3][3] = {{n0, 1, p->ys * n2}, {n1, n2, p->xs}, {n2, 1, p->xs * n1}};  // (n, s, batch) per axis
+        size_t          need = 0;
+        for (const auto& ps : passes) {
+            if (length_kind(ps[0]) != 3) continue;
+            BluesteinTablesPtr t;
+            const int          rc = bluestein_tables(ps[0], dtype, direction, &t);
+            if (rc) {
+                dfft_plan_destroy(p);
+                return rc;
+            }
+            p->bs.tables.push_back(t);
+            need = std::max(need, bluestein_scratch_bytes(*t, ps[1], ps[2], p->bs.fused));
+        }
+        if (need) {
+            e = hipMalloc(&p->bs.scratch, need);
+            if (e != hipSuccess) {
+                dfft_plan_destroy(p);
+                return fail(DFFT_EHIP, std::string("dfft_plan_create: Bluestein scratch: ") + hipGetErrorString(e));
+            }
+            p->bs.bytes = need;
+        }
+    }
     // warm the twiddle caches so execute never allocates
     for (long long n : {n0, n1, n2}) {
-        if (n > 4096) continue;  // long axes: their factors' tables are built on first use
+        if (n > 4096 || length_kind(n) == 3) continue;  // long axes: their factors' tables are built on first use; Bluestein axes: above
         const void* tw;
         int         rc = get_twiddles((int)n, dtype, &tw);
         if (rc) {
@@ -1837,12 +1937,14 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
     auto run = [&]() {
         t_plan_scratch = plan->lbuf;
         t_plan_zgrid = plan->grid_z;
+        t_plan_bs = plan->bs.tables.empty() ? nullptr : &plan->bs;
         const int r = plan->r2c ? execute_r2c(plan, sync)
                       : (plan->flags & DFFT_PLAN_NATURAL) ? execute_natural(plan, sync)
                       : plan->direction == DFFT_FORWARD ? execute_forward(plan, sync)
                                                         : execute_backward(plan, sync);
         t_plan_scratch = nullptr;
         t_plan_zgrid = 0;
+        t_plan_bs = nullptr;
         return r;
     };
     const bool zy_used = plan->zy_on;
@@ -2098,6 +2200,14 @@ int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
              (p->zy_on && fused) ? "one-launch" : "two-launches-per-chunk", (p->zy_on && fused && p->zy_lazy) ? "-lazy" : "", nch, cp,
              (fused && p->wbuf && !p->exch) ? "padded-buffer" : "bufferDev1", p->rot_elems, p->part_planes, p->ycuts, (p->zy_on && fused && p->zy_part_done) ? 1 : 0, p->w_kept >= 0 ? 1 : 0,
              (p->x_hints & FFT_HINT_HALF_PREFETCH) ? "half-prefetch" : ((p->x_hints & FFT_HINT_EARLY_WAIT) ? "early-wait" : "default"));
+    for (int a = 0; a < 3; ++a) {  // Bluestein axes: "bluestein_axis0=n11/M24/fused"
+        if (length_kind(p->N[a]) != 3 || p->bs.tables.empty()) continue;
+        const size_t used = strlen(buf);
+        if (used + 1 >= (size_t)len) break;
+        const bool fused = p->N[a] == 1 || (p->bs.fused && p->N[a] <= kBluesteinFusedMaxLength);
+        snprintf(buf + used, (size_t)len - used, " bluestein_axis%d=n%lld/M%lld/%s", a, p->N[a], bluestein_padded_length(p->N[a]),
+                 fused ? "fused" : "multi-pass");
+    }
     return DFFT_OK;
 }
 
@@ -2199,6 +2309,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     (void)comm_recv_free(plan->comm, plan->rbuf);
     if (plan->wbuf) slab_free(plan->wbuf);
     if (plan->lbuf) hipFree(plan->lbuf);
+    if (plan->bs.scratch) hipFree(plan->bs.scratch);
     if (plan->cbuf) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
@@ -2402,6 +2513,7 @@ int dfft_fft2d_batch_status(void* stream) {
 
 int dfft_trim(void) {
     long_scratch_trim();
+    bluestein_trim();
     zy2d_trim();
     return DFFT_OK;
 }
@@ -2412,6 +2524,18 @@ int dfft_scale(void* data, long long count, int dtype, double s, void* stream) {
     hipError_t e = launch_scale(dtype, data, count, s, (hipStream_t)stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_scale: ") + hipGetErrorString(e));
     return DFFT_OK;
+}
+
+int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream) {
+    if (!in || !out || batch < 0 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
+        return fail(DFFT_EINVAL, "dfft_fft1d_any: bad arguments");
+    const int kind = length_kind(n);
+    if (kind == 0) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_any: length " + std::to_string(n) + " is outside every form (at most 2^23, or a four-step length)");
+    if (kind != 3)  // single-pass and four-step lengths: exactly the existing entry points
+        return s == 1 ? dfft_fft1d_rows(in, out, n, batch, dtype, direction, stream) : dfft_fft1d_cols(in, out, n, s, batch, dtype, direction, stream);
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_any: no HIP device visible (no CPU fallback)");
+    if (batch == 0) return DFFT_OK;
+    return bluestein_pass(in, out, n, s, batch, dtype, direction, 1.0, (hipStream_t)stream);
 }
 
 int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,

@@ -54,6 +54,10 @@ extern "C" {
 #define DFFT_PLAN_NATURAL 8u        /* input AND output in the natural X-slab layout [x_local][N1][N2] (both directions):
                                        the un-transposed output the reference declares (fft_mpi_local_size_3d,
                                        fft_mpi_3d_api.h:73) but never implements.  Costs a second all-to-all when P > 1. */
+#define DFFT_PLAN_ANY_LENGTH 16u    /* also accept axes of dfft_length_kind 3 (Bluestein, see dfft_fft1d_any).  A plan with such an
+                                       axis runs the un-fused stage structure like a four-step plan: UNFUSED is forced, OVERLAP
+                                       dropped, NATURAL rejected (DFFT_EUNSUPPORTED).  Without a kind-3 axis the flag changes nothing
+                                       (bit-identical results).  Not accepted by dfft_plan_create_r2c. */
 
 /* execute flags */
 #define DFFT_EXEC_ASYNC 0u          /* enqueue on the plan's stream and return */
@@ -80,6 +84,13 @@ int dfft_device_pci_bus_id(int device, char* buf, int len);
  * and, above 4096, every product of two tuned lengths up to 2^24 (two-pass "four-step" plans, csrc/dfft_long.hip; the
  * reference's multi-upload plans, templateFFT.cpp:3972-4106).  3D plans with such an axis run the un-fused stage structure. */
 int dfft_length_supported(long long n);
+/* How length n is computed: 1 single-pass (7-smooth, n <= 4096: where dfft_length_supported is 1 up to 4096), 2 four-step (the rest of
+ * dfft_length_supported), 3 Bluestein (every other n from 1 to 2^23, n = 1 included: a scaled copy; dfft_fft1d_any and plans with
+ * DFFT_PLAN_ANY_LENGTH), 0 none.  Pure host arithmetic. */
+int dfft_length_kind(long long n);
+/* The padded length M >= 2n - 1 a Bluestein transform of length n runs on (1 for n = 1; the smallest tuned single-pass length for
+ * n <= 2048, the smallest four-step length above), or 0 if n is not of kind 3.  Pure host arithmetic. */
+long long dfft_bluestein_length(long long n);
 
 /* ---- slab bookkeeping: pure host arithmetic, callable without a GPU ------------------------------------------------ */
 /* getProperDeviceNum (fft_mpi_3d_api.cpp:232-272): shrink the device count when N0 % P != 0 so every device but the
@@ -228,6 +239,15 @@ int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype
 int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,
                     void* stream);
 
+/* Length-n C2C FFT along the middle axis of data[batch][n][s] (s = 1: contiguous rows), unnormalised, in place (out == in) or out of
+ * place, for ANY n of kind 1, 2 or 3 (dfft_length_kind).  Kinds 1 and 2 run exactly what dfft_fft1d_rows (s = 1) / dfft_fft1d_cols
+ * run (bit-identical results).  Kind 3 runs Bluestein's chirp-z algorithm (csrc/dfft_bluestein.hip): for n <= 2048 one launch that
+ * keeps the padded M-point transforms in registers and LDS (the HBM traffic of an n-point transform), above that a multi-pass form on
+ * the four-step transforms with scratch from the same per-(device, stream) buffer the four-step lengths use.  The chirp and B^ tables
+ * are built on the first call for (device, n, dtype, direction) and cached; dfft_trim frees them and the scratch.
+ * DFFT_BLUESTEIN_FUSED=0 (read per call) runs the multi-pass form for n <= 2048 as well (A/B and measurement switch). */
+int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream);
+
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
  * `batch` planes of [n1][n2] complex elements (n2 contiguous), each transformed along both axes, in place (out == in) or out
@@ -244,7 +264,8 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
  * for the stream.  Each failure is reported once, here or by the next dfft_fft2d_batch call on that stream. */
 int dfft_fft2d_batch_status(void* stream);
 
-/* Frees the scratch buffers the 1-D entry points cache per (device, stream) for lengths above 4096 (four-step transforms) and the
+/* Frees the scratch buffers the 1-D entry points cache per (device, stream) for lengths above 4096 (four-step transforms) and for
+ * Bluestein transforms, the cached Bluestein tables (a plan keeps those of its own axes until it is destroyed) and the
  * control blocks of dfft_fft2d_batch.
  * Buffers in use by a call in progress are left alone.  No counterpart in the reference. */
 int dfft_trim(void);

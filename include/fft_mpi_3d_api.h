@@ -199,8 +199,11 @@ inline fft_mpi_3d_plan_p fft_mpi_plan_dft_c2c_3d(longInt64 n0, longInt64 n1, lon
     }
     // DFFT_OVERLAP=1: forward plans pipeline the exchange behind t0 and t3 behind the tail of the exchange (the printed
     // t2 is then the exposed remainder).  Default: the reference's serial t0 -> t1 -> t2 -> t3 stage structure.
+    // DFFT_ANY_LENGTH=1: also accept axis lengths that are not 7-smooth (Bluestein, DFFT_PLAN_ANY_LENGTH).  Default off.
     const char*    ov = getenv("DFFT_OVERLAP");
-    const unsigned plan_flags = (ov && *ov && *ov != '0' && totalDevCount > 1) ? DFFT_PLAN_OVERLAP : DFFT_PLAN_DEFAULT;
+    const char*    al = getenv("DFFT_ANY_LENGTH");
+    const unsigned plan_flags = ((ov && *ov && *ov != '0' && totalDevCount > 1) ? DFFT_PLAN_OVERLAP : DFFT_PLAN_DEFAULT) |
+                                ((al && *al && *al != '0') ? DFFT_PLAN_ANY_LENGTH : 0u);
     DFFT_CHECK(dfft_plan_create(&plan->handle, n0, n1, n2, DFFT_F64, direction, in, out, c, plan->globalDevIdx,
                                 totalDevCount, plan_flags));
     // plan-time placement of the internal hand-over buffer (dfft_plan_tune, a few X-pass kernel launches): done here so that
