@@ -35,6 +35,7 @@ SIGNATURES = {
     "dfft_length_supported": (C.c_int, [_LL]),
     "dfft_length_kind": (C.c_int, [_LL]),
     "dfft_bluestein_length": (_LL, [_LL]),
+    "dfft_real_form": (C.c_int, [_LL]),
     "dfft_proper_device_count": (C.c_int, [_LLP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dfft_local_count": (_LL, [_LLP, C.c_int, C.c_int]),
     "dfft_max_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
@@ -52,6 +53,7 @@ SIGNATURES = {
     "dfft_free": (C.c_int, [_VP, C.c_int]),
     "dfft_plan_create": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_plan_create_r2c": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
+    "dfft_plan_create_r2c_any": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_r2c_counts": (C.c_int, [_LL, _LL, _LL, C.c_int, C.c_int, _LLP, _LLP]),
     "dfft_plan_buffer1": (_VP, [_VP]),
     "dfft_plan_result": (_VP, [_VP]),
@@ -71,6 +73,7 @@ SIGNATURES = {
     "dfft_fft1d_rows": (C.c_int, [_VP, _VP, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_fft1d_cols": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_fft1d_any": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rfft1d": (C.c_int, [_VP, _VP, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_scale": (C.c_int, [_VP, _LL, C.c_int, C.c_double, _VP]),
     "dfft_trim": (C.c_int, []),
     "dfft_boot_init": (C.c_int, []),

@@ -287,7 +287,7 @@ class PlanR2C(Plan):
     the bins (BACKWARD)."""
 
     def __init__(self, n0, n1, n2, inp, out, comm: Optional[Comm], global_idx: int, total_devices: int, direction: int,
-                 flags: int = PLAN_DEFAULT):
+                 flags: int = PLAN_DEFAULT, any_length: bool = False):
         import torch
         lib = L.load()
         if inp is None or out is None:
@@ -314,9 +314,10 @@ class PlanR2C(Plan):
         self.handle = C.c_void_p()
         torch.cuda.synchronize(inp.device)
         with torch.cuda.device(inp.device):
-            L.check(lib.dfft_plan_create_r2c(C.byref(self.handle), n0, n1, n2, self.dtype, direction, inp.data_ptr(), out.data_ptr(),
-                                             comm.handle if comm is not None else None, global_idx, total_devices, flags),
-                    "dfft_plan_create_r2c")
+            # any_length: the real axis may be of any real_form != 0 (dfft_plan_create_r2c_any); otherwise dfft_plan_create_r2c's limits
+            create, name = (lib.dfft_plan_create_r2c_any, "dfft_plan_create_r2c_any") if any_length else (lib.dfft_plan_create_r2c, "dfft_plan_create_r2c")
+            L.check(create(C.byref(self.handle), n0, n1, n2, self.dtype, direction, inp.data_ptr(), out.data_ptr(),
+                           comm.handle if comm is not None else None, global_idx, total_devices, flags), name)
         self.device = inp.device
 
     def load_input(self, src) -> None:
@@ -419,6 +420,58 @@ def fft1d_any(x, dim: int = -1, direction: int = FORWARD, out=None):
     s = math.prod(int(v) for v in x.shape[d + 1:])
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_fft1d_any(x.data_ptr(), out.data_ptr(), n, s, batch, _dtype_code(x), direction, None), "dfft_fft1d_any")
+        torch.cuda.synchronize()
+    return out
+
+
+def real_form(n: int) -> int:
+    """How a real transform of length n is computed (dfft_real_form): 1 half-length, 2 paired single-pass, 3 paired four-step /
+    Bluestein, 0 none."""
+    return int(L.load().dfft_real_form(int(n)))
+
+
+def rfft1d(x, out=None):
+    """numpy.fft.rfft along the last dimension of a contiguous float64 / float32 device tensor [..., n] -> complex128 / complex64
+    [..., n//2 + 1], for any n with real_form(n) != 0 (dfft_rfft1d).  Unnormalised, out of place."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32)
+    n = int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    shape = tuple(x.shape[:-1]) + (n // 2 + 1,)
+    if out is None:
+        out = torch.empty(shape, dtype=cdt, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == cdt and out.device == x.device and out.is_contiguous(), \
+        f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
+    batch = math.prod(int(v) for v in x.shape[:-1])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rfft1d(x.data_ptr(), out.data_ptr(), n, batch, F64 if x.dtype == torch.float64 else F32, FORWARD, None),
+                "dfft_rfft1d")
+        torch.cuda.synchronize()
+    return out
+
+
+def irfft1d(X, n: int, out=None):
+    """n * numpy.fft.irfft(X, n) along the last dimension of a contiguous complex128 / complex64 device tensor [..., n//2 + 1] -> float64
+    / float32 [..., n] (dfft_rfft1d, backward): unnormalised; the imaginary parts of bin 0 and, n even, bin n/2 are ignored.  X is left
+    untouched."""
+    import math
+
+    import torch
+    assert X.is_cuda and X.is_contiguous() and X.dim() >= 1 and X.dtype in (torch.complex128, torch.complex64)
+    n = int(n)
+    assert int(X.shape[-1]) == n // 2 + 1, f"irfft1d: the last dimension must hold n//2 + 1 = {n // 2 + 1} bins, got {X.shape[-1]}"
+    rdt = torch.float64 if X.dtype == torch.complex128 else torch.float32
+    shape = tuple(X.shape[:-1]) + (n,)
+    if out is None:
+        out = torch.empty(shape, dtype=rdt, device=X.device)
+    assert tuple(out.shape) == shape and out.dtype == rdt and out.device == X.device and out.is_contiguous(), \
+        f"out must be a contiguous {rdt} tensor of shape {shape} on {X.device}"
+    batch = math.prod(int(v) for v in X.shape[:-1])
+    with torch.cuda.device(X.device):
+        L.check(L.load().dfft_rfft1d(X.data_ptr(), out.data_ptr(), n, batch, F64 if rdt == torch.float64 else F32, BACKWARD, None),
+                "dfft_rfft1d")
         torch.cuda.synchronize()
     return out
 

@@ -92,6 +92,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     # Bluestein (any-length) transforms: the fused kernels of the same groups of padded lengths, plus the dispatcher (group NUM_INST_GROUPS)
     for g in range(NUM_INST_GROUPS + 1):
         units.append((CSRC / "dfft_bluestein.hip", OBJ / f"dfft_bluestein_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # any-length real rows (two-for-one pairs): the fused kernels of the odd tuned lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        units.append((CSRC / "dfft_real_pair.hip", OBJ / f"dfft_real_pair_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
     units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
     units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstdint>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -30,6 +31,7 @@
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
+#include "dfft_real_pair.h"
 #include "dfft_zy.h"
 
 namespace dfft {
@@ -149,6 +151,14 @@ static int length_kind(long long n) {
     int a, b;
     if (long_split(n, &a, &b)) return 2;
     return n <= kBluesteinMaxLength ? 3 : 0;
+}
+
+// dfft_real_form: 1 the half-length kernels of dfft_real.hip (n even, n/2 single-pass); 2 two-for-one pairs on an n-point single-pass
+// transform (the odd 7-smooth n <= 4096, and n = 2); 3 two-for-one pairs on the n-point four-step or Bluestein transform; 0 none
+static int real_form(long long n) {
+    if (real_length_supported(n)) return 1;
+    const int k = length_kind(n);
+    return k == 1 ? 2 : (k == 0 ? 0 : 3);
 }
 
 // Length-n Bluestein transforms of data[batch][n][s] (dfft_bluestein.hip): with the executing plan's tables and scratch, or -- plan-less
@@ -316,6 +326,14 @@ struct dfft_plan_s {
     long long               n2r = 0;
     void*                   cbuf = nullptr;
     SlabLayout              cl{0, 0};
+    // dfft_plan_create_r2c_any: the form of the real axis (dfft_real_form; 1 = exactly dfft_plan_create_r2c's plan) and, forms 2 / 3, the
+    // two-for-one rows' Bluestein tables (Bluestein n2r only) and scratch, sized for one cache chunk of rows (dfft_real_pair.hip)
+    bool                    real_any = false;
+    int                     real_form = 1;
+    BluesteinTablesPtr      rtab;
+    bool                    rfused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
+    void*                   rscratch = nullptr;
+    size_t                  rscratch_bytes = 0;
     std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
     int                     w_kept = -1;
     float                   w_final_ms = 0.f;  // the kept candidate re-timed after the others were freed
@@ -928,6 +946,23 @@ static int execute_backward(dfft_plan_s* p, bool sync) {
 static int real_rows(dfft_plan_s* p, const void* in, void* out, int dir, long long x0, long long nx) {
     const long long n1 = p->N[1];
     const size_t    cs = elem_bytes(p->dtype), rs = cs / 2;
+    if (p->real_form != 1) {  // two-for-one pairs (rows pair up across plane boundaries)
+        RealPairLaunch R;
+        std::memset(&R, 0, sizeof(R));
+        R.dtype = p->dtype;
+        R.n = p->n2r;
+        R.dir = dir;
+        const size_t roff = (size_t)x0 * n1 * p->n2r * rs, coff = (size_t)x0 * p->cl.plane * cs;
+        R.in = (const char*)in + (dir > 0 ? roff : coff);
+        R.out = (char*)out + (dir > 0 ? coff : roff);
+        R.rows = nx * n1;
+        R.rows_per_plane = n1;
+        R.rpitch = p->n2r;
+        R.rplane = n1 * p->n2r;
+        R.cpitch = p->cl.pitch;
+        R.cplane = p->cl.plane;
+        return real_pair_rows(R, p->rtab.get(), p->rfused, p->rscratch, p->rscratch_bytes, p->stream);
+    }
     RealLaunch      L;
     std::memset(&L, 0, sizeof(L));
     L.dtype = p->dtype;
@@ -1766,39 +1801,48 @@ int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices,
     return DFFT_OK;
 }
 
-int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                         dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
-    if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: null plan/in");
-    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: sizes must be positive");
-    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: dtype");
-    if (direction != DFFT_FORWARD && direction != DFFT_BACKWARD) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: direction");
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: device index");
-    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: a communicator is required for P > 1");
-    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: communicator size != P");
-    if (out == nullptr || out == in) return fail(DFFT_EINVAL, "dfft_plan_create_r2c: real-to-complex plans are out of place (out != NULL, out != in)");
+}  // extern "C"
+
+// dfft_plan_create_r2c (any = false) and dfft_plan_create_r2c_any (any = true: the real axis of any dfft_real_form != 0)
+static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
+                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any) {
+    const std::string fn = any ? "dfft_plan_create_r2c_any" : "dfft_plan_create_r2c";
+    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
+    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
+    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
+    if (direction != DFFT_FORWARD && direction != DFFT_BACKWARD) return fail(DFFT_EINVAL, fn + ": direction");
+    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
+    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
+    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
+    if (out == nullptr || out == in) return fail(DFFT_EINVAL, fn + ": real-to-complex plans are out of place (out != NULL, out != in)");
     if (flags & ~DFFT_PLAN_INPUT_FROM_IN)
-        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: only DFFT_PLAN_DEFAULT and DFFT_PLAN_INPUT_FROM_IN are supported "
+        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT and DFFT_PLAN_INPUT_FROM_IN are supported "
                                        "(no OVERLAP, NATURAL or UNFUSED real-to-complex plans)");
-    if (!real_length_supported(n2))
-        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: N2 = " + std::to_string(n2) +
+    const int form = any ? real_form(n2) : 1;
+    if (any && form == 0)
+        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) + " -- no real form (at most 2^23, or a four-step length)");
+    if (!any && !real_length_supported(n2))
+        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) +
                                            " -- the real axis must be even with N2/2 a supported length of at most 4096");
     for (long long n : {n0, n1})
         if (n > 4096 || !dfft_length_supported(n))
-            return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: FFT length " + std::to_string(n) +
+            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) +
                                                " -- N0 and N1 must be single-pass lengths (products of 2, 3, 5, 7 up to 4096)");
     long long rc_n = 0, cc_n = 0, rc_last = 0, cc_last = 0;
     if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, global_idx, &rc_n, &cc_n)) return rc;
     if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, total_devices - 1, &rc_last, &cc_last)) return rc;
     long long rc0 = 0, cc0 = 0;
     (void)dfft_r2c_counts(n0, n1, n2, total_devices, 0, &rc0, &cc0);
-    if (std::max(cc0, cc_last) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, "dfft_plan_create_r2c: more than 2^31 complex elements per device");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_plan_create_r2c: no HIP device visible (no CPU fallback)");
+    if (std::max(cc0, cc_last) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, fn + ": more than 2^31 complex elements per device");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
 
     const long long nh = n2 / 2 + 1;
     trace("dfft_plan_create_r2c", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
     dfft_plan_s* p = new dfft_plan_s;
     p->r2c = true;
     p->n2r = n2;
+    p->real_any = any;
+    p->real_form = form;
     p->N[0] = n0;
     p->N[1] = n1;
     p->N[2] = nh;
@@ -1863,7 +1907,7 @@ int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long lon
         if (e == hipSuccess) e = hipEventCreate(&ev);
     if (e != hipSuccess) {
         dfft_plan_destroy(p);
-        return fail(DFFT_EHIP, std::string("dfft_plan_create_r2c: ") + hipGetErrorString(e));
+        return fail(DFFT_EHIP, fn + ": " + hipGetErrorString(e));
     }
     fill_exchange(p, p->xd, direction);  // at width nh
     p->xd.sendbuf = direction == DFFT_FORWARD ? p->buf2 : p->cbuf;
@@ -1893,8 +1937,28 @@ int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long lon
         if (cpe && atoll(cpe) > 0) p->chunk_planes = atoll(cpe);
         if (p->chunk_planes >= p->xs) p->chunk_planes = 0;
     }
-    // warm the twiddle caches so execute never allocates
-    for (long long n : {n0, n1, n2 / 2, n2}) {
+    if (form != 1) {
+        // the two-for-one rows: Bluestein tables (n2 of kind 3) and the scratch of one cache chunk of rows
+        p->rfused = bluestein_fused_env();
+        if (length_kind(n2) == 3) {
+            const int rc = bluestein_tables(n2, dtype, direction, &p->rtab);
+            if (rc) {
+                dfft_plan_destroy(p);
+                return rc;
+            }
+        }
+        const long long rows = (p->chunk_planes > 0 ? p->chunk_planes : p->xs) * n1;
+        p->rscratch_bytes = real_pair_scratch_bytes(n2, dtype, rows, p->rtab.get(), p->rfused);
+        if (p->rscratch_bytes && (e = hipMalloc(&p->rscratch, p->rscratch_bytes)) != hipSuccess) {
+            dfft_plan_destroy(p);
+            return fail(DFFT_EHIP, fn + ": scratch of the real rows: " + hipGetErrorString(e));
+        }
+    }
+    // warm the twiddle caches so execute never allocates (form 3: the Bluestein tables above; four-step factors on first use)
+    std::vector<long long> warm{n0, n1};
+    if (form == 1) warm.insert(warm.end(), {n2 / 2, n2});
+    if (form == 2) warm.push_back(n2);
+    for (long long n : warm) {
         const void* tw;
         const int   rc = get_twiddles((int)n, dtype, &tw);
         if (rc) {
@@ -1904,6 +1968,20 @@ int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long lon
     }
     *plan = p;
     return DFFT_OK;
+}
+
+extern "C" {
+
+int dfft_real_form(long long n) { return real_form(n); }
+
+int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
+                         dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    return create_r2c(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, false);
+}
+
+int dfft_plan_create_r2c_any(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
+                             dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    return create_r2c(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, true);
 }
 
 int dfft_plan_set_scale(dfft_plan_t plan, double s) {
@@ -2188,6 +2266,17 @@ int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
         snprintf(buf, (size_t)len, "pipeline=%s n2=%lld bins=%lld chunks=%lldx%lld intermediate_pitch=%lld", p->direction == DFFT_FORWARD ? "r2c" : "c2r",
                  p->n2r, p->N[2], p->chunk_planes > 0 ? (p->xs + p->chunk_planes - 1) / p->chunk_planes : 1ll, p->chunk_planes > 0 ? p->chunk_planes : p->xs,
                  p->cl.pitch);
+        if (p->real_any) {  // "real_form=3 complex_form=four-step/125x125" or "... complex_form=bluestein/M194/fused"
+            const size_t used = strlen(buf);
+            int          a = 0, b = 0;
+            char         cf[96] = "";
+            if (p->real_form == 3 && p->rtab)
+                snprintf(cf, sizeof(cf), " complex_form=bluestein/M%lld/%s", p->rtab->M,
+                         (p->n2r == 1 || (p->rfused && p->n2r <= kBluesteinFusedMaxLength)) ? "fused" : "multi-pass");
+            else if (p->real_form == 3 && long_split(p->n2r, &a, &b))
+                snprintf(cf, sizeof(cf), " complex_form=four-step/%dx%d", a, b);
+            if (used + 1 < (size_t)len) snprintf(buf + used, (size_t)len - used, " real_form=%d%s", p->real_form, cf);
+        }
         return DFFT_OK;
     }
     const bool         one = p->zy_on && !(p->flags & DFFT_PLAN_UNFUSED);
@@ -2310,6 +2399,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     if (plan->wbuf) slab_free(plan->wbuf);
     if (plan->lbuf) hipFree(plan->lbuf);
     if (plan->bs.scratch) hipFree(plan->bs.scratch);
+    if (plan->rscratch) hipFree(plan->rscratch);
     if (plan->cbuf) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
@@ -2536,6 +2626,96 @@ int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batc
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_any: no HIP device visible (no CPU fallback)");
     if (batch == 0) return DFFT_OK;
     return bluestein_pass(in, out, n, s, batch, dtype, direction, 1.0, (hipStream_t)stream);
+}
+
+int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream) {
+    if (!in || !out || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
+        return fail(DFFT_EINVAL, "dfft_rfft1d: bad arguments");
+    const int form = real_form(n);
+    if (form == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft1d: length " + std::to_string(n) + " has no real form (at most 2^23, or a four-step length)");
+    const bool      fwd = direction == DFFT_FORWARD;
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const long long nh = n / 2 + 1;
+    {  // out of place: the byte ranges of in and out must not overlap
+        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+        const uintptr_t ib = (uintptr_t)batch * (fwd ? n * rs : nh * cs), ob = (uintptr_t)batch * (fwd ? nh * cs : n * rs);
+        if (i0 == o0 || (i0 < o0 + ob && o0 < i0 + ib)) return fail(DFFT_EINVAL, "dfft_rfft1d: in and out overlap (the transform is out of place)");
+    }
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d: no HIP device visible (no CPU fallback)");
+    if (batch == 0) return DFFT_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    // rows as one plane: real pitch n, complex pitch nh; at most 2^30 rows per launch (an even count: pairs never straddle two calls)
+    const long long  max_rows = 1ll << 30;
+    if (form == 1) {
+        // the half-length kernels; their two-launch C2R form (n/2 without a tuned plan) merges in place on its input, so the bins go
+        // through the per-(device, stream) scratch first, in chunks of at most 256 MiB
+        const bool       copy = !fwd && !fft_length_tuned((int)(n / 2));
+        const long long  chunk = copy ? std::max(1ll, std::min(max_rows, (long long)((256ll << 20) / (nh * (long long)cs)))) : max_rows;
+        LongScratchLease lease = nullptr;
+        void*            scr = nullptr;
+        if (copy) {
+            scr = long_scratch((size_t)std::min(chunk, batch) * nh * cs, st, &lease);
+            if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
+        }
+        int rc = DFFT_OK;
+        for (long long b0 = 0; b0 < batch && rc == DFFT_OK; b0 += chunk) {
+            const long long rows = std::min(chunk, batch - b0);
+            RealLaunch      L;
+            std::memset(&L, 0, sizeof(L));
+            L.dtype = dtype;
+            L.n2 = (int)n;
+            L.dir = direction;
+            L.in = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
+            L.out = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
+            L.rows = rows;
+            L.rows_per_plane = rows;
+            L.rpitch = n;
+            L.rplane = rows * n;
+            L.cpitch = nh;
+            L.cplane = rows * nh;
+            L.scale = 1.0;
+            if (copy) {
+                const hipError_t e = hipMemcpyAsync(scr, L.in, (size_t)rows * nh * cs, hipMemcpyDeviceToDevice, st);
+                if (e != hipSuccess) rc = fail(DFFT_EHIP, std::string("dfft_rfft1d: ") + hipGetErrorString(e));
+                L.in = scr;
+            }
+            if (rc == DFFT_OK) rc = check_launch(launch_real_rows(L, st), fwd ? "dfft_rfft1d (R2C rows)" : "dfft_rfft1d (C2R rows)");
+        }
+        long_scratch_release(lease);
+        return rc;
+    }
+    // two-for-one pairs: the cached Bluestein tables of (n, dtype, direction) for Bluestein lengths, scratch from the same lease
+    BluesteinTablesPtr t;
+    if (length_kind(n) == 3)
+        if (int rc = bluestein_tables(n, dtype, direction, &t)) return rc;
+    const bool       fused = bluestein_fused_env();
+    const size_t     need = real_pair_scratch_bytes(n, dtype, std::min(batch, max_rows), t.get(), fused);
+    LongScratchLease lease = nullptr;
+    void*            scr = nullptr;
+    if (need) {
+        scr = long_scratch(need, st, &lease);
+        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
+    }
+    int rc = DFFT_OK;
+    for (long long b0 = 0; b0 < batch && rc == DFFT_OK; b0 += max_rows) {
+        const long long rows = std::min(max_rows, batch - b0);
+        RealPairLaunch  R;
+        std::memset(&R, 0, sizeof(R));
+        R.dtype = dtype;
+        R.n = n;
+        R.dir = direction;
+        R.in = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
+        R.out = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
+        R.rows = rows;
+        R.rows_per_plane = rows;
+        R.rpitch = n;
+        R.rplane = rows * n;
+        R.cpitch = nh;
+        R.cplane = rows * nh;
+        rc = real_pair_rows(R, t.get(), fused, scr, need, st);
+    }
+    long_scratch_release(lease);
+    return rc;
 }
 
 int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,

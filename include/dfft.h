@@ -91,6 +91,11 @@ int dfft_length_kind(long long n);
 /* The padded length M >= 2n - 1 a Bluestein transform of length n runs on (1 for n = 1; the smallest tuned single-pass length for
  * n <= 2048, the smallest four-step length above), or 0 if n is not of kind 3.  Pure host arithmetic. */
 long long dfft_bluestein_length(long long n);
+/* How a real transform of length n is computed (dfft_rfft1d, dfft_plan_create_r2c_any): 1 half-length (n even, n/2 a single-pass length:
+ * the row kernels of dfft_plan_create_r2c); 2 paired single-pass (the odd 7-smooth n <= 4096, and n = 2: two real rows a, b packed into
+ * one complex row a + i b share one n-point transform); 3 paired multi-pass (the n-point four-step or Bluestein transform, n = 1
+ * included); 0 none.  Pure host arithmetic. */
+int dfft_real_form(long long n);
 
 /* ---- slab bookkeeping: pure host arithmetic, callable without a GPU ------------------------------------------------ */
 /* getProperDeviceNum (fft_mpi_3d_api.cpp:232-272): shrink the device count when N0 % P != 0 so every device but the
@@ -175,6 +180,15 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
  * buffer to place) and dfft_kernel_times returns DFFT_EUNSUPPORTED. */
 int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                          void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* dfft_plan_create_r2c with the real axis N2 of any dfft_real_form != 0 (N2 >= 2): same arguments, layouts (dfft_r2c_counts,
+ * Nh = N2/2 + 1), flags (DFFT_PLAN_DEFAULT, DFFT_PLAN_INPUT_FROM_IN) and limits on N0 and N1 (single-pass).  For N2 of form 1 the plan is
+ * exactly dfft_plan_create_r2c's.  Forms 2 and 3 run the Z stage on pairs of rows (rows pair up across plane boundaries), each pair
+ * through one N2-point complex transform; the plan owns the Bluestein tables and the scratch of one cache chunk of rows, so
+ * dfft_execute allocates nothing.  Each row's rounding error is bounded relative to its pair's combined magnitude.
+ * dfft_plan_describe appends "real_form=<f>" and, for form 3, "complex_form=four-step/<a>x<b>" or "complex_form=bluestein/M<M>/<fused|
+ * multi-pass>".  Arguments are checked before the device is queried. */
+int dfft_plan_create_r2c_any(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
+                             void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
 /* Elements the caller's buffers of an r2c plan must hold on device global_idx: *real_count reals on the real side (R2C input / C2R
  * output), *complex_count complex elements on the complex side (R2C output / C2R input) -- the result [y_local][Nh][N0] and, for P > 1,
  * the packed send layout of the forward exchange, which the R2C plan writes into `out` before its result.  Pure host arithmetic. */
@@ -247,6 +261,14 @@ int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long
  * are built on the first call for (device, n, dtype, direction) and cached; dfft_trim frees them and the scratch.
  * DFFT_BLUESTEIN_FUSED=0 (read per call) runs the multi-pass form for n <= 2048 as well (A/B and measurement switch). */
 int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream);
+
+/* Real transforms of `batch` contiguous rows, for ANY n with dfft_real_form(n) != 0.  Forward: reals [batch][n] -> bins [batch][n/2+1]
+ * (= numpy.fft.rfft).  Backward: bins -> reals, = n * numpy.fft.irfft(row, n) for ANY input (the imaginary parts of bin 0 and, n even,
+ * bin n/2 are ignored).  Unnormalised, out of place (the byte ranges of in and out must not overlap: DFFT_EINVAL), `in` is never
+ * written.  Form 1 runs the half-length kernels of the r2c plans; forms 2 and 3 pair rows 2p and 2p + 1 in one n-point complex
+ * transform (an odd last row is paired with a zero row, or its partner's output dropped), so each row's rounding error is bounded
+ * relative to its pair's combined magnitude.  Scratch and Bluestein tables come from the caches dfft_trim frees. */
+int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
 
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
