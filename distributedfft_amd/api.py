@@ -430,48 +430,104 @@ def real_form(n: int) -> int:
     return int(L.load().dfft_real_form(int(n)))
 
 
-def rfft1d(x, out=None):
-    """numpy.fft.rfft along the last dimension of a contiguous float64 / float32 device tensor [..., n] -> complex128 / complex64
-    [..., n//2 + 1], for any n with real_form(n) != 0 (dfft_rfft1d).  Unnormalised, out of place."""
+def _axis_split(shape, dim):
+    """(batch, n, s) of a contiguous tensor seen as [batch][n][s] along dimension `dim` (-ndim <= dim < ndim, as in torch and numpy)."""
     import math
+    if not -len(shape) <= dim < len(shape):
+        raise IndexError(f"dim {dim} is out of range for a tensor of {len(shape)} dimensions")
+    d = dim % len(shape)
+    return math.prod(int(v) for v in shape[:d]), int(shape[d]), math.prod(int(v) for v in shape[d + 1:]), d
 
+
+def rfft1d(x, out=None, *, dim: int = -1):
+    """numpy.fft.rfft along dimension `dim` of a contiguous float64 / float32 device tensor -> complex128 / complex64 with n//2 + 1 bins
+    in that dimension, for any n with real_form(n) != 0: the last dimension through dfft_rfft1d, any other through dfft_rfft1d_strided
+    (the tensor seen as [batch][n][s]).  Unnormalised, out of place."""
     import torch
     assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32)
-    n = int(x.shape[-1])
+    batch, n, s, d = _axis_split(x.shape, dim)
     cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
-    shape = tuple(x.shape[:-1]) + (n // 2 + 1,)
+    shape = tuple(x.shape[:d]) + (n // 2 + 1,) + tuple(x.shape[d + 1:])
     if out is None:
         out = torch.empty(shape, dtype=cdt, device=x.device)
     assert tuple(out.shape) == shape and out.dtype == cdt and out.device == x.device and out.is_contiguous(), \
         f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
-    batch = math.prod(int(v) for v in x.shape[:-1])
+    code = F64 if x.dtype == torch.float64 else F32
     with torch.cuda.device(x.device):
-        L.check(L.load().dfft_rfft1d(x.data_ptr(), out.data_ptr(), n, batch, F64 if x.dtype == torch.float64 else F32, FORWARD, None),
-                "dfft_rfft1d")
+        if s == 1:
+            L.check(L.load().dfft_rfft1d(x.data_ptr(), out.data_ptr(), n, batch, code, FORWARD, None), "dfft_rfft1d")
+        else:
+            L.check(L.load().dfft_rfft1d_strided(x.data_ptr(), out.data_ptr(), n, s, batch, code, FORWARD, None), "dfft_rfft1d_strided")
         torch.cuda.synchronize()
     return out
 
 
-def irfft1d(X, n: int, out=None):
-    """n * numpy.fft.irfft(X, n) along the last dimension of a contiguous complex128 / complex64 device tensor [..., n//2 + 1] -> float64
-    / float32 [..., n] (dfft_rfft1d, backward): unnormalised; the imaginary parts of bin 0 and, n even, bin n/2 are ignored.  X is left
-    untouched."""
-    import math
-
+def irfft1d(X, n: int, out=None, *, dim: int = -1):
+    """n * numpy.fft.irfft(X, n, axis=dim) of a contiguous complex128 / complex64 device tensor with n//2 + 1 bins in dimension `dim`
+    -> float64 / float32 with n reals there (dfft_rfft1d / dfft_rfft1d_strided, backward): unnormalised; the imaginary parts of bin 0
+    and, n even, bin n/2 are ignored.  X is left untouched."""
     import torch
     assert X.is_cuda and X.is_contiguous() and X.dim() >= 1 and X.dtype in (torch.complex128, torch.complex64)
     n = int(n)
-    assert int(X.shape[-1]) == n // 2 + 1, f"irfft1d: the last dimension must hold n//2 + 1 = {n // 2 + 1} bins, got {X.shape[-1]}"
+    batch, nh, s, d = _axis_split(X.shape, dim)
+    assert nh == n // 2 + 1, f"irfft1d: dimension {d} must hold n//2 + 1 = {n // 2 + 1} bins, got {nh}"
     rdt = torch.float64 if X.dtype == torch.complex128 else torch.float32
-    shape = tuple(X.shape[:-1]) + (n,)
+    shape = tuple(X.shape[:d]) + (n,) + tuple(X.shape[d + 1:])
     if out is None:
         out = torch.empty(shape, dtype=rdt, device=X.device)
     assert tuple(out.shape) == shape and out.dtype == rdt and out.device == X.device and out.is_contiguous(), \
         f"out must be a contiguous {rdt} tensor of shape {shape} on {X.device}"
-    batch = math.prod(int(v) for v in X.shape[:-1])
+    code = F64 if rdt == torch.float64 else F32
     with torch.cuda.device(X.device):
-        L.check(L.load().dfft_rfft1d(X.data_ptr(), out.data_ptr(), n, batch, F64 if rdt == torch.float64 else F32, BACKWARD, None),
-                "dfft_rfft1d")
+        if s == 1:
+            L.check(L.load().dfft_rfft1d(X.data_ptr(), out.data_ptr(), n, batch, code, BACKWARD, None), "dfft_rfft1d")
+        else:
+            L.check(L.load().dfft_rfft1d_strided(X.data_ptr(), out.data_ptr(), n, s, batch, code, BACKWARD, None), "dfft_rfft1d_strided")
+        torch.cuda.synchronize()
+    return out
+
+
+def rfft2d_batch(x, out=None):
+    """numpy.fft.rfft2 of every (n1, n2) plane of a contiguous float64 / float32 device tensor [..., n1, n2] -> complex128 / complex64
+    [..., n1, n2//2 + 1] (dfft_rfft2d_batch): n2 of any real form, n1 of any length kind.  Unnormalised, out of place."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32)
+    n1, n2 = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    shape = tuple(x.shape[:-1]) + (n2 // 2 + 1,)
+    if out is None:
+        out = torch.empty(shape, dtype=cdt, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == cdt and out.device == x.device and out.is_contiguous(), \
+        f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rfft2d_batch(x.data_ptr(), out.data_ptr(), n1, n2, batch, F64 if x.dtype == torch.float64 else F32, FORWARD,
+                                           None), "dfft_rfft2d_batch")
+        torch.cuda.synchronize()
+    return out
+
+
+def irfft2d_batch(X, n2: int, out=None):
+    """n1 * n2 * numpy.fft.irfft2(X, s=(n1, n2)) of every plane of a contiguous complex128 / complex64 device tensor [..., n1, n2//2 + 1]
+    -> float64 / float32 [..., n1, n2] (dfft_rfft2d_batch, backward), for any input.  Unnormalised; X is left untouched."""
+    import math
+
+    import torch
+    assert X.is_cuda and X.is_contiguous() and X.dim() >= 2 and X.dtype in (torch.complex128, torch.complex64)
+    n1, n2 = int(X.shape[-2]), int(n2)
+    assert int(X.shape[-1]) == n2 // 2 + 1, f"irfft2d_batch: the last dimension must hold n2//2 + 1 = {n2 // 2 + 1} bins, got {X.shape[-1]}"
+    rdt = torch.float64 if X.dtype == torch.complex128 else torch.float32
+    shape = tuple(X.shape[:-1]) + (n2,)
+    if out is None:
+        out = torch.empty(shape, dtype=rdt, device=X.device)
+    assert tuple(out.shape) == shape and out.dtype == rdt and out.device == X.device and out.is_contiguous(), \
+        f"out must be a contiguous {rdt} tensor of shape {shape} on {X.device}"
+    batch = math.prod(int(v) for v in X.shape[:-2])
+    with torch.cuda.device(X.device):
+        L.check(L.load().dfft_rfft2d_batch(X.data_ptr(), out.data_ptr(), n1, n2, batch, F64 if rdt == torch.float64 else F32, BACKWARD,
+                                           None), "dfft_rfft2d_batch")
         torch.cuda.synchronize()
     return out
 

@@ -31,6 +31,7 @@
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
+#include "dfft_real_cols.h"
 #include "dfft_real_pair.h"
 #include "dfft_zy.h"
 
@@ -2417,6 +2418,16 @@ int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype
 }
 
 // ---- batched 2D transform: the plan's t0 stage as an entry point of its own ------------------------------------
+// Planes per group of `batch` planes of plane_b bytes that fit the 256 MiB Infinity Cache (dfft_plan_create's rule for single-GPU plans:
+// one plane less per group from 8 MiB planes on, groups of equal size): the column pass then reads what the row pass wrote from the cache.
+static long long cache_plane_group(long long batch, long long plane_b) {
+    if (batch * plane_b <= (256ll << 20)) return batch;
+    long long fit = std::max(1ll, (256ll << 20) / plane_b);
+    if (plane_b >= (8ll << 20) && fit > 1) --fit;
+    const long long nchunks = std::max(1ll, (batch + fit - 1) / fit);
+    return (batch + nchunks - 1) / nchunks;
+}
+
 // State of the one-launch stage for one (device, stream, plane shape, structure): the kernel's control block, its pinned error word and
 // the host's running ticket / execute counters (dfft_zy.hip) -- what a plan keeps in dfft_plan_s, cached here because the call is
 // plan-less.  Freed by dfft_trim().
@@ -2551,13 +2562,7 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
         }
     }
     // ---- two launches per Infinity-Cache chunk (dfft_plan_create's rule for single-GPU plans)
-    long long cp = batch;
-    if (batch * plane_b > (256ll << 20)) {
-        long long fit = std::max(1ll, (256ll << 20) / plane_b);
-        if (plane_b >= (8ll << 20) && fit > 1) --fit;
-        const long long nchunks = std::max(1ll, (batch + fit - 1) / fit);
-        cp = (batch + nchunks - 1) / nchunks;
-    }
+    const long long cp = cache_plane_group(batch, plane_b);
     const void* twy = nullptr;
     DFFT_TRY(get_twiddles((int)n1, dtype, &twy));
     const bool chunked = cp < batch;
@@ -2628,6 +2633,142 @@ int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batc
     return bluestein_pass(in, out, n, s, batch, dtype, direction, 1.0, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// ---- shared by dfft_rfft1d, dfft_rfft1d_strided and dfft_rfft2d_batch ------------------------------------------------------------------
+// A caller that needs the per-(device, stream) scratch for more than one step at a time (dfft_rfft2d_batch's inverse: the bins of a plane
+// group and the scratch of the transforms on them) takes ONE lease for all of it -- the lease is not re-entrant -- so these helpers size
+// their scratch first (*_prepare) and then run on whatever scratch they are given (*_run).
+
+// Real rows of dfft_rfft1d: `rows` rows of n reals <-> n/2 + 1 bins.  in_is_scratch: the C2R input is the caller's own scratch, which
+// the two-launch C2R form of real form 1 may merge in place on (no copy into scratch first).
+struct RealRowsPass {
+    long long          n, chunk;  // rows per launch
+    int                dtype, dir, form;
+    bool               copy;      // form 1 C2R with n/2 untuned: the bins go through scratch first
+    BluesteinTablesPtr t;         // forms 2 / 3 with a Bluestein n
+    bool               bs_fused;
+    size_t             need;      // scratch bytes
+};
+static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, RealRowsPass* R) {
+    const size_t    cs = elem_bytes(dtype);
+    const long long nh = n / 2 + 1;
+    // rows as one plane: real pitch n, complex pitch nh; at most 2^30 rows per launch (an even count: pairs never straddle two calls)
+    const long long max_rows = 1ll << 30;
+    R->n = n;
+    R->dtype = dtype;
+    R->dir = dir;
+    R->form = real_form(n);
+    R->t.reset();
+    R->bs_fused = true;
+    R->copy = false;
+    R->chunk = max_rows;
+    R->need = 0;
+    if (R->form == 1) {
+        // the half-length kernels; their two-launch C2R form (n/2 without a tuned plan) merges in place on its input, so the bins go
+        // through the per-(device, stream) scratch first, in chunks of at most 256 MiB
+        R->copy = dir != DFFT_FORWARD && !fft_length_tuned((int)(n / 2)) && !in_is_scratch;
+        if (R->copy) {
+            R->chunk = std::max(1ll, std::min(max_rows, (long long)((256ll << 20) / (nh * (long long)cs))));
+            R->need = (size_t)std::min(R->chunk, rows) * nh * cs;
+        }
+        return DFFT_OK;
+    }
+    // two-for-one pairs: the cached Bluestein tables of (n, dtype, direction) for Bluestein lengths
+    if (length_kind(n) == 3)
+        if (int rc = bluestein_tables(n, dtype, dir, &R->t)) return rc;
+    R->bs_fused = bluestein_fused_env();
+    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), R->t.get(), R->bs_fused);
+    return DFFT_OK;
+}
+static int real_rows_run(const RealRowsPass& R, const void* in, void* out, long long rows, void* scr, hipStream_t st) {
+    const bool      fwd = R.dir == DFFT_FORWARD;
+    const long long n = R.n, nh = n / 2 + 1;
+    const size_t    cs = elem_bytes(R.dtype), rs = cs / 2;
+    int             rc = DFFT_OK;
+    for (long long b0 = 0; b0 < rows && rc == DFFT_OK; b0 += R.chunk) {
+        const long long m = std::min(R.chunk, rows - b0);
+        const void*     ip = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
+        void*           op = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
+        if (R.form == 1) {
+            RealLaunch L;
+            std::memset(&L, 0, sizeof(L));
+            L.dtype = R.dtype;
+            L.n2 = (int)n;
+            L.dir = R.dir;
+            L.in = ip;
+            L.out = op;
+            L.rows = m;
+            L.rows_per_plane = m;
+            L.rpitch = n;
+            L.rplane = m * n;
+            L.cpitch = nh;
+            L.cplane = m * nh;
+            L.scale = 1.0;
+            if (R.copy) {
+                const hipError_t e = hipMemcpyAsync(scr, L.in, (size_t)m * nh * cs, hipMemcpyDeviceToDevice, st);
+                if (e != hipSuccess) rc = fail(DFFT_EHIP, std::string("dfft_rfft1d: ") + hipGetErrorString(e));
+                L.in = scr;
+            }
+            if (rc == DFFT_OK) rc = check_launch(launch_real_rows(L, st), fwd ? "dfft_rfft1d (R2C rows)" : "dfft_rfft1d (C2R rows)");
+        } else {
+            RealPairLaunch P;
+            std::memset(&P, 0, sizeof(P));
+            P.dtype = R.dtype;
+            P.n = n;
+            P.dir = R.dir;
+            P.in = ip;
+            P.out = op;
+            P.rows = m;
+            P.rows_per_plane = m;
+            P.rpitch = n;
+            P.rplane = m * n;
+            P.cpitch = nh;
+            P.cplane = m * nh;
+            rc = real_pair_rows(P, R.t.get(), R.bs_fused, scr, R.need, st);
+        }
+    }
+    return rc;
+}
+
+// dfft_fft1d_any's transforms of [batch][n][s] on caller-provided scratch (the four-step and Bluestein forms need some; dfft_fft1d_any
+// itself leases it inside dfft_fft1d_rows / dfft_fft1d_cols / bluestein_pass)
+struct AnyPass {
+    long long          n, s;
+    int                dtype, dir, kind;
+    BluesteinTablesPtr t;
+    bool               bs_fused;
+    size_t             need;
+};
+static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, AnyPass* A) {
+    A->n = n;
+    A->s = s;
+    A->dtype = dtype;
+    A->dir = dir;
+    A->kind = length_kind(n);
+    A->t.reset();
+    A->bs_fused = bluestein_fused_env();
+    A->need = A->kind == 2 ? (size_t)batch * n * s * elem_bytes(dtype) : 0;
+    if (A->kind == 3) {
+        if (int rc = bluestein_tables(n, dtype, dir, &A->t)) return rc;
+        A->need = bluestein_scratch_bytes(*A->t, s, batch, A->bs_fused);
+    }
+    return DFFT_OK;
+}
+static int any_run(const AnyPass& A, const void* in, void* out, long long batch, void* scr, hipStream_t st) {
+    if (A.kind == 3) return bluestein_fft(*A.t, in, out, A.s, batch, 1.0, A.bs_fused, scr, A.need, st);
+    if (A.kind == 2) return long_fft(in, out, A.n, A.s, batch, A.dtype, A.dir, 1.0, scr, st);
+    return A.s == 1 ? dfft_fft1d_rows((void*)in, out, A.n, batch, A.dtype, A.dir, st) : dfft_fft1d_cols((void*)in, out, A.n, A.s, batch, A.dtype, A.dir, st);
+}
+
+// the byte ranges [a, a + ab) and [b, b + bb) overlap (or start at the same address)
+static bool ranges_overlap(const void* a, uintptr_t ab, const void* b, uintptr_t bb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 == b0 || (a0 < b0 + bb && b0 < a0 + ab);
+}
+
+extern "C" {
+
 int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream) {
     if (!in || !out || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
         return fail(DFFT_EINVAL, "dfft_rfft1d: bad arguments");
@@ -2636,83 +2777,115 @@ int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, in
     const bool      fwd = direction == DFFT_FORWARD;
     const size_t    cs = elem_bytes(dtype), rs = cs / 2;
     const long long nh = n / 2 + 1;
-    {  // out of place: the byte ranges of in and out must not overlap
-        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-        const uintptr_t ib = (uintptr_t)batch * (fwd ? n * rs : nh * cs), ob = (uintptr_t)batch * (fwd ? nh * cs : n * rs);
-        if (i0 == o0 || (i0 < o0 + ob && o0 < i0 + ib)) return fail(DFFT_EINVAL, "dfft_rfft1d: in and out overlap (the transform is out of place)");
-    }
+    // out of place: the byte ranges of in and out must not overlap
+    if (ranges_overlap(in, (uintptr_t)batch * (fwd ? n * rs : nh * cs), out, (uintptr_t)batch * (fwd ? nh * cs : n * rs)))
+        return fail(DFFT_EINVAL, "dfft_rfft1d: in and out overlap (the transform is out of place)");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d: no HIP device visible (no CPU fallback)");
     if (batch == 0) return DFFT_OK;
     const hipStream_t st = (hipStream_t)stream;
-    // rows as one plane: real pitch n, complex pitch nh; at most 2^30 rows per launch (an even count: pairs never straddle two calls)
-    const long long  max_rows = 1ll << 30;
-    if (form == 1) {
-        // the half-length kernels; their two-launch C2R form (n/2 without a tuned plan) merges in place on its input, so the bins go
-        // through the per-(device, stream) scratch first, in chunks of at most 256 MiB
-        const bool       copy = !fwd && !fft_length_tuned((int)(n / 2));
-        const long long  chunk = copy ? std::max(1ll, std::min(max_rows, (long long)((256ll << 20) / (nh * (long long)cs)))) : max_rows;
-        LongScratchLease lease = nullptr;
-        void*            scr = nullptr;
-        if (copy) {
-            scr = long_scratch((size_t)std::min(chunk, batch) * nh * cs, st, &lease);
-            if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
-        }
-        int rc = DFFT_OK;
-        for (long long b0 = 0; b0 < batch && rc == DFFT_OK; b0 += chunk) {
-            const long long rows = std::min(chunk, batch - b0);
-            RealLaunch      L;
-            std::memset(&L, 0, sizeof(L));
-            L.dtype = dtype;
-            L.n2 = (int)n;
-            L.dir = direction;
-            L.in = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
-            L.out = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
-            L.rows = rows;
-            L.rows_per_plane = rows;
-            L.rpitch = n;
-            L.rplane = rows * n;
-            L.cpitch = nh;
-            L.cplane = rows * nh;
-            L.scale = 1.0;
-            if (copy) {
-                const hipError_t e = hipMemcpyAsync(scr, L.in, (size_t)rows * nh * cs, hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) rc = fail(DFFT_EHIP, std::string("dfft_rfft1d: ") + hipGetErrorString(e));
-                L.in = scr;
-            }
-            if (rc == DFFT_OK) rc = check_launch(launch_real_rows(L, st), fwd ? "dfft_rfft1d (R2C rows)" : "dfft_rfft1d (C2R rows)");
-        }
-        long_scratch_release(lease);
-        return rc;
+    RealRowsPass      R;
+    if (int rc = real_rows_prepare(n, batch, dtype, direction, false, &R)) return rc;
+    LongScratchLease lease = nullptr;
+    void*            scr = nullptr;
+    if (R.need) {
+        scr = long_scratch(R.need, st, &lease);
+        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
     }
-    // two-for-one pairs: the cached Bluestein tables of (n, dtype, direction) for Bluestein lengths, scratch from the same lease
+    const int rc = real_rows_run(R, in, out, batch, scr, st);
+    long_scratch_release(lease);
+    return rc;
+}
+
+// Real transforms along the middle axis of [batch][n][s] (dfft_real_cols.hip); s = 1 is dfft_rfft1d.
+int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream) {
+    if (!in || !out || batch < 0 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
+        return fail(DFFT_EINVAL, "dfft_rfft1d_strided: bad arguments");
+    if (length_kind(n) == 0)
+        return fail(DFFT_EUNSUPPORTED, "dfft_rfft1d_strided: length " + std::to_string(n) + " has no real form (at most 2^23, or a four-step length)");
+    const bool      fwd = direction == DFFT_FORWARD;
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const uintptr_t rb = (uintptr_t)batch * n * s * rs, cb = (uintptr_t)batch * (n / 2 + 1) * s * cs;
+    if (ranges_overlap(in, fwd ? rb : cb, out, fwd ? cb : rb))
+        return fail(DFFT_EINVAL, "dfft_rfft1d_strided: in and out overlap (the transform is out of place)");
+    if (s == 1) return dfft_rfft1d(in, out, n, batch, dtype, direction, stream);
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d_strided: no HIP device visible (no CPU fallback)");
+    if (batch == 0) return DFFT_OK;
+    const hipStream_t  st = (hipStream_t)stream;
     BluesteinTablesPtr t;
     if (length_kind(n) == 3)
         if (int rc = bluestein_tables(n, dtype, direction, &t)) return rc;
-    const bool       fused = bluestein_fused_env();
-    const size_t     need = real_pair_scratch_bytes(n, dtype, std::min(batch, max_rows), t.get(), fused);
+    const bool       bs_fused = bluestein_fused_env();
+    const size_t     need = real_cols_scratch_bytes(n, s, batch, dtype, t.get(), bs_fused);
     LongScratchLease lease = nullptr;
     void*            scr = nullptr;
     if (need) {
         scr = long_scratch(need, st, &lease);
-        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
+        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d_strided: cannot allocate the scratch buffer");
     }
-    int rc = DFFT_OK;
-    for (long long b0 = 0; b0 < batch && rc == DFFT_OK; b0 += max_rows) {
-        const long long rows = std::min(max_rows, batch - b0);
-        RealPairLaunch  R;
-        std::memset(&R, 0, sizeof(R));
-        R.dtype = dtype;
-        R.n = n;
-        R.dir = direction;
-        R.in = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
-        R.out = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
-        R.rows = rows;
-        R.rows_per_plane = rows;
-        R.rpitch = n;
-        R.rplane = rows * n;
-        R.cpitch = nh;
-        R.cplane = rows * nh;
-        rc = real_pair_rows(R, t.get(), fused, scr, need, st);
+    RealColsLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.n = n;
+    L.s = s;
+    L.batch = batch;
+    L.dir = direction;
+    L.in = in;
+    L.out = out;
+    const int rc = real_cols(L, t.get(), bs_fused, scr, need, st);
+    long_scratch_release(lease);
+    return rc;
+}
+
+// `batch` planes of [n1][n2] reals <-> [n1][n2/2 + 1] bins, in groups of planes sized for the 256 MiB Infinity Cache (dfft_fft2d_batch's
+// rule, on the complex side): forward R2C rows into `out`, then the n1-point columns in place on `out` (dfft_fft1d_any); backward the
+// inverse columns from `in` into a scratch group, then C2R rows from there into `out`.
+int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream) {
+    if (!in || !out || n1 < 1 || n2 < 1 || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
+        return fail(DFFT_EINVAL, "dfft_rfft2d_batch: bad arguments");
+    if (real_form(n2) == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft2d_batch: n2 = " + std::to_string(n2) + " has no real form");
+    if (length_kind(n1) == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft2d_batch: n1 = " + std::to_string(n1) + " is outside every form");
+    const bool      fwd = direction == DFFT_FORWARD;
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const long long nh = n2 / 2 + 1;
+    const uintptr_t rplane_b = (uintptr_t)n1 * n2 * rs, cplane_b = (uintptr_t)n1 * nh * cs;
+    if (ranges_overlap(in, (uintptr_t)batch * (fwd ? rplane_b : cplane_b), out, (uintptr_t)batch * (fwd ? cplane_b : rplane_b)))
+        return fail(DFFT_EINVAL, "dfft_rfft2d_batch: in and out overlap (the transform is out of place)");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft2d_batch: no HIP device visible (no CPU fallback)");
+    if (batch == 0) return DFFT_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    const long long   cp = cache_plane_group(batch, (long long)cplane_b);  // planes per group
+    RealRowsPass R;
+    if (int rc = real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, &R)) return rc;
+    if (fwd) {
+        for (long long p0 = 0; p0 < batch; p0 += cp) {
+            const long long  np = std::min(cp, batch - p0);
+            void*            op = (char*)out + p0 * cplane_b;
+            LongScratchLease lease = nullptr;
+            void*            scr = nullptr;
+            if (R.need) {
+                scr = long_scratch(R.need, st, &lease);
+                if (!scr) return fail(DFFT_EHIP, "dfft_rfft2d_batch: cannot allocate the scratch buffer");
+            }
+            const int rc = real_rows_run(R, (const char*)in + p0 * rplane_b, op, np * n1, scr, st);
+            long_scratch_release(lease);
+            if (rc) return rc;
+            if (int rc2 = dfft_fft1d_any(op, op, n1, nh, np, dtype, direction, stream)) return rc2;
+        }
+        return DFFT_OK;
+    }
+    AnyPass A;
+    if (int rc = any_prepare(n1, nh, cp, dtype, direction, &A)) return rc;
+    const size_t     gb = (size_t)cp * cplane_b;  // the bins of one plane group
+    const size_t     inner = std::max(R.need, A.need);
+    LongScratchLease lease = nullptr;
+    void*            scr = long_scratch(gb + inner, st, &lease);
+    if (!scr) return fail(DFFT_EHIP, "dfft_rfft2d_batch: cannot allocate the scratch buffer");
+    void* iscr = inner ? (char*)scr + gb : nullptr;
+    int   rc = DFFT_OK;
+    for (long long p0 = 0; p0 < batch && rc == DFFT_OK; p0 += cp) {
+        const long long np = std::min(cp, batch - p0);
+        rc = any_run(A, (const char*)in + p0 * cplane_b, scr, np, iscr, st);
+        if (rc == DFFT_OK) rc = real_rows_run(R, scr, (char*)out + p0 * rplane_b, np * n1, iscr, st);
     }
     long_scratch_release(lease);
     return rc;

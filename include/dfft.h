@@ -270,6 +270,24 @@ int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batc
  * relative to its pair's combined magnitude.  Scratch and Bluestein tables come from the caches dfft_trim frees. */
 int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
 
+/* Real transforms along the middle axis of [batch][n][s] (s = 1: dfft_rfft1d, bit-identical), for ANY n of dfft_length_kind 1, 2 or 3.
+ * Forward: reals [batch][n][s] -> bins [batch][n/2+1][s] (= numpy.fft.rfft(x, axis=1)).  Backward: bins -> reals, = n * numpy.fft.irfft(X, n,
+ * axis=1) for ANY input (the imaginary parts of bin 0 and, n even, bin n/2 are ignored).  Unnormalised, out of place (overlapping byte
+ * ranges of in and out: DFFT_EINVAL), `in` is never written; any s >= 1 and any element-aligned pointers.  Real columns 2c and 2c + 1 share
+ * one n-point complex transform down the column pair (an odd last column is paired with a zero column), so each column's rounding error
+ * is bounded relative to its pair's combined magnitude.  Tuned single-pass n (n * s < 2^31) run as one launch; every other n in batch
+ * chunks on the four-step / Bluestein / run-time-scheduled transforms with scratch from the caches dfft_trim frees.  Arguments are checked
+ * before the device is queried. */
+int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream);
+
+/* Batched 2-D real transforms of `batch` planes [n1][n2] (n2 contiguous), for n2 of any dfft_real_form != 0 and n1 of any
+ * dfft_length_kind != 0.  Forward: reals [batch][n1][n2] -> bins [batch][n1][n2/2+1] (= numpy.fft.rfft2).  Backward: n1*n2 *
+ * numpy.fft.irfft2(X, s=(n1, n2)) for ANY input (inverse C2C along n1, then C2R along n2 with numpy's rule for the imaginary parts).
+ * Unnormalised, out of place (overlap: DFFT_EINVAL), `in` is never written.  Planes are processed in groups sized for the 256 MiB
+ * Infinity Cache: R2C rows (dfft_rfft1d) then the n1-point columns in place on `out` (dfft_fft1d_any); backward the inverse columns
+ * into a scratch group, then C2R rows into `out`.  Arguments are checked before the device is queried. */
+int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream);
+
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
  * `batch` planes of [n1][n2] complex elements (n2 contiguous), each transformed along both axes, in place (out == in) or out
