@@ -5,9 +5,14 @@
 
 One "step" = one forward transform (t0 YZ FFT -> t1 pack -> t2 RCCL all-to-all -> t3 X FFT) of the same device-resident
 synthetic input (uniform [-1,1) re/im, seeded); the total problem is fixed at 512^3 (strong scaling: BASELINE.json quotes
-512^3 at 1/2/4/8 GPUs).  Everything timed runs through the C-ABI of libdfft_mi355x (HIP kernels + RCCL); the oracle and
-the reference's heFFTe stock CPU backend are used only for the error check and the cpu_baseline leg on rank 0.
+512^3 at 1/2/4/8 GPUs).  Everything timed runs through the C-ABI of libdfft_mi355x (HIP kernels + RCCL).
 Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs: plan set-up (the placement tuning and, for N > 1, the choice between the
+overlapped and the serial pipeline included), warm-up, the timed steps, --dump-outputs, the line.  --full then goes on to
+measure and check the transform it timed: per-stage and per-kernel times, the round-trip and direct-DFT errors, the roofline
+block (with this command's rocprofv3 counter passes unless --no-pmc), for N > 1 the serial pipeline's full exchange, and at
+N = 1 the CPU baseline (unless --no-cpu-baseline: the reference's heFFTe stock backend, or the oracle where that is not built).
 """
 from __future__ import annotations
 
@@ -280,10 +285,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--size", type=parse_size, default=(512, 512, 512))
     ap.add_argument("--precision", choices=["fp64", "fp32"], default="fp64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: stage and "
+                         "kernel times, round-trip and direct-DFT errors, roofline, serial-pipeline diagnostic, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not measure roofline.traffic with a rocprofv3 counter pass of this very command (N = 1 only); "
-                         "the committed profiles/hbm_traffic.json figure is used if it belongs to the loaded library")
+                    help="with --full: do not measure roofline.traffic with a rocprofv3 counter pass of this very command (N = 1 "
+                         "only); the committed profiles/hbm_traffic.json figure is used if it belongs to the loaded library")
     ap.add_argument("--dry-run", action="store_true",
                     help="control-plane check only (CPU tests): rendezvous, id broadcast, slab bookkeeping; no GPU work")
     ap.add_argument("--unfused", action="store_true", help="reference stage structure (separate pack / transpose)")
@@ -562,110 +570,115 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, b, count, rank, P)  # before any untimed execute below touches b
 
-    # ---- per-stage / per-kernel breakdown from HIP events on the plan's stream (separate, untimed executes) ----
-    stage, kern = [], []
-    for _ in range(10):
-        barrier()
-        plan.execute(api.EXEC_ASYNC)
-        stage.append(plan.stage_times())
-        if not args.unfused:
-            try:
-                kern.append(plan.kernel_times())
-            except api.DfftError:
-                pass  # Z and Y launches interleaved per Infinity-Cache chunk: only t0 (Z+Y) and t3 (X) are separable
-    stage = np.median(np.array(stage), axis=0)
-    kern = np.median(np.array(kern), axis=0) if kern else None
-    if P > 1:
-        t = torch.tensor(np.concatenate([stage, kern if kern is not None else np.zeros(3)]), dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        stage = t[:4].numpy()
-        kern = t[4:].numpy() if kern is not None else None
-
-    # ---- P > 1: the same transform without overlap, to report the full (un-hidden) t2 and the per-link rate ----
-    serial_stage = None
-    same = None
-    if overlap:
-        try:
-            ss = []
-            for i in range(8):
-                barrier()
-                plan_s.execute(api.EXEC_ASYNC)
-                st = plan_s.stage_times()
-                if i >= 3:
-                    ss.append(st)
-            t = torch.tensor(np.median(np.array(ss), axis=0), dtype=torch.float64)
+    # A plain run ends here: its line carries the headline figure and what the set-up decided.  --full goes on to measure and
+    # check the transform it timed.
+    if args.full:
+        # ---- per-stage / per-kernel breakdown from HIP events on the plan's stream (separate, untimed executes) ----
+        stage, kern = [], []
+        for _ in range(10):
+            barrier()
+            plan.execute(api.EXEC_ASYNC)
+            stage.append(plan.stage_times())
+            if not args.unfused:
+                try:
+                    kern.append(plan.kernel_times())
+                except api.DfftError:
+                    pass  # Z and Y launches interleaved per Infinity-Cache chunk: only t0 (Z+Y) and t3 (X) are separable
+        stage = np.median(np.array(stage), axis=0)
+        kern = np.median(np.array(kern), axis=0) if kern else None
+        if P > 1:
+            t = torch.tensor(np.concatenate([stage, kern if kern is not None else np.zeros(3)]), dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            serial_stage = t.numpy()
-            same = bool(torch.equal(b2[:count], b[:count]))  # overlap must not change a single bit of the result
-            plan_s.destroy()
-            del b2
-        except Exception as e:  # never lose the headline number to the diagnostic
-            serial_stage, same = None, f"serial diagnostic failed: {e}"
+            stage = t[:4].numpy()
+            kern = t[4:].numpy() if kern is not None else None
 
-    # ---- error: the driver's round-trip metric (fftSpeed3d_c2c.cpp:84-91) on the device, plus an oracle spot check ----
-    fwd_out = b.clone()
-    c = torch.zeros(max_count, dtype=cdt, device=dev)
-    planb = api.Plan(n0, n1, n2, fwd_out, c, comm, rank, P, api.BACKWARD, api.PLAN_DEFAULT)
-    barrier()
-    planb.execute(api.EXEC_ASYNC)
-    planb.sync()
-    rt_err = float((a[:count] - c[:count] / N).abs().max().item())
-    if P > 1:
-        t = torch.tensor([rt_err], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        rt_err = float(t.item())
-    planb.destroy()
-    del c, fwd_out
+        # ---- P > 1: the same transform without overlap, to report the full (un-hidden) t2 and the per-link rate ----
+        serial_stage = None
+        same = None
+        if overlap:
+            try:
+                ss = []
+                for i in range(8):
+                    barrier()
+                    plan_s.execute(api.EXEC_ASYNC)
+                    st = plan_s.stage_times()
+                    if i >= 3:
+                        ss.append(st)
+                t = torch.tensor(np.median(np.array(ss), axis=0), dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                serial_stage = t.numpy()
+                same = bool(torch.equal(b2[:count], b[:count]))  # overlap must not change a single bit of the result
+                plan_s.destroy()
+                del b2
+            except Exception as e:  # never lose the headline number to the diagnostic
+                serial_stage, same = None, f"serial diagnostic failed: {e}"
 
-    # ---- independent full-size check: X[k] = sum_n x[n] e^{-2 pi i k.n/N} evaluated directly (fp64, summed over the
-    # ranks' slabs) for a few seeded k, against the element of the distributed result that should hold it ----
-    ks = [(0, 0, 0), (1, 2, 3), (n0 // 2, n1 - 1, n2 // 3), (n0 - 1, n1 // 2 + 1, n2 - 1), (n0 // 3, n1 // 5, 1)]
-    xl_blk, yl_blk = -(-n0 // P), -(-n1 // P)
-    x_first, xl = rank * xl_blk, count // (n1 * n2)
-    x3 = a[:count].reshape(xl, n1, n2)
-    direct = torch.zeros(len(ks), 2, dtype=torch.float64)
-    got = torch.zeros(len(ks), 2, dtype=torch.float64)
-    two_pi = 2.0 * math.pi
-    for i, (kx, ky, kz) in enumerate(ks):
-        def phase(k, n, idx):
-            ang = (-two_pi * ((k * idx) % n).to(torch.float64) / n)
-            return torch.complex(torch.cos(ang), torch.sin(ang))
-        ez = phase(kz, n2, torch.arange(n2, device=dev))
-        ey = phase(ky, n1, torch.arange(n1, device=dev))
-        ex = phase(kx, n0, torch.arange(x_first, x_first + xl, device=dev))
-        v = ((x3.to(torch.complex128) @ ez) @ ey * ex).sum() if cdt == torch.complex128 else \
-            (((x3 @ ez.to(cdt)).to(torch.complex128)) @ ey * ex).sum()
-        direct[i, 0], direct[i, 1] = float(v.real), float(v.imag)
-        d_owner = min(ky // yl_blk, P - 1)
-        if rank == d_owner:
-            e = b[((ky - d_owner * yl_blk) * n2 + kz) * n0 + kx]
-            got[i, 0], got[i, 1] = float(e.real), float(e.imag)
-    if P > 1:
-        dist.all_reduce(direct, op=dist.ReduceOp.SUM)
-        dist.all_reduce(got, op=dist.ReduceOp.SUM)
-    spot_err = float(((direct - got).pow(2).sum(dim=1).sqrt().max() / direct.pow(2).sum(dim=1).sqrt().max().clamp_min(1e-300)).item())
-    del x3
+        # ---- error: the driver's round-trip metric (fftSpeed3d_c2c.cpp:84-91) on the device, plus an oracle spot check ----
+        fwd_out = b.clone()
+        c = torch.zeros(max_count, dtype=cdt, device=dev)
+        planb = api.Plan(n0, n1, n2, fwd_out, c, comm, rank, P, api.BACKWARD, api.PLAN_DEFAULT)
+        barrier()
+        planb.execute(api.EXEC_ASYNC)
+        planb.sync()
+        rt_err = float((a[:count] - c[:count] / N).abs().max().item())
+        if P > 1:
+            t = torch.tensor([rt_err], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            rt_err = float(t.item())
+        planb.destroy()
+        del c, fwd_out
 
-    # ---- context for the roofline fraction: what a plain device-to-device copy of one pass's bytes achieves right now ----
-    copy_gbs = None
-    if rank == 0 and not stub_mode:
-        try:
-            dst = torch.empty_like(a)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            for _ in range(2):
-                dst.copy_(a)
-            e0.record()
-            for _ in range(5):
-                dst.copy_(a)
-            e1.record()
-            torch.cuda.synchronize()
-            copy_gbs = 2.0 * a.numel() * S / (e0.elapsed_time(e1) / 5 * 1e-3) / 1e9
-            del dst
-        except Exception:
-            copy_gbs = None
+        # ---- independent full-size check: X[k] = sum_n x[n] e^{-2 pi i k.n/N} evaluated directly (fp64, summed over the
+        # ranks' slabs) for a few seeded k, against the element of the distributed result that should hold it ----
+        ks = [(0, 0, 0), (1, 2, 3), (n0 // 2, n1 - 1, n2 // 3), (n0 - 1, n1 // 2 + 1, n2 - 1), (n0 // 3, n1 // 5, 1)]
+        xl_blk, yl_blk = -(-n0 // P), -(-n1 // P)
+        x_first, xl = rank * xl_blk, count // (n1 * n2)
+        x3 = a[:count].reshape(xl, n1, n2)
+        direct = torch.zeros(len(ks), 2, dtype=torch.float64)
+        got = torch.zeros(len(ks), 2, dtype=torch.float64)
+        two_pi = 2.0 * math.pi
+        for i, (kx, ky, kz) in enumerate(ks):
+            def phase(k, n, idx):
+                ang = (-two_pi * ((k * idx) % n).to(torch.float64) / n)
+                return torch.complex(torch.cos(ang), torch.sin(ang))
+            ez = phase(kz, n2, torch.arange(n2, device=dev))
+            ey = phase(ky, n1, torch.arange(n1, device=dev))
+            ex = phase(kx, n0, torch.arange(x_first, x_first + xl, device=dev))
+            v = ((x3.to(torch.complex128) @ ez) @ ey * ex).sum() if cdt == torch.complex128 else \
+                (((x3 @ ez.to(cdt)).to(torch.complex128)) @ ey * ex).sum()
+            direct[i, 0], direct[i, 1] = float(v.real), float(v.imag)
+            d_owner = min(ky // yl_blk, P - 1)
+            if rank == d_owner:
+                e = b[((ky - d_owner * yl_blk) * n2 + kz) * n0 + kx]
+                got[i, 0], got[i, 1] = float(e.real), float(e.imag)
+        if P > 1:
+            dist.all_reduce(direct, op=dist.ReduceOp.SUM)
+            dist.all_reduce(got, op=dist.ReduceOp.SUM)
+        spot_err = float(((direct - got).pow(2).sum(dim=1).sqrt().max() / direct.pow(2).sum(dim=1).sqrt().max().clamp_min(1e-300)).item())
+        del x3
+
+        # ---- context for the roofline fraction: what a plain device-to-device copy of one pass's bytes achieves right now ----
+        copy_gbs = None
+        if rank == 0 and not stub_mode:
+            try:
+                dst = torch.empty_like(a)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                for _ in range(2):
+                    dst.copy_(a)
+                e0.record()
+                for _ in range(5):
+                    dst.copy_(a)
+                e1.record()
+                torch.cuda.synchronize()
+                copy_gbs = 2.0 * a.numel() * S / (e0.elapsed_time(e1) / 5 * 1e-3) / 1e9
+                del dst
+            except Exception:
+                copy_gbs = None
+    elif plan_s is not None:
+        plan_s.destroy()  # kept through the timed steps for the serial diagnostic of --full
 
     result = None
-    if rank == 0:
+    if args.full and rank == 0:
         local_bytes = 2.0 * S * (N / P)  # each compute stage reads + writes its N/P elements once
         names = ["fft_rows Z", "fft_cols Y(+pack)", "fft_cols X(+transpose)"]
         roof = None
@@ -738,6 +751,7 @@ def main():
                     "local_pipeline": {"bytes": 2 * local_bytes, "GB/s": round(2 * local_bytes / float(stage[0] + stage[1] + stage[3]) / 1e9, 1)}}
             roof["traffic"], roof["traffic_source"] = measured_traffic(f"{n0}x{n1}x{n2}_{args.precision}_P{P}", names[k])
         total_stage = float(sum(stage))
+    if rank == 0:
         result = {
             "metric": "GFlops/s forward 3D C2C (5 N log2 N), 512^3 fp64" if args.size == (512, 512, 512) and args.precision == "fp64"
                       else f"GFlops/s forward 3D C2C (5 N log2 N), {n0}x{n1}x{n2} {args.precision}",
@@ -752,36 +766,40 @@ def main():
                                     else "hipIpc peer copies + stream-ordered flag words (DFFT_EXCHANGE=ipc-async)"
                                     if exchange_backend == "ipc-async" else "RCCL grouped send/recv over xGMI") +
                                    (", X-plane parts overlapped with t0 on a second stream (stages_ms.t2 = exposed part)" if overlap else "")},
-            "max_error": rt_err / 1e7, "roundtrip_abs_error": rt_err,
-            "direct_dft_spot_check_rel_error": spot_err,  # 5 output elements against the defining sum over all ranks' input
-            "stages_ms": {"t0": round(float(stage[0]) * 1e3, 4), "t1": round(float(stage[1]) * 1e3, 4),
-                          "t2": round(float(stage[2]) * 1e3, 4), "t3": round(float(stage[3]) * 1e3, 4)},
-            "t2_fraction": round(float(stage[2]) / total_stage, 4) if total_stage > 0 else None,
-            "roofline": roof,
-            "reference_published": {"value": 644.112, "unit": "GFlops/s", "config": "512^3 fp64, 4 ranks, unnamed AMD GPUs "
-                                    "(README.md:54 of the reference); comparable only at n_gpus=4"},
         }
+        if args.full:
+            result.update({
+                "max_error": rt_err / 1e7, "roundtrip_abs_error": rt_err,
+                "direct_dft_spot_check_rel_error": spot_err,  # 5 output elements against the defining sum over all ranks' input
+                "stages_ms": {"t0": round(float(stage[0]) * 1e3, 4), "t1": round(float(stage[1]) * 1e3, 4),
+                              "t2": round(float(stage[2]) * 1e3, 4), "t3": round(float(stage[3]) * 1e3, 4)},
+                "t2_fraction": round(float(stage[2]) / total_stage, 4) if total_stage > 0 else None,
+                "roofline": roof,
+            })
+        result["reference_published"] = {"value": 644.112, "unit": "GFlops/s", "config": "512^3 fp64, 4 ranks, unnamed AMD GPUs "
+                                         "(README.md:54 of the reference); comparable only at n_gpus=4"}
         if tune_report is not None:
             result["plan_tune"] = tune_report  # X-pass kernel time per candidate hand-over buffer, the one kept, and its re-timing
         if P == 4 and args.size == (512, 512, 512) and args.precision == "fp64":
             result["vs_baseline"] = round(gflops / 644.112, 3)
         if P > 1:
-            pair = S * N / (P * P)
-            t2_full = float(serial_stage[2]) if serial_stage is not None else float(stage[2])
-            result["xgmi"] = {"pair_chunk_bytes": pair, "t2_full_ms": round(t2_full * 1e3, 4),
-                              "achieved_GB/s_per_link": round(pair / t2_full / 1e9, 1) if t2_full > 0 else None,
-                              "peak_GB/s_per_link": 153.0}
-            if overlap:
-                result["stages_ms_without_overlap"] = None if serial_stage is None else {
-                    "t0": round(float(serial_stage[0]) * 1e3, 4), "t1": round(float(serial_stage[1]) * 1e3, 4),
-                    "t2": round(float(serial_stage[2]) * 1e3, 4), "t3": round(float(serial_stage[3]) * 1e3, 4)}
-                result["overlap_result_bit_identical"] = same
-                if referee_forms_note is not None:
-                    result["overlap_result_within_referee_tolerance"] = referee_same
-            elif referee_same is not None:
-                result["overlap_result_bit_identical"] = referee_bits  # the referee's findings before the fallback
-                if referee_forms_note is not None:
-                    result["overlap_result_within_referee_tolerance"] = referee_same
+            if args.full:
+                pair = S * N / (P * P)
+                t2_full = float(serial_stage[2]) if serial_stage is not None else float(stage[2])
+                result["xgmi"] = {"pair_chunk_bytes": pair, "t2_full_ms": round(t2_full * 1e3, 4),
+                                  "achieved_GB/s_per_link": round(pair / t2_full / 1e9, 1) if t2_full > 0 else None,
+                                  "peak_GB/s_per_link": 153.0}
+                if overlap:
+                    result["stages_ms_without_overlap"] = None if serial_stage is None else {
+                        "t0": round(float(serial_stage[0]) * 1e3, 4), "t1": round(float(serial_stage[1]) * 1e3, 4),
+                        "t2": round(float(serial_stage[2]) * 1e3, 4), "t3": round(float(serial_stage[3]) * 1e3, 4)}
+                    result["overlap_result_bit_identical"] = same
+                    if referee_forms_note is not None:
+                        result["overlap_result_within_referee_tolerance"] = referee_same
+                elif referee_same is not None:
+                    result["overlap_result_bit_identical"] = referee_bits  # the referee's findings before the fallback
+                    if referee_forms_note is not None:
+                        result["overlap_result_within_referee_tolerance"] = referee_same
             result["pipeline"] = "overlapped" if overlap else "serial"
             if comm_fallback is not None:
                 result["exchange_fallback"] = comm_fallback
@@ -791,7 +809,7 @@ def main():
                 result["overlap_referee"] = referee_forms_note
             if pipeline_probe_ms is not None:
                 result["pipeline_probe_ms_per_step"] = pipeline_probe_ms
-        if P == 1 and not args.no_cpu_baseline:
+        if args.full and P == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline()
     plan.destroy()
     if comm is not None:

@@ -117,7 +117,7 @@ def test_bench_two_gpus_on_rccl(gpu):
     two devices.  The report must say RCCL ran (no fall-back), the overlapped pipeline must match the serial one bit for bit,
     and the result must pass the direct-DFT spot check over both ranks' inputs."""
     outs = _launch(2, [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--size", "256", "--steps", "5", "--warmup", "2",
-                       "--no-cpu-baseline"], {"DFFT_EXCHANGE": "rccl", "DFFT_BENCH_ALLOW_SHARED_GPU": "0"}, timeout=600)
+                       "--full", "--no-cpu-baseline"], {"DFFT_EXCHANGE": "rccl", "DFFT_BENCH_ALLOW_SHARED_GPU": "0"}, timeout=600)
     d = json.loads([l for l in outs[0][0].splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and "RCCL" in d["config"]["exchange"] and "exchange_fallback" not in d
     assert d["overlap_result_bit_identical"] is True
@@ -256,7 +256,7 @@ def test_bench_falls_back_to_ipc_when_rccl_cannot_start(gpu):
     which once left a rank inside the call until the 180 s watchdog) -- every rank agrees on the failure and the run continues on
     the stream-ordered IPC communicator; the report says so."""
     outs = _launch(2, [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--size", "64", "--steps", "3", "--warmup", "1",
-                       "--no-cpu-baseline"],
+                       "--full", "--no-cpu-baseline"],
                    {"DFFT_EXCHANGE": "rccl", "NCCL_DEBUG": "WARN",
                     # one visible device (the first of whatever is visible now): both ranks land on it even on a multi-GPU box
                     "HIP_VISIBLE_DEVICES": os.environ.get("HIP_VISIBLE_DEVICES", "0").split(",")[0]}, timeout=300)
@@ -271,7 +271,7 @@ def test_bench_multirank_flow_with_real_data(gpu, world, size, backend):
     """bench.py --gpus W exactly as the driver launches it (one rank per process, torchrun-style environment), with the IPC
     exchange so that all ranks can share the one GPU: every check of the N > 1 report on real transforms."""
     outs = _launch(world, [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--size", size, "--steps", "4",
-                           "--warmup", "2", "--no-cpu-baseline"], {"DFFT_EXCHANGE": backend})
+                           "--warmup", "2", "--full", "--no-cpu-baseline"], {"DFFT_EXCHANGE": backend})
     lines = [l for l in outs[0][0].splitlines() if l.startswith("{")]
     assert len(lines) == 1 and outs[0][0].strip() == lines[0]          # exactly one line on rank 0's stdout
     for o, _ in outs[1:]:
@@ -288,6 +288,21 @@ def test_bench_multirank_flow_with_real_data(gpu, world, size, backend):
         assert d["stages_ms_without_overlap"]["t2"] > 0
     assert d["xgmi"]["pair_chunk_bytes"] == 16 * n ** 3 // world ** 2 and "ipc" in d["config"]["exchange"].lower()
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["achieved"] > 0
+
+
+def test_bench_multirank_plain_run_with_real_data(gpu):
+    """bench.py --gpus 2 without --full on real transforms: the referee and the probe still choose the pipeline before the warm-up,
+    every rank destroys alike what it set up (plan destruction is a collective on the IPC communicator; the serial plan kept for
+    --full's diagnostic too when the overlapped pipeline was timed), and the one line carries the headline figure and none of
+    --full's measurements."""
+    outs = _launch(2, [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--size", "64", "--steps", "4", "--warmup", "2"],
+                   {"DFFT_EXCHANGE": "ipc-async"})
+    lines = [l for l in outs[0][0].splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and outs[0][0].strip() == lines[0] and outs[1][0].strip() == ""
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    assert d["pipeline"] in ("overlapped", "serial") and set(d["pipeline_probe_ms_per_step"]) == {"overlapped", "serial"}
+    assert not {"stages_ms", "roundtrip_abs_error", "direct_dft_spot_check_rel_error", "roofline", "xgmi"} & set(d)
 
 
 STRESS_WORKER = r'''

@@ -321,16 +321,23 @@ from distributedfft_amd import api
 
 # Replace the native plan / communicator objects by stubs: NOTHING is computed; this only drives bench.py's multi-rank
 # control flow and report assembly (the part that cannot be exercised on a single-GPU box).
+import atexit, collections
+calls = collections.Counter()   # what bench.py asked the plans to do, on stderr at exit
+atexit.register(lambda: print("STUB_CALLS " + json.dumps(calls), file=sys.stderr, flush=True))
 class StubPlan:
     def __init__(self, n0, n1, n2, a, b, comm, rank, P, direction, flags=0):
         self.a, self.b, self.direction, self.flags = a, b, direction, flags
+        calls["forward_plans" if direction > 0 else "backward_plans"] += 1
     def execute(self, flags=0):
+        calls["executes"] += 1
         n = min(self.a.numel(), self.b.numel())
         self.b[:n] = self.a[:n] * (1.0 if self.direction > 0 else 4096.0)   # "backward(forward(x)) = N x" for 16^3
         if (self.flags & api.PLAN_OVERLAP) and os.environ.get("STUB_BREAK_OVERLAP") == os.environ["RANK"]:
             self.b[3] += 1.0   # an overlapped pipeline that corrupts one element on one rank
     def sync(self): pass
-    def stage_times(self): return [1e-3, 0.0, (5e-4 if self.flags & api.PLAN_OVERLAP else 2e-3), 1e-3]
+    def stage_times(self):
+        calls["stage_times"] += 1
+        return [1e-3, 0.0, (5e-4 if self.flags & api.PLAN_OVERLAP else 2e-3), 1e-3]
     def kernel_times(self): raise api.DfftError(-1, "stub", "interleaved")
     def destroy(self): pass
 class StubComm:
@@ -356,7 +363,7 @@ def test_bench_multirank_report_with_stubbed_plans(native_lib, world):
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), DFFT_ROOT=str(ROOT))
+                   MASTER_PORT=str(port), DFFT_ROOT=str(ROOT), STUB_EXTRA_ARGS="--full")
         procs.append(subprocess.Popen([sys.executable, "-c", STUB_WORKER], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
@@ -380,7 +387,7 @@ def test_bench_falls_back_to_serial_pipeline_when_overlap_result_differs(native_
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), DFFT_ROOT=str(ROOT), STUB_BREAK_OVERLAP="1")
+                   MASTER_PORT=str(port), DFFT_ROOT=str(ROOT), STUB_BREAK_OVERLAP="1", STUB_EXTRA_ARGS="--full")
         procs.append(subprocess.Popen([sys.executable, "-c", STUB_WORKER], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
@@ -390,6 +397,30 @@ def test_bench_falls_back_to_serial_pipeline_when_overlap_result_differs(native_
     assert "overlap_fallback" in d and "serial pipeline" in d["overlap_fallback"]
     assert d["stages_ms"]["t2"] == 2.0 and "stages_ms_without_overlap" not in d   # the serial plan's stage times
     assert "overlapped" not in d["config"]["exchange"] and d["value"] > 0
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_does_only_the_headline_work(native_lib, world):
+    """Without --full a run sets up, warms up, times its steps and prints the line: no stage timing, no serial diagnostic, no
+    backward plan for the round trip (the stub plans count what they are asked to do), and none of --full's fields in the line."""
+    import json
+    port = _free_port()
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), DFFT_ROOT=str(ROOT))
+        procs.append(subprocess.Popen([sys.executable, "-c", STUB_WORKER], env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=300) for p in procs]
+    for p, (o, e) in zip(procs, outs):
+        assert p.returncode == 0, e[-3000:]
+        calls = json.loads([l for l in e.splitlines() if l.startswith("STUB_CALLS ")][-1].split(" ", 1)[1])
+        # warm-up 1 + steps 3; P > 1: the referee runs the overlapped and the serial plan once each before the warm-up
+        assert calls == ({"forward_plans": 1, "executes": 1 + 3} if world == 1 else {"forward_plans": 2, "executes": 2 + 1 + 3})
+    d = json.loads([l for l in outs[0][0].splitlines() if l.startswith("{")][-1])
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                      "vs_baseline", "dtype", "data", "config", "reference_published"} | ({"pipeline"} if world > 1 else set())
+    assert d["n_gpus"] == world and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["dtype"] == "f64"
 
 
 def test_bench_dumps_the_timed_output_of_every_rank(native_lib, tmp_path):

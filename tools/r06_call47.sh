@@ -9,7 +9,7 @@ timeout 900 python tools/roundtrip_check.py 2>&1 | grep "^ok\|^FAIL\|shapes" > $
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 PROFILE_SKIP_NOCHUNK=1 timeout 1200 bash tools/profile_bench.sh r06 > $OUT/profile_bench.log 2>&1
 cd $R
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err; cut -c1-300 $OUT/bench_driver_args.json
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err; cut -c1-300 $OUT/bench_driver_args.json
 L=$OUT/backward_status_final.log; : > $L
 SPECS="512x512x512:fp64:1 512x512x512:fp64:4 1024x768x512:fp64:8 1024x768x512:fp64:1 2048x2048x1024:fp32:8 1024x1024x1024:fp32:1 2048x1024x512:fp64:1 512x512x512:fp32:1 1024x768x512:fp32:1 1024x1024x1024:fp64:1"
 for rep in 1 2; do

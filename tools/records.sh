@@ -26,7 +26,7 @@ cd $R
 python tools/sweep_bench.py 3d > $OUT/sweep_3d.csv 2> /dev/null
 python tools/long_axis_bench.py > $OUT/long_axis_kernels.csv 2> /dev/null
 bash tools/tune_check.sh $OUT/tune_check_final.log 6 > /dev/null 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err
 skip pytest || python -m pytest tests -m gpu -q > $OUT/pytest_gpu_full.log 2>&1
 if ! skip local; then
 python tools/local_by_P.py 512x512x512 fp64 4 2>&1 | grep -v amdgpu.ids > $OUT/local_by_P.log

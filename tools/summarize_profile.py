@@ -69,7 +69,7 @@ def timed_region(run: str, out: str, steps: int = 20):
     rows = [r for r in csv.DictReader(open(max(files, key=lambda f: Path(f).stat().st_mtime))) if "dfft::" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     names = [short(r["Kernel_Name"]) for r in rows]
-    # bench.py ends with one backward execute (round-trip check): cut at the last forward X pass
+    # bench.py --full ends with one backward execute (round-trip check): cut at the last forward X pass
     last = max(i for i, n in enumerate(names) if "TuneTransposedStore" in n and "dir=1" in n)
     xs = [i for i in range(last + 1) if "TuneTransposedStore" in names[i] and "dir=1" in names[i]]
     first = xs[-steps - 1] + 1 if len(xs) > steps else 0  # the region starts behind the X pass of the execute before it
