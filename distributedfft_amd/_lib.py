@@ -20,6 +20,7 @@ ALLOC_HOST, ALLOC_DEV = 1, -1
 F64, F32 = 0, 1
 PLAN_DEFAULT, PLAN_UNFUSED, PLAN_INPUT_FROM_IN, PLAN_OVERLAP, PLAN_NATURAL, PLAN_ANY_LENGTH = 0, 1, 2, 4, 8, 16
 EXEC_ASYNC, EXEC_SYNC_STAGES, EXEC_PRINT, EXEC_NO_TIMING = 0, 1, 2, 4
+FILTER_COMPLEX, FILTER_REAL = 0, 1
 OK, EINVAL, EHIP, ERCCL, ENOGPU, ECOMM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
 _LL = C.c_longlong
@@ -55,6 +56,10 @@ SIGNATURES = {
     "dfft_plan_create_r2c": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_plan_create_r2c_any": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_r2c_counts": (C.c_int, [_LL, _LL, _LL, C.c_int, C.c_int, _LLP, _LLP]),
+    "dfft_plan_create_conv": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
+    "dfft_conv_filter_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
+    "dfft_conv_set_filter": (C.c_int, [_VP, _VP, C.c_int]),
+    "dfft_conv_set_kernel": (C.c_int, [_VP, _VP]),
     "dfft_plan_buffer1": (_VP, [_VP]),
     "dfft_plan_result": (_VP, [_VP]),
     "dfft_plan_stream": (_VP, [_VP]),

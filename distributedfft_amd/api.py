@@ -12,7 +12,7 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import _lib as L
-from ._lib import (BACKWARD, EXEC_ASYNC, EXEC_NO_TIMING, EXEC_PRINT, EXEC_SYNC_STAGES, F32, F64, FORWARD, PLAN_ANY_LENGTH,  # noqa: F401
+from ._lib import (BACKWARD, EXEC_ASYNC, EXEC_NO_TIMING, EXEC_PRINT, EXEC_SYNC_STAGES, F32, F64, FILTER_COMPLEX, FILTER_REAL, FORWARD, PLAN_ANY_LENGTH,  # noqa: F401
                    PLAN_DEFAULT, PLAN_INPUT_FROM_IN, PLAN_NATURAL, PLAN_OVERLAP, PLAN_UNFUSED, DfftError)
 
 
@@ -345,6 +345,84 @@ class PlanR2C(Plan):
         t = torch.as_tensor(r, device=self.device)
         assert t.dtype == tdtype
         return t
+
+
+def conv_filter_count(n0, n1, n2, total_devices: int, global_idx: int) -> int:
+    """Elements of device global_idx's share of a PlanConv filter: local_n1 * N2 * N0 (dfft_conv_filter_count)."""
+    n = int(L.load().dfft_conv_filter_count(n0, n1, n2, total_devices, global_idx))
+    if n < 0:
+        raise ValueError("conv_filter_count: bad arguments")
+    return n
+
+
+class PlanConv(Plan):
+    """Spectral-filter plan (dfft_plan_create_conv): y = ifftn(fftn(x) * H) with numpy's conventions, inp / out complex128 / complex64
+    X slabs [x_local][N1][N2]; out None or inp: in place.  inp is read at every execute.  The filter is given with set_filter (its
+    spectrum, in a forward Plan's output layout [y_local][N2][N0]; a real tensor selects the real-filter kernels) or set_kernel (a
+    real-space kernel in the input layout).  Shares Plan's execute / sync / describe / stage_times / set_scale / destroy; set_scale takes
+    effect at the next set_filter / set_kernel."""
+
+    def __init__(self, n0, n1, n2, inp, out, comm: Optional[Comm], global_idx: int, total_devices: int, flags: int = PLAN_DEFAULT):
+        import torch
+        lib = L.load()
+        if not inp.is_cuda:
+            raise DfftError(L.ENOGPU, "PlanConv", "buffers must live on a HIP device (no CPU fallback)")
+        self.N = (int(n0), int(n1), int(n2))
+        self.dtype = _dtype_code(inp)
+        self.direction = FORWARD
+        self.total_devices, self.global_idx = total_devices, global_idx
+        self.max_count = get_data_count(self.N, total_devices, global_idx)
+        self.filter_count = conv_filter_count(n0, n1, n2, total_devices, global_idx)
+        if inp.numel() < self.max_count or (out is not None and out.numel() < self.max_count):
+            raise ValueError(f"in/out must hold getDataCount = {self.max_count} elements")
+        if out is not None and out.dtype != inp.dtype:
+            raise TypeError("PlanConv: inp and out must have the same dtype")
+        self._in, self._out, self._comm = inp, out, comm  # keep alive
+        self.handle = C.c_void_p()
+        torch.cuda.synchronize(inp.device)
+        with torch.cuda.device(inp.device):
+            L.check(lib.dfft_plan_create_conv(C.byref(self.handle), n0, n1, n2, self.dtype, inp.data_ptr(),
+                                              out.data_ptr() if out is not None else None,
+                                              comm.handle if comm is not None else None, global_idx, total_devices, flags),
+                    "dfft_plan_create_conv")
+        self.device = inp.device
+
+    def _check_operand(self, t, what: str, count: int, dtypes) -> None:
+        """Argument checks of set_filter / set_kernel, made before the library is called."""
+        if not hasattr(t, "dtype") or not hasattr(t, "is_contiguous"):
+            raise TypeError(f"PlanConv.{what}: a torch tensor is required")
+        name = str(t.dtype).replace("torch.", "")
+        if name not in dtypes:
+            raise TypeError(f"PlanConv.{what}: dtype {name} does not match the plan's precision (expected {' or '.join(dtypes)})")
+        if t.numel() != count:
+            raise ValueError(f"PlanConv.{what}: {count} elements expected on this device, got {t.numel()}")
+        if not t.is_contiguous():
+            raise ValueError(f"PlanConv.{what}: the tensor must be contiguous")
+        if not t.is_cuda or t.device != self.device:
+            raise ValueError(f"PlanConv.{what}: the tensor must live on the plan's device {self.device}")
+
+    def set_filter(self, h) -> None:
+        """The filter's spectrum on this device, [y_local][N2][N0] (any shape with that many elements, C order): complex tensor of the
+        plan's dtype, or a real tensor of the matching precision for a real filter.  The plan keeps a private copy."""
+        import torch
+        cplx, real = ("complex128", "float64") if self.dtype == F64 else ("complex64", "float32")
+        self._check_operand(h, "set_filter", self.filter_count, (cplx, real))
+        kind = FILTER_COMPLEX if h.is_complex() else FILTER_REAL
+        with torch.cuda.device(self.device):
+            L.check(L.load().dfft_conv_set_filter(self.handle, h.data_ptr(), kind), "dfft_conv_set_filter")
+
+    def set_kernel(self, k) -> None:
+        """The filter is fftn(k): k is a real-space kernel in the plan's input layout [x_local][N1][N2], complex dtype of the plan."""
+        import torch
+        self._check_operand(k, "set_kernel", self.max_count, ("complex128" if self.dtype == F64 else "complex64",))
+        with torch.cuda.device(self.device):
+            L.check(L.load().dfft_conv_set_kernel(self.handle, k.data_ptr()), "dfft_conv_set_kernel")
+
+    def load_input(self, src) -> None:
+        raise DfftError(L.EUNSUPPORTED, "PlanConv.load_input", "spectral-filter plans read `inp` at every execute")
+
+    def buffer1_tensor(self, count: Optional[int] = None):
+        raise DfftError(L.EUNSUPPORTED, "PlanConv.buffer1_tensor", "spectral-filter plans have no caller-visible bufferDev1")
 
 
 def fft_mpi_plan_dft_c2c_3d(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags=PLAN_DEFAULT) -> Plan:

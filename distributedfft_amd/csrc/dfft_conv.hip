@@ -1,0 +1,338 @@
+// dfft_conv.hip -- the X stage of the spectral-filter plans (dfft_plan_create_conv): y = ifft_x( fft_x(data) . H ) along the slow axis of the
+// slab [x][row][z] that the forward YZ stage (P > 1: the forward exchange) leaves and the inverse YZ stage (the backward exchange) picks up.
+//
+// Fused form, xconv_cols_kernel (N0 = 64, 128, 256, 384, 512, 768, 1024): one launch, in place.  A thread group owns a tile of CB adjacent
+// columns (CB * sizeof(V) = 128 bytes: 8 fp64 columns, or 8 PAIRS of fp32 columns), loads the N0 points of every column, issues the loads
+// of the same tile of the filter copy behind them (the copy has the data's physical layout, so one offset serves both operands), runs the
+// tuned forward stages of the C2C kernels (run_stages, dfft_fft_impl.h) -- which leave bin j + T k where point j + T k was loaded --,
+// multiplies, runs the inverse as conj . forward . conj (one set of forward twiddles serves both halves; the form the Bluestein column
+// kernel uses) and stores where it loaded.  Three volume-sized streams (data in, filter, data out; two and a half with a real filter)
+// instead of the seven of forward X pass + multiply + inverse X pass, and no transpose in either direction.  1 / (N0 N1 N2) and the plan's
+// scale are folded into the filter copy.
+//
+// Multi route (every other single-pass length, fp32 slabs that cannot be read as column pairs, DFFT_CONV_FUSED=0): the C2C column kernels
+// in place along X (launch_fft), xconv_mul_kernel, the inverse column kernels -- same filter copy.
+//
+// Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the lengths of group g) and once with
+// -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the multiply and the re-layout kernel).
+#include "dfft_fft_impl.h"
+#include "dfft_internal.h"
+#include "dfft_plans.h"
+#include "dfft_conv.h"
+
+#include <algorithm>
+#include <atomic>
+
+#ifndef DFFT_INST_GROUP
+#error "compile with -DDFFT_INST_GROUP=<g>"
+#endif
+
+namespace dfft {
+
+constexpr bool conv_fused_n(int n) { return n == 64 || n == 128 || n == 256 || n == 384 || n == 512 || n == 768 || n == 1024; }
+
+template <int N> struct XcPlanFor;
+#define DFFT_DECL_XC_PLAN(N, GRP, E, ...) \
+    template <> struct XcPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
+DFFT_PLAN_TABLE(DFFT_DECL_XC_PLAN)
+#undef DFFT_DECL_XC_PLAN
+
+// entry point of length N: defined (and explicitly instantiated) in the translation unit of N's group only
+template <bool ON, int N> struct XcInst {};
+template <int N> struct XcInst<true, N> {
+    static hipError_t run(const ConvLaunch& L, hipStream_t stream);
+};
+
+#if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
+
+// Geometry: full-line tiles (the C2C column kernel's cols_per_tile: 8 elements of 16 bytes for every fused length -- the 1024-point tile
+// is 128 KiB of the CU's 160 KiB LDS), at most 512 threads per workgroup so that a thread may use 256 registers: it keeps its E points
+// live across two transforms while up to E filter elements are in flight.
+template <class V, class P> struct XcGeom {
+    static constexpr int CB = cols_per_tile<V, P>();
+    static_assert(CB * (int)sizeof(V) == 128 && CB * P::T <= 512, "fused conv lengths use full-line tiles of at most 512 threads");
+    static constexpr int G = ConstMax1<256 / (CB * P::T)>::value;
+    using KG = KernelGeom<V, P, CB, G, TuneDefault>;
+    static_assert(KG::PH == 1, "single-phase tiles only");
+};
+
+// filter element as it lies in memory, per data type V and filter kind
+template <class V, bool REAL> struct XcFilter;
+template <> struct XcFilter<double2, false> {
+    using T = double2;
+    static __device__ __forceinline__ double2 mul(double2 a, T h) { return double2{a.x * h.x - a.y * h.y, a.x * h.y + a.y * h.x}; }
+};
+template <> struct XcFilter<double2, true> {
+    using T = double;
+    static __device__ __forceinline__ double2 mul(double2 a, T h) { return double2{a.x * h, a.y * h}; }
+};
+template <> struct XcFilter<cpair, false> {
+    using T = f32x4;  // (re0, im0, re1, im1) of two adjacent columns
+    static __device__ __forceinline__ cpair mul(cpair a, T g) {
+        const cpair h = VecTraits<cpair>::from_g(g);
+        return cpair{a.x * h.x - a.y * h.y, a.x * h.y + a.y * h.x};
+    }
+};
+template <> struct XcFilter<cpair, true> {
+    using T = f32x2;  // the two columns' reals
+    static __device__ __forceinline__ cpair mul(cpair a, T h) { return cpair{a.x * h, a.y * h}; }
+};
+template <class V> __device__ __forceinline__ V xc_conj(V a) { return V{a.x, -a.y}; }
+
+// One launch per X stage.  Thread group g of a workgroup owns tile r0 + g = (row r, column block b): columns [b CB, b CB + CB) of row r
+// in every plane x.  All strides in units of one V (fp32: pairs of columns).  in == out is the normal case: a tile reads all its points
+// before its first exchange and writes them after the last one, and no two tiles share an element.
+template <class V, class P, bool REAL, bool ROT>
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, XcGeom<V, P>::KG::THREADS)))
+xconv_cols_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* out, const typename XcFilter<V, REAL>::T* __restrict__ filt,
+                  const typename VecTraits<V>::W* __restrict__ tw, unsigned plane, long long pitch, unsigned tiles, unsigned tiles_per_row,
+                  int ncols, int rot, int mask, int forward_only, double scale) {
+    using XG = XcGeom<V, P>;
+    using KG = typename XG::KG;
+    using VT = VecTraits<V>;
+    using W = typename VT::W;
+    using RT = typename real_of<W>::type;
+    using F = XcFilter<V, REAL>;
+    constexpr int  E = P::E, T = P::T, G = XG::G, GT = KG::GT, CB = XG::CB;
+    constexpr bool TWPOW = KG::TWMODE == TW_REG;
+    // The filter loads are issued right behind the data loads wherever data and filter fit the thread's registers together: always in
+    // workgroups of at most 256 threads (one wave per SIMD may use 512 registers: 384 points, 96 + 96), and in 512-thread workgroups (256
+    // registers) up to 12 points.  16 points of 16 bytes with a complex filter (1024 points: 64 + 64 registers, next to 16 offsets and the
+    // butterflies' temporaries) do not fit -- that form kept 92-124 bytes per lane in scratch -- and read the filter between the two
+    // transforms instead.
+    constexpr bool EARLY = REAL || E * (int)sizeof(V) / 4 < 64 || KG::THREADS <= 256;
+    extern __shared__ __attribute__((aligned(16))) char dfft_smem[];
+    const int g = threadIdx.x / GT;
+    const int tid = (int)threadIdx.x - g * GT;
+    const int c = tid % CB;
+    const int j = tile_j<CB, KG::NW>(tid);
+    V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * KG::LDS_ELEMS;
+    W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
+    const W*  twr = twreg;
+    if constexpr (KG::TWMODE == TW_GLOBAL) {
+        twr = tw;
+    } else if constexpr (KG::TWMODE == TW_LDS) {
+        fill_stage_major<W, P, 0, +1, KG::NW>(reinterpret_cast<W*>(dfft_smem), tw, (int)threadIdx.x, KG::THREADS);
+        __syncthreads();
+        twr = reinterpret_cast<W*>(dfft_smem);
+    } else {
+        load_twiddles<W, P, 0, +1, true>(twreg, tw, j);
+    }
+    // rotated rows: point k of this thread lies in plane j + T k, whose rows are rotated by rot * (j + T k) mod the row length
+    const int rot_j = ROT ? (rot * j) & mask : 0, rot_t = ROT ? (rot * T) & mask : 0;
+    const RT  sc = (RT)scale;
+    for (unsigned r0 = blockIdx.x * G; r0 < tiles; r0 += gridDim.x * G) {
+        const unsigned t = r0 + g;
+        bool           valid = t < tiles;
+        const unsigned r = valid ? t / tiles_per_row : 0u;
+        const int      col = (int)((valid ? t - r * tiles_per_row : 0u) * CB) + c;
+        valid = valid && col < ncols;
+        const long long base = (long long)r * pitch;
+        unsigned        off[E];
+#pragma unroll
+        for (int k = 0; k < E; ++k) {
+            const unsigned x = (unsigned)(j + T * k);
+            off[k] = x * plane + (unsigned)(ROT ? ((col + rot_j + k * rot_t) & mask) : col);
+        }
+        V                    v[E];
+        typename F::T        h[EARLY ? E : 1];
+        if (valid) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) v[k] = VT::from_g(in[base + off[k]]);
+            if (EARLY && !forward_only) {  // behind the data loads, so that they fly under the forward stages
+#pragma unroll
+                for (int k = 0; k < E; ++k) h[EARLY ? k : 0] = filt[base + off[k]];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+                v[k] = VT::zero();
+                h[EARLY ? k : 0] = typename F::T{};
+            }
+        }
+        run_stages<V, P, 0, +1, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, c);
+        if (forward_only) {  // (uniform over the launch) the filter copy of dfft_conv_set_kernel: the scaled spectrum, same layout
+            if (valid) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) out[base + off[k]] = VT::to_g(cscale(v[k], sc));
+            }
+            group_sync<KG::WAVE_LOCAL>();  // the next tile's exchanges reuse the tile
+            continue;
+        }
+        // (A . H) conjugated: the inverse transform is conj(FFT(conj(A . H))); 1 / N is in H
+#pragma unroll
+        for (int k = 0; k < E; ++k) {
+            if constexpr (EARLY) v[k] = xc_conj(F::mul(v[k], h[k]));
+            else v[k] = valid ? xc_conj(F::mul(v[k], filt[base + off[k]])) : VT::zero();
+        }
+        group_sync<KG::WAVE_LOCAL>();  // the second transform's exchanges reuse the tile
+        run_stages<V, P, 0, +1, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, c);
+        if (valid) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) out[base + off[k]] = VT::to_g(xc_conj(v[k]));
+        }
+        group_sync<KG::WAVE_LOCAL>();  // the next tile's exchanges reuse the tile
+    }
+}
+
+// persistent grid: resident workgroups per CU (occupancy query, once per kernel and device) times the CUs
+template <class KG> int xc_blocks_per_cu(const void* kern, std::atomic<int>* cache) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    int occ = cache[dev].load(std::memory_order_acquire);
+    if (occ > 0) return occ;
+    if (KG::LDS_BYTES > 64 * 1024 &&
+        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KG::LDS_BYTES) != hipSuccess)
+        return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, KG::THREADS, KG::LDS_BYTES) != hipSuccess || occ < 1) {
+        (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
+        occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, KG::LDS_BYTES));
+    }
+    cache[dev].store(occ, std::memory_order_release);
+    return occ;
+}
+
+template <class V, class P, bool REAL, bool ROT> hipError_t launch_xconv(const ConvLaunch& L, hipStream_t stream) {
+    using XG = XcGeom<V, P>;
+    using KG = typename XG::KG;
+    using VT = VecTraits<V>;
+    constexpr int           LANES = VT::LANES, CB = XG::CB, G = XG::G;
+    static std::atomic<int> occ_cache[64];
+    const long long         ncols = L.ncols / LANES, plane = L.plane / LANES, pitch = L.pitch / LANES;
+    const long long         per_row = (ncols + CB - 1) / CB, tiles = L.rows * per_row;
+    // 32-bit offsets inside a row's columns, 32-bit tile counts: the largest element offset is below (n0 - 1) * plane + pitch
+    if (tiles < 1 || tiles >= (1ll << 31) || (long long)L.n0 * plane + pitch >= (1ll << 32)) return hipErrorInvalidValue;
+    if (ROT != (L.rot > 0) || (ROT && ((ncols & (ncols - 1)) != 0 || L.rot % LANES != 0))) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    auto      kern = xconv_cols_kernel<V, P, REAL, ROT>;
+    const int occ = xc_blocks_per_cu<KG>(reinterpret_cast<const void*>(kern), occ_cache);
+    if (occ < 0) return hipErrorInvalidDevice;
+    const long long grid = std::min<long long>((long long)device_info().cus * occ, (tiles + G - 1) / G);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const typename VT::G*)L.in, (typename VT::G*)L.out,
+                       (const typename XcFilter<V, REAL>::T*)L.filt, (const typename VT::W*)L.tw, (unsigned)plane, pitch, (unsigned)tiles,
+                       (unsigned)per_row, (int)ncols, L.rot / LANES, (int)ncols - 1, L.forward_only, L.scale);
+    return hipGetLastError();
+}
+
+template <class V, class P> hipError_t launch_xconv_vp(const ConvLaunch& L, hipStream_t stream) {
+    if (L.filter_real) return L.rot > 0 ? launch_xconv<V, P, true, true>(L, stream) : launch_xconv<V, P, true, false>(L, stream);
+    return L.rot > 0 ? launch_xconv<V, P, false, true>(L, stream) : launch_xconv<V, P, false, false>(L, stream);
+}
+
+template <int N> hipError_t XcInst<true, N>::run(const ConvLaunch& L, hipStream_t stream) {
+    if (L.dtype == F64) return launch_xconv_vp<double2, typename XcPlanFor<N>::type>(L, stream);
+    if (L.dtype == F32) return launch_xconv_vp<cpair, typename XcPlanFor<N>::type>(L, stream);
+    return hipErrorInvalidValue;
+}
+#define DFFT_XC_INST(N, GRP, E, ...) template struct XcInst<(GRP == DFFT_INST_GROUP && conv_fused_n(N)), N>;
+DFFT_PLAN_TABLE(DFFT_XC_INST)
+#undef DFFT_XC_INST
+
+#else  // the dispatcher, the multiply of the multi route and the filter re-layout
+
+namespace {
+
+// data[i] *= filt[i]: D = 16 bytes of data (one fp64 element, two fp32 elements), H the filter elements that go with them
+template <class D, class H> __device__ __forceinline__ D xc_mul16(D d, H h);
+template <> __device__ __forceinline__ double2 xc_mul16(double2 d, double2 h) { return double2{d.x * h.x - d.y * h.y, d.x * h.y + d.y * h.x}; }
+template <> __device__ __forceinline__ double2 xc_mul16(double2 d, double h) { return double2{d.x * h, d.y * h}; }
+template <> __device__ __forceinline__ f32x4 xc_mul16(f32x4 d, f32x4 h) {
+    return f32x4{d.x * h.x - d.y * h.y, d.x * h.y + d.y * h.x, d.z * h.z - d.w * h.w, d.z * h.w + d.w * h.z};
+}
+template <> __device__ __forceinline__ f32x4 xc_mul16(f32x4 d, f32x2 h) { return f32x4{d.x * h.x, d.y * h.x, d.z * h.y, d.w * h.y}; }
+
+template <class D, class H>
+__global__ void __launch_bounds__(256) xconv_mul_kernel(D* __restrict__ data, const H* __restrict__ filt, long long n16) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) data[i] = xc_mul16(data[i], filt[i]);
+}
+// the odd last element of an fp32 buffer
+__global__ void xconv_mul_tail_kernel(float2* data, const float* filt, long long i, int real) {
+    const float2 d = data[i];
+    if (real) data[i] = float2{d.x * filt[i], d.y * filt[i]};
+    else data[i] = float2{d.x * filt[2 * i] - d.y * filt[2 * i + 1], d.x * filt[2 * i + 1] + d.y * filt[2 * i]};
+}
+
+// dst[layout(kx, r, z)] = scale * h[(r * ncols + z) * n0 + kx], COMPS scalars per element (2: complex, 1: real); e runs over the source
+template <class S, int COMPS>
+__global__ void __launch_bounds__(256) xconv_relayout_kernel(const S* __restrict__ h, S* __restrict__ dst, long long n0, long long ncols,
+                                                             long long plane, long long pitch, int rot, long long total, double scale) {
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long rz = e / n0, kx = e - rz * n0;
+        const long long r = rz / ncols, z = rz - r * ncols;
+        const long long zz = rot > 0 ? ((z + (long long)rot * kx) & (ncols - 1)) : z;
+        const long long o = kx * plane + r * pitch + zz;
+#pragma unroll
+        for (int i = 0; i < COMPS; ++i) dst[o * COMPS + i] = (S)((double)h[e * COMPS + i] * scale);
+    }
+}
+
+unsigned xc_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
+
+template <int N> hipError_t xc_run(const ConvLaunch& L, hipStream_t stream) {
+    if constexpr (conv_fused_n(N)) return XcInst<true, N>::run(L, stream);
+    else return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+bool conv_fused_length(int n0) { return conv_fused_n(n0); }
+
+bool conv_fused_applies(const ConvLaunch& L) {
+    if (!conv_fused_n(L.n0) || L.rows < 1 || L.ncols < 1) return false;
+    if (L.rot > 0 && (L.ncols & (L.ncols - 1)) != 0) return false;
+    if (L.dtype == F32 && ((L.ncols | L.plane | L.pitch | (long long)L.rot) & 1)) return false;  // fp32 runs on column pairs
+    const long long lanes = L.dtype == F32 ? 2 : 1;
+    return (long long)L.n0 * (L.plane / lanes) + L.pitch / lanes < (1ll << 32) && L.rows * ((L.ncols / lanes + 7) / 8) < (1ll << 31);
+}
+
+hipError_t launch_conv_fused(const ConvLaunch& L, hipStream_t stream) {
+    if (!conv_fused_applies(L)) return hipErrorInvalidValue;
+    switch (L.n0) {
+#define DFFT_XC_CASE(N, GRP, E, ...) \
+    case N: return xc_run<N>(L, stream);
+        DFFT_PLAN_TABLE(DFFT_XC_CASE)
+#undef DFFT_XC_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_conv_mul(int dtype, int filter_real, void* data, const void* filt, long long count, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    (void)hipGetLastError();
+    if (dtype == F64) {
+        if (filter_real) hipLaunchKernelGGL((xconv_mul_kernel<double2, double>), dim3(xc_grid(count)), dim3(256), 0, stream, (double2*)data, (const double*)filt, count);
+        else hipLaunchKernelGGL((xconv_mul_kernel<double2, double2>), dim3(xc_grid(count)), dim3(256), 0, stream, (double2*)data, (const double2*)filt, count);
+        return hipGetLastError();
+    }
+    if (dtype != F32) return hipErrorInvalidValue;
+    const long long n16 = count / 2;
+    if (n16 > 0) {
+        if (filter_real) hipLaunchKernelGGL((xconv_mul_kernel<f32x4, f32x2>), dim3(xc_grid(n16)), dim3(256), 0, stream, (f32x4*)data, (const f32x2*)filt, n16);
+        else hipLaunchKernelGGL((xconv_mul_kernel<f32x4, f32x4>), dim3(xc_grid(n16)), dim3(256), 0, stream, (f32x4*)data, (const f32x4*)filt, n16);
+    }
+    if (count & 1) hipLaunchKernelGGL(xconv_mul_tail_kernel, dim3(1), dim3(1), 0, stream, (float2*)data, (const float*)filt, count - 1, filter_real);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_relayout(const ConvLaunch& L, const void* h, void* dst, hipStream_t stream) {
+    const long long total = L.rows * L.ncols * (long long)L.n0;
+    if (total <= 0) return hipSuccess;
+    if (L.rot > 0 && (L.ncols & (L.ncols - 1)) != 0) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    const dim3 grid(xc_grid(total)), block(256);
+    if (L.dtype == F64 && L.filter_real)
+        hipLaunchKernelGGL((xconv_relayout_kernel<double, 1>), grid, block, 0, stream, (const double*)h, (double*)dst, (long long)L.n0, L.ncols, L.plane, L.pitch, L.rot, total, L.scale);
+    else if (L.dtype == F64)
+        hipLaunchKernelGGL((xconv_relayout_kernel<double, 2>), grid, block, 0, stream, (const double*)h, (double*)dst, (long long)L.n0, L.ncols, L.plane, L.pitch, L.rot, total, L.scale);
+    else if (L.dtype == F32 && L.filter_real)
+        hipLaunchKernelGGL((xconv_relayout_kernel<float, 1>), grid, block, 0, stream, (const float*)h, (float*)dst, (long long)L.n0, L.ncols, L.plane, L.pitch, L.rot, total, L.scale);
+    else if (L.dtype == F32)
+        hipLaunchKernelGGL((xconv_relayout_kernel<float, 2>), grid, block, 0, stream, (const float*)h, (float*)dst, (long long)L.n0, L.ncols, L.plane, L.pitch, L.rot, total, L.scale);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+#endif
+
+}  // namespace dfft

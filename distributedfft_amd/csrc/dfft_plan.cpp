@@ -28,6 +28,7 @@
 #include <thread>
 
 #include "dfft_bluestein.h"
+#include "dfft_conv.h"
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
@@ -335,10 +336,35 @@ struct dfft_plan_s {
     bool                    rfused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
     void*                   rscratch = nullptr;
     size_t                  rscratch_bytes = 0;
+    // spectral-filter plans (dfft_plan_create_conv).  The handle the caller holds has `conv` set and owns two HALF plans: a forward plan
+    // that stops in front of its X pass and a backward plan that starts behind its inverse X pass (conv_half; the stage code of
+    // execute_forward / execute_backward, minus launch_x), which share the stream and the hand-over buffer; the X stage in between is
+    // dfft_conv.hip's.  conv_no_rot: a half plan whose X stage takes the multi route keeps plain rows in its exchange buffers (the in-place
+    // C2C column kernels exist for plain rows only).  borrowed: stream and hand-over buffer belong to the other half.
+    struct ConvState*       conv = nullptr;
+    bool                    conv_half = false, conv_no_rot = false, borrowed = false;
     std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
     int                     w_kept = -1;
     float                   w_final_ms = 0.f;  // the kept candidate re-timed after the others were freed
 };
+
+// state of a spectral-filter plan (dfft_plan_s::conv)
+struct ConvState {
+    dfft_plan_s *f = nullptr, *b = nullptr;  // the forward / backward half plans
+    void*        sbuf = nullptr;             // send buffer of the forward exchange (plans with a communicator)
+    void*        filt = nullptr;             // the filter copy, in the hand-over slab's physical layout
+    size_t       filt_bytes = 0;
+    int          kind = -1;                  // DFFT_FILTER_*; -1: no filter yet
+    bool         fused = false;              // xconv_cols_kernel (else the multi route)
+    ConvLaunch   L{};                        // the X stage's slab: buffers, strides, rotation
+    long long    slab_elems = 0;             // elements of the slab, padding included (= elements of the filter copy)
+    double       x_host = 0;                 // host-timed X stage of the last DFFT_EXEC_SYNC_STAGES execute
+};
+static int conv_execute(dfft_plan_s* p, unsigned exec_flags);
+static int conv_describe(const dfft_plan_s* p, char* buf, int len);
+static int conv_sync(dfft_plan_s* p);
+static int conv_stage_times(dfft_plan_s* p, double t[4]);
+static int conv_destroy(dfft_plan_s* p);
 
 static int fill_exchange(dfft_plan_s* p, ExchangeDesc& x, int direction) {
     const int       P = p->P, me = p->me;
@@ -777,7 +803,9 @@ static int execute_forward(dfft_plan_s* p, bool sync) {
     }
     DFFT_TRY(clk.end_stage());
     // ---- t3: X FFT (+ transpose to [yl][N2][N0]) ----
-    if (fused) {
+    if (p->conv_half) {
+        // (spectral-filter plans: the X stage works in place on what t0 / t2 left -- dfft_conv.hip, conv_x_stage)
+    } else if (fused) {
         DFFT_TRY(launch_x(p, xsrc, p->buf2, false, 0, (!p->exch && p->wbuf) ? &zl : nullptr));
     } else {
         hipError_t e = launch_transpose(p->dtype, p->buf1, p->buf2, n0, p->ys * n2, p->stream);
@@ -880,7 +908,10 @@ static int execute_backward(dfft_plan_s* p, bool sync) {
     // ---- inverse X FFT: [ys][N2][kx] -> [x][ys][N2] ----
     // (single GPU: straight into the padded work buffer -- the plane-strided 128-byte stores are the scattered side here)
     const bool xw = fused && !p->exch && p->wbuf;
-    if (fused) {
+    if (p->conv_half) {
+        // (spectral-filter plans: the X stage has left its result where the inverse X pass would have -- the hand-over buffer, the result
+        // buffer, or the send buffer of the exchange, which conv plans point at the forward half's receive buffer)
+    } else if (fused) {
         DFFT_TRY(launch_x(p, src, xw ? p->wbuf : p->buf2, false, 0, xw ? &yl : nullptr));
     } else {
         DFFT_TRY(fft_rows(src, p->buf1, (int)n0, p->ys * n2, p->dtype, p->direction, p->stream, 0, 0, p->scale));
@@ -1350,8 +1381,9 @@ int dfft_free(void* p, int flag) {
     return DFFT_OK;
 }
 
-int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
-                     void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+// conv_half: 0 = dfft_plan_create; 1 / 2 = a half plan of dfft_plan_create_conv (2: plain rows in the exchange buffers)
+static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
+                            void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, int conv_half) {
     if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create: null plan/in");
     if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, "dfft_plan_create: sizes must be positive");
     if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, "dfft_plan_create: dtype");
@@ -1382,6 +1414,8 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     trace("dfft_plan_create", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
     dfft_plan_s* p = new dfft_plan_s;
     p->long_axis = long_axis;
+    p->conv_half = conv_half != 0;
+    p->conv_no_rot = conv_half == 2;
     p->N[0] = n0;
     p->N[1] = n1;
     p->N[2] = n2;
@@ -1418,7 +1452,7 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     p->out = out;
     p->inplace = (out == nullptr || out == in);  // fft_mpi_3d_api.cpp:68-75
     p->buf2 = p->inplace ? in : out;
-    if (p->inplace && (flags & DFFT_PLAN_INPUT_FROM_IN)) {
+    if (p->inplace && (flags & DFFT_PLAN_INPUT_FROM_IN) && !conv_half) {  // (a forward half plan never writes its result buffer)
         delete p;
         return fail(DFFT_EINVAL, "dfft_plan_create: DFFT_PLAN_INPUT_FROM_IN needs an out-of-place plan");
     }
@@ -1457,7 +1491,8 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     // differed from the serial result in 2 of 20 four-process runs).  So: everything the caller queued (whatever stream produced
     // `in`) is waited for, the copy runs on the plan's own stream, and plan creation returns when it has landed.
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyAsync(p->buf1, in, bytes, hipMemcpyDeviceToDevice, p->stream);
+    // (half plans of a spectral-filter plan capture nothing: their `in` holds dfft_local_count elements, not dfft_max_count)
+    if (e == hipSuccess && !conv_half) e = hipMemcpyAsync(p->buf1, in, bytes, hipMemcpyDeviceToDevice, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     for (auto& ev : p->ev)
         if (e == hipSuccess) e = hipEventCreate(&ev);
@@ -1574,7 +1609,7 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
         // themselves).  DFFT_ROT=0 / 1 forces it off / on (wherever it is possible).
         const char*     re = getenv("DFFT_ROT");
         const long long S = (long long)elem_bytes(dtype);
-        const bool      possible = p->exch && !(flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL)) && !p->long_axis && n0 % total_devices == 0 &&
+        const bool      possible = p->exch && !p->conv_no_rot && !(flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL)) && !p->long_axis && n0 % total_devices == 0 &&
                               n1 % total_devices == 0 && (n2 & (n2 - 1)) == 0 && (n2 * S) % 128 == 0 && n2 * S >= 256 && n2 < (1ll << 30) &&
                               fft_length_tuned((int)n0) && fft_length_tuned((int)n1) && fft_length_tuned((int)n2);
         const long long ysub = p->ys / std::max(1, p->ycuts);
@@ -1787,6 +1822,11 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
     return DFFT_OK;
 }
 
+int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
+                     void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    return plan_create_impl(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, 0);
+}
+
 int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices, int global_idx, long long* real_count, long long* complex_count) {
     if (n0 < 1 || n1 < 1 || n2 < 2 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices)
         return fail(DFFT_EINVAL, "dfft_r2c_counts: bad arguments");
@@ -1799,6 +1839,330 @@ int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices,
     const long long send = (long long)(total_devices - 1) * xs * sy.blk * nh + xs * sy.size(total_devices - 1) * nh;
     if (real_count) *real_count = xs * n1 * n2;
     if (complex_count) *complex_count = std::max(ys * nh * n0, total_devices > 1 ? send : 0ll);
+    return DFFT_OK;
+}
+
+}  // extern "C"
+
+// ---- spectral-filter (FFT convolution) plans ---------------------------------------------------------------------------------------
+// y = ifftn(fftn(x) . H): forward half plan (YZ stage, exchange) -> X stage in place on the slab it leaves (dfft_conv.hip: forward X
+// transform, multiply by the filter copy, inverse X transform) -> backward half plan (exchange, inverse YZ stage).
+static int conv_alloc_filter(dfft_plan_s* p, int kind) {
+    ConvState*   c = p->conv;
+    const size_t need = (size_t)c->slab_elems * elem_bytes(p->dtype) / (kind == DFFT_FILTER_REAL ? 2 : 1);
+    if (c->filt && c->filt_bytes >= need) return DFFT_OK;
+    DFFT_HIP_TRY(hipStreamSynchronize(p->stream));  // an execute that still reads the old copy
+    if (c->filt) (void)hipFree(c->filt);
+    c->filt = nullptr;
+    c->filt_bytes = 0;
+    c->kind = -1;
+    DFFT_HIP_TRY(hipMalloc(&c->filt, need));
+    c->filt_bytes = need;
+    DFFT_HIP_TRY(hipMemsetAsync(c->filt, 0, need, p->stream));  // the padding of the layout is read (and multiplied into padding)
+    return DFFT_OK;
+}
+
+// The X stage on the plan's stream.  to_filter: the forward transform alone, times `scale`, into the filter copy (dfft_conv_set_kernel).
+static int conv_x_stage(dfft_plan_s* p, bool to_filter, double scale) {
+    ConvState* c = p->conv;
+    ConvLaunch L = c->L;
+    DFFT_TRY(get_twiddles(L.n0, p->dtype, &L.tw));
+    L.filt = c->filt;
+    L.filter_real = (!to_filter && c->kind == DFFT_FILTER_REAL) ? 1 : 0;
+    if (c->fused) {
+        if (to_filter) {
+            L.forward_only = 1;
+            L.out = c->filt;
+            L.scale = scale;
+        }
+        return check_launch(launch_conv_fused(L, p->stream), "X stage of the spectral-filter plan");
+    }
+    // multi route: the C2C column kernels in place along X, the multiply, the inverse column kernels into the slab the backward half reads
+    FftLaunch X;
+    std::memset(&X, 0, sizeof(X));
+    X.dtype = p->dtype;
+    X.n = L.n0;
+    X.dir = DFFT_FORWARD;
+    X.cols = 1;
+    X.in = L.in;
+    X.out = to_filter ? c->filt : const_cast<void*>(L.in);
+    X.tw = L.tw;
+    X.imap = X.omap = plain_axis(L.n0, L.plane, 1);
+    X.itile = X.otile = TileMap{L.pitch, 1};
+    X.na = L.rows;
+    X.ncols = (int)L.ncols;
+    X.scale = to_filter ? scale : 1.0;
+    X.grid_limit = p->grid_x;
+    DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the spectral-filter plan (forward columns)"));
+    if (to_filter) return DFFT_OK;
+    DFFT_TRY(check_launch(launch_conv_mul(p->dtype, L.filter_real, const_cast<void*>(L.in), c->filt, c->slab_elems, p->stream),
+                          "X stage of the spectral-filter plan (multiply)"));
+    X.dir = DFFT_BACKWARD;
+    X.out = L.out;
+    return check_launch(launch_fft(X, p->stream), "X stage of the spectral-filter plan (inverse columns)");
+}
+
+static int conv_execute(dfft_plan_s* p, unsigned exec_flags) {
+    ConvState* c = p->conv;
+    if (c->kind < 0) return fail(DFFT_EINVAL, "dfft_execute: this spectral-filter plan has no filter yet (dfft_conv_set_filter / dfft_conv_set_kernel)");
+    const bool     sync = (exec_flags & DFFT_EXEC_SYNC_STAGES) != 0;
+    const unsigned half_flags = exec_flags & ~DFFT_EXEC_PRINT;
+    p->host_timed = sync;
+    p->timed = sync || !(exec_flags & DFFT_EXEC_NO_TIMING);
+    // a half that fails on this device alone must not leave the peers waiting in the other half's exchange: with a communicator the
+    // sequence is queued to its end and the first failure is the return code
+    int         rc = dfft_execute(c->f, half_flags);
+    std::string msg = rc ? g_last_error : std::string();
+    if (rc && !p->exch) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int        rx = conv_x_stage(p, false, 1.0);
+    if (rx == DFFT_OK && sync) {
+        const hipError_t e = hipStreamSynchronize(p->stream);
+        if (e != hipSuccess) rx = fail(DFFT_EHIP, std::string("X stage of the spectral-filter plan: ") + hipGetErrorString(e));
+        c->x_host = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (rx && !rc) {
+        rc = rx;
+        msg = g_last_error;
+    }
+    if (rc && !p->exch) return rc;
+    const int rb = dfft_execute(c->b, half_flags);
+    if (rc) return fail(rc, msg);
+    return rb;
+}
+
+static int conv_describe(const dfft_plan_s* p, char* buf, int len) {
+    const ConvState* c = p->conv;
+    char             half[512] = "";
+    (void)dfft_plan_describe(c->f, half, (int)sizeof(half));
+    const char* yz = strstr(half, "yz_stage=");
+    char        yzs[64] = "yz_stage=?";
+    if (yz) sscanf(yz, "%63s", yzs);
+    snprintf(buf, (size_t)len, "pipeline=conv xconv=%s filter=%s %s handover=%s rotated_exchange_rows=%d", c->fused ? "fused" : "multi",
+             c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"), yzs,
+             (!p->exch && c->f->wbuf) ? "padded-buffer" : (p->exch ? "receive-buffer" : "bufferDev1"), c->L.rot);
+    return DFFT_OK;
+}
+
+static int conv_sync(dfft_plan_s* p) {
+    ConvState* c = p->conv;
+    DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
+    DFFT_TRY(zy_check(c->f));
+    DFFT_TRY(zy_check(c->b));
+    if (p->comm) return comm_check(p->comm);
+    return DFFT_OK;
+}
+
+// t = forward YZ stage (with the packing), both exchanges, the X stage, inverse YZ stage (with the unpacking)
+static int conv_stage_times(dfft_plan_s* p, double t[4]) {
+    ConvState* c = p->conv;
+    DFFT_TRY(conv_sync(p));
+    if (!p->timed) return fail(DFFT_EINVAL, "dfft_stage_times: the last execute ran with DFFT_EXEC_NO_TIMING");
+    const dfft_plan_s *f = c->f, *b = c->b;
+    if (p->host_timed) {
+        t[0] = f->host_t[0] + f->host_t[1];
+        t[1] = f->host_t[2] + b->host_t[1];
+        t[2] = f->host_t[3] + c->x_host + b->host_t[0];
+        t[3] = b->host_t[2] + b->host_t[3];
+        return DFFT_OK;
+    }
+    auto ms = [](hipEvent_t a, hipEvent_t z, double* out) {
+        float v = 0;
+        DFFT_HIP_TRY(hipEventElapsedTime(&v, a, z));
+        *out = v * 1e-3;
+        return (int)DFFT_OK;
+    };
+    double x1 = 0, x2 = 0;
+    DFFT_TRY(ms(f->ev[0], f->ev[2], &t[0]));
+    DFFT_TRY(ms(f->ev[2], f->ev[3], &x1));
+    DFFT_TRY(ms(b->ev[1], b->ev[2], &x2));
+    t[1] = x1 + x2;
+    DFFT_TRY(ms(f->ev[3], b->ev[1], &t[2]));
+    DFFT_TRY(ms(b->ev[2], b->ev[4], &t[3]));
+    return DFFT_OK;
+}
+
+static int conv_destroy(dfft_plan_s* p) {
+    ConvState* c = p->conv;
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    int rc = DFFT_OK;
+    if (c->b) {  // (the stream and the hand-over buffer are the forward half's)
+        const int r = dfft_plan_destroy(c->b);
+        if (!rc) rc = r;
+    }
+    if (c->f) {
+        const int r = dfft_plan_destroy(c->f);
+        if (!rc) rc = r;
+    }
+    if (c->sbuf) (void)hipFree(c->sbuf);
+    if (c->filt) (void)hipFree(c->filt);
+    delete c;
+    delete p;
+    return rc;
+}
+
+extern "C" {
+
+long long dfft_conv_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx) {
+    if (n0 < 1 || n1 < 1 || n2 < 1 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return -1;
+    return make_slab(n1, total_devices).size(global_idx) * n2 * n0;
+}
+
+int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
+                          int global_idx, int total_devices, unsigned flags) {
+    const std::string fn = "dfft_plan_create_conv";
+    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
+    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
+    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
+    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
+    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
+    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
+    if (flags != DFFT_PLAN_DEFAULT)
+        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT is supported (no OVERLAP, NATURAL, UNFUSED, INPUT_FROM_IN -- which is "
+                                            "implied -- or ANY_LENGTH spectral-filter plans)");
+    for (long long n : {n0, n1, n2})
+        if (length_kind(n) != 1)
+            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) + " -- every axis must be a single-pass length (products of 2, 3, 5, 7 up to 4096)");
+    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
+    if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1) return fail(DFFT_EINVAL, fn + ": slab decomposition leaves the last device empty");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
+
+    const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
+    // fp32 runs the fused kernel on column PAIRS: an even N2 (every other stride of the slab is then even too)
+    const bool  want_fused = !(fe && *fe == '0') && conv_fused_length((int)n0) && (dtype == DFFT_F64 || n2 % 2 == 0);
+    trace("dfft_plan_create_conv", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices);
+    dfft_plan_s* p = new dfft_plan_s;
+    ConvState*   c = new ConvState;
+    p->conv = c;
+    p->N[0] = n0;
+    p->N[1] = n1;
+    p->N[2] = n2;
+    p->dtype = dtype;
+    p->direction = DFFT_FORWARD;
+    p->P = total_devices;
+    p->me = global_idx;
+    p->flags = flags;
+    p->is_last = global_idx == total_devices - 1;
+    p->inplace = out == nullptr || out == in;
+    p->sx = sx;
+    p->sy = sy;
+    p->xs = sx.size(global_idx);
+    p->ys = sy.size(global_idx);
+    p->max_count = dfft_max_count(n0, n1, n2, total_devices, p->is_last);
+    p->in = in;
+    p->out = p->inplace ? in : out;
+    p->buf1 = p->buf2 = nullptr;
+    p->comm = comm;
+    p->device = 0;
+    p->stream = nullptr;
+    for (auto& e : p->ev) e = nullptr;
+    for (double& t : p->host_t) t = 0;
+    p->host_timed = false;
+    p->chunk_planes = 0;
+    p->grid_x = env_grid("DFFT_X_GRID");
+    auto bail = [&](int rc) {
+        const std::string msg = g_last_error;
+        (void)conv_destroy(p);
+        return fail(rc, msg);
+    };
+    if (comm) {  // the forward half packs into a send buffer of the plan's own: `in` is left alone, and `out` may be `in`
+        const hipError_t e = hipMalloc(&c->sbuf, (size_t)p->max_count * elem_bytes(dtype));
+        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": send buffer: " + hipGetErrorString(e)));
+    }
+    const int mode = want_fused ? 1 : 2;
+    int       rc = plan_create_impl(&c->f, n0, n1, n2, dtype, DFFT_FORWARD, in, c->sbuf, comm, global_idx, total_devices, DFFT_PLAN_INPUT_FROM_IN, mode);
+    if (rc) return bail(rc);
+    rc = plan_create_impl(&c->b, n0, n1, n2, dtype, DFFT_BACKWARD, c->f->buf1, p->out, comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, mode);
+    if (rc) return bail(rc);
+    dfft_plan_s *f = c->f, *b = c->b;
+    // one stream, one hand-over buffer
+    (void)hipStreamSynchronize(b->stream);
+    (void)hipStreamDestroy(b->stream);
+    if (b->wbuf) (void)slab_free(b->wbuf);
+    b->stream = f->stream;
+    b->wbuf = f->wbuf;
+    b->wl = f->wl;
+    b->borrowed = true;
+    p->stream = f->stream;
+    p->device = f->device;
+    p->exch = f->exch;
+    if (f->exch != b->exch || f->rot_elems != b->rot_elems) return bail(fail(DFFT_EINVAL, fn + ": internal: the two halves disagree about the exchange"));
+    ConvLaunch& L = c->L;
+    L.dtype = dtype;
+    L.n0 = (int)n0;
+    L.ncols = n2;
+    L.scale = 1.0;
+    if (p->exch) {
+        // the forward exchange's receive layout [x][yl][N2] IS the backward exchange's send layout (fill_exchange, uneven splits included):
+        // the X stage works in place on the forward half's receive buffer and the backward half sends from it
+        for (int q = 0; q < p->P; ++q)
+            if (f->xd.roffset[q] != b->xd.soffset[q] || f->xd.rcount[q] != b->xd.scount[q])
+                return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
+        b->xd.sendbuf = f->buf1;
+        L.in = L.out = f->buf1;
+        L.plane = p->ys * n2;
+        L.pitch = n2;
+        L.rows = p->ys;
+        L.rot = f->rot_elems;
+        c->slab_elems = n0 * p->ys * n2;
+    } else if (f->wbuf) {
+        L.in = L.out = f->wbuf;
+        L.plane = f->wl.plane;
+        L.pitch = f->wl.pitch;
+        L.rows = n1;
+        c->slab_elems = p->xs * f->wl.plane;
+    } else {  // natural layout: out of bufferDev1 of the forward half into the result buffer, where the inverse YZ stage works in place
+        L.in = f->buf1;
+        L.out = b->buf2;
+        L.plane = n1 * n2;
+        L.pitch = n2;
+        L.rows = n1;
+        c->slab_elems = n0 * n1 * n2;
+    }
+    c->fused = want_fused && conv_fused_applies(L);
+    if (!c->fused && L.rot > 0) return bail(fail(DFFT_EINVAL, fn + ": internal: rotated rows without the fused X stage"));
+    *plan = p;
+    return DFFT_OK;
+}
+
+static int conv_check_handle(dfft_plan_t plan, const char* fn) {
+    if (!plan || !plan->conv) return fail(DFFT_EINVAL, std::string(fn) + ": not a spectral-filter plan");
+    return DFFT_OK;
+}
+
+int dfft_conv_set_filter(dfft_plan_t plan, const void* h, int kind) {
+    DFFT_TRY(conv_check_handle(plan, "dfft_conv_set_filter"));
+    if (!h || (kind != DFFT_FILTER_COMPLEX && kind != DFFT_FILTER_REAL)) return fail(DFFT_EINVAL, "dfft_conv_set_filter: null filter or bad kind");
+    ConvState* c = plan->conv;
+    DFFT_HIP_TRY(hipDeviceSynchronize());  // whatever stream produced `h`, and this plan's executes that read the old copy
+    DFFT_TRY(conv_alloc_filter(plan, kind));
+    ConvLaunch R = c->L;
+    R.filter_real = kind == DFFT_FILTER_REAL;
+    R.scale = plan->scale / ((double)plan->N[0] * (double)plan->N[1] * (double)plan->N[2]);
+    DFFT_TRY(check_launch(launch_conv_relayout(R, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
+    DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
+    c->kind = kind;
+    return DFFT_OK;
+}
+
+int dfft_conv_set_kernel(dfft_plan_t plan, const void* k) {
+    DFFT_TRY(conv_check_handle(plan, "dfft_conv_set_kernel"));
+    if (!k) return fail(DFFT_EINVAL, "dfft_conv_set_kernel: null kernel");
+    ConvState* c = plan->conv;
+    DFFT_HIP_TRY(hipDeviceSynchronize());
+    int arc = conv_alloc_filter(plan, DFFT_FILTER_COMPLEX);
+    if (arc && !plan->exch) return arc;
+    // the plan's own forward half on `k` (collective like an execute), then the forward X transform of the slab it leaves, times
+    // scale / N, straight into the filter copy: the slab's layout is the copy's
+    void* const user_in = c->f->in;
+    c->f->in = const_cast<void*>(k);
+    int rc = dfft_execute(c->f, DFFT_EXEC_NO_TIMING);
+    c->f->in = user_in;
+    if (!rc) rc = arc;
+    if (!rc) rc = conv_x_stage(plan, true, plan->scale / ((double)plan->N[0] * (double)plan->N[1] * (double)plan->N[2]));
+    if (rc) return rc;
+    DFFT_TRY(conv_sync(plan));
+    c->kind = DFFT_FILTER_COMPLEX;
     return DFFT_OK;
 }
 
@@ -2002,6 +2366,7 @@ void* dfft_plan_workbuf(dfft_plan_t plan, long long* bytes) {
 
 int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
     if (!plan) return fail(DFFT_EINVAL, "dfft_execute: null plan");
+    if (plan->conv) return conv_execute(plan, exec_flags);
     const bool sync = (exec_flags & DFFT_EXEC_SYNC_STAGES) != 0;
     plan->host_timed = sync;
     plan->timed = sync || !(exec_flags & DFFT_EXEC_NO_TIMING);
@@ -2065,7 +2430,9 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
         rc = zy_check(plan);
         if (rc) {
             const void* src = (plan->flags & DFFT_PLAN_INPUT_FROM_IN) ? plan->in : plan->buf1;
-            const bool  input_intact = !plan->exch && plan->wbuf && src != plan->buf2 && !(plan->flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL));
+            // (a backward half plan of a spectral-filter plan has no inverse X pass that would rebuild the hand-over buffer)
+            const bool  input_intact = !plan->exch && plan->wbuf && src != plan->buf2 && !(plan->flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL)) &&
+                                      !(plan->conv_half && plan->direction == DFFT_BACKWARD);
             if (!input_intact) return rc;
             if (getenv("DFFT_DEBUG")) fprintf(stderr, "[dfft] %s -- running the transform again on the two-launch stage\n", dfft_last_error());
             rc = run();
@@ -2123,6 +2490,7 @@ static int probe_x_pass(dfft_plan_s* p, void* w, float* ms_out) {
 
 int dfft_plan_tune(dfft_plan_t plan) {
     if (!plan) return fail(DFFT_EINVAL, "dfft_plan_tune: null plan");
+    if (plan->conv) return DFFT_OK;  // the X stage works in place: no read / write placement to choose
     const char* te = getenv("DFFT_TUNE");
     if (te && *te == '0') return DFFT_OK;
     // only fused single-GPU plans with a hand-over buffer have anything to place
@@ -2263,6 +2631,7 @@ int dfft_plan_tune(dfft_plan_t plan) {
 int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
     if (!plan || !buf || len < 64) return fail(DFFT_EINVAL, "dfft_plan_describe: bad arguments");
     const dfft_plan_s* p = plan;
+    if (p->conv) return conv_describe(p, buf, len);
     if (p->r2c) {
         snprintf(buf, (size_t)len, "pipeline=%s n2=%lld bins=%lld chunks=%lldx%lld intermediate_pitch=%lld", p->direction == DFFT_FORWARD ? "r2c" : "c2r",
                  p->n2r, p->N[2], p->chunk_planes > 0 ? (p->xs + p->chunk_planes - 1) / p->chunk_planes : 1ll, p->chunk_planes > 0 ? p->chunk_planes : p->xs,
@@ -2313,6 +2682,7 @@ int dfft_plan_tune_report(dfft_plan_t plan, int max_n, double* ms, int* kept, do
 
 int dfft_plan_sync(dfft_plan_t plan) {
     if (!plan) return fail(DFFT_EINVAL, "dfft_plan_sync: null plan");
+    if (plan->conv) return conv_sync(plan);
     if (plan->P > 1) trace("dfft_plan_sync enter", plan->direction, plan->flags);
     DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
     if (plan->P > 1) trace("dfft_plan_sync stream drained", plan->direction, plan->flags);
@@ -2326,6 +2696,7 @@ int dfft_plan_sync(dfft_plan_t plan) {
 
 int dfft_stage_times(dfft_plan_t plan, double t[4]) {
     if (!plan || !t) return fail(DFFT_EINVAL, "dfft_stage_times: bad arguments");
+    if (plan->conv) return conv_stage_times(plan, t);
     DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
     {
         const int rc = zy_check(plan);
@@ -2350,6 +2721,7 @@ int dfft_stage_times(dfft_plan_t plan, double t[4]) {
 
 int dfft_kernel_times(dfft_plan_t plan, double t[3]) {
     if (!plan || !t) return fail(DFFT_EINVAL, "dfft_kernel_times: bad arguments");
+    if (plan->conv) return fail(DFFT_EUNSUPPORTED, "dfft_kernel_times: not available for spectral-filter plans");
     if (plan->host_timed || !plan->timed)
         return fail(DFFT_EINVAL, "dfft_kernel_times: needs an execute without DFFT_EXEC_SYNC_STAGES / DFFT_EXEC_NO_TIMING");
     if (plan->flags & DFFT_PLAN_UNFUSED) return fail(DFFT_EINVAL, "dfft_kernel_times: fused plans only");
@@ -2378,6 +2750,7 @@ int dfft_kernel_times(dfft_plan_t plan, double t[3]) {
 
 int dfft_plan_destroy(dfft_plan_t plan) {
     if (!plan) return DFFT_OK;
+    if (plan->conv) return conv_destroy(plan);
     if (plan->P > 1) trace("dfft_plan_destroy", plan->direction, plan->flags);
     if (plan->stream) hipStreamSynchronize(plan->stream);
     if (plan->stream2) hipStreamSynchronize(plan->stream2);
@@ -2394,10 +2767,10 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     for (auto& e : plan->y_ev)
         if (e) hipEventDestroy(e);
     if (plan->stream2) hipStreamDestroy(plan->stream2);
-    if (plan->stream) hipStreamDestroy(plan->stream);
+    if (plan->stream && !plan->borrowed) hipStreamDestroy(plan->stream);
     (void)comm_recv_free(plan->comm, plan->buf1);
     (void)comm_recv_free(plan->comm, plan->rbuf);
-    if (plan->wbuf) slab_free(plan->wbuf);
+    if (plan->wbuf && !plan->borrowed) slab_free(plan->wbuf);
     if (plan->lbuf) hipFree(plan->lbuf);
     if (plan->bs.scratch) hipFree(plan->bs.scratch);
     if (plan->rscratch) hipFree(plan->rscratch);

@@ -189,6 +189,38 @@ int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long lon
  * multi-pass>".  Arguments are checked before the device is queried. */
 int dfft_plan_create_r2c_any(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                              void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* ---- spectral-filter (FFT convolution) plans ---------------------------------------------------------------------------------------
+ * y = ifftn( fftn(x) * H ), numpy conventions (normalised: H == 1 gives y == x), C2C, DFFT_F64 / DFFT_F32, slab-decomposed like
+ * dfft_plan_create.  in / out: device buffers in the X-slab layout [x_local][N1][N2] holding dfft_local_count elements; out == in or
+ * NULL: in place.  `in` is read at every execute (no capture at plan time) and is left alone when out != in.
+ * Pipeline: forward YZ stage -> (P > 1: exchange) -> X stage IN PLACE on the slab [x][y_local][N2] (forward X transform, multiply by the
+ * plan's filter copy, inverse X transform: one kernel for N0 = 64, 128, 256, 384, 512, 768, 1024, three launches otherwise or with
+ * DFFT_CONV_FUSED=0, read at plan creation) -> (exchange) -> inverse YZ stage.  Execute allocates nothing.
+ * Accepted: every axis of dfft_length_kind 1; P >= 1 on any communicator; flags DFFT_PLAN_DEFAULT only.  Any other flag and axes of
+ * kind 0, 2 or 3: DFFT_EUNSUPPORTED; NULL plan / in, sizes < 1, a bad dtype or device index: DFFT_EINVAL -- all checked before the
+ * device is queried (then DFFT_ENOGPU without one).
+ * The handle is an ordinary plan: dfft_execute (ASYNC / SYNC_STAGES / NO_TIMING; DFFT_EINVAL before a filter is set), dfft_plan_sync,
+ * dfft_plan_stream, dfft_stage_times (t = forward YZ stage, both exchanges, X stage, inverse YZ stage), dfft_plan_describe
+ * ("pipeline=conv xconv=fused|multi filter=complex|real|unset ...") and dfft_plan_destroy work on it.  dfft_plan_set_scale(s) multiplies
+ * the output by s; the factor is folded into the filter copy, so it TAKES EFFECT AT THE NEXT dfft_conv_set_filter / dfft_conv_set_kernel
+ * (the stored copy is not re-folded).  dfft_plan_tune is a no-op (the X stage works in place: no placement to choose);
+ * dfft_kernel_times returns DFFT_EUNSUPPORTED, dfft_plan_buffer1 / dfft_plan_result / dfft_plan_workbuf NULL. */
+#define DFFT_FILTER_COMPLEX 0
+#define DFFT_FILTER_REAL 1
+int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out,
+                          dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* Elements of this device's share of the filter: local_n1 * N2 * N0 (host-only arithmetic, no device needed); -1 for bad arguments. */
+long long dfft_conv_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx);
+/* The filter's spectrum, given in the layout a forward dfft_plan_create plan of the same shape / communicator returns on this device:
+ * element (yy*N2 + kz)*N0 + kx = H[kx, y0 + yy, kz].  kind DFFT_FILTER_COMPLEX: elements of the plan's complex type;
+ * DFFT_FILTER_REAL: its real type (H real: Green's functions, Gaussians, masks -- half the filter bytes per execute).
+ * The plan keeps a PRIVATE copy, re-laid-out for its X stage and with 1/(N0*N1*N2) and the plan's scale folded in; `h` may be freed or
+ * changed afterwards.  May be called again between executes.  Synchronises the device; never called from dfft_execute. */
+int dfft_conv_set_filter(dfft_plan_t plan, const void* h, int kind);
+/* Convenience: the filter is fftn(k) of a real-space kernel k given in the plan's INPUT layout (complex type).  The plan runs its own
+ * forward half on it (collective over the communicator like an execute) and keeps a complex filter copy.  Synchronises. */
+int dfft_conv_set_kernel(dfft_plan_t plan, const void* k);
+
 /* Elements the caller's buffers of an r2c plan must hold on device global_idx: *real_count reals on the real side (R2C input / C2R
  * output), *complex_count complex elements on the complex side (R2C output / C2R input) -- the result [y_local][Nh][N0] and, for P > 1,
  * the packed send layout of the forward exchange, which the R2C plan writes into `out` before its result.  Pure host arithmetic. */
