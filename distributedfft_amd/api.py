@@ -389,17 +389,18 @@ class PlanConv(Plan):
 
     def _check_operand(self, t, what: str, count: int, dtypes) -> None:
         """Argument checks of set_filter / set_kernel, made before the library is called."""
+        cls = type(self).__name__
         if not hasattr(t, "dtype") or not hasattr(t, "is_contiguous"):
-            raise TypeError(f"PlanConv.{what}: a torch tensor is required")
+            raise TypeError(f"{cls}.{what}: a torch tensor is required")
         name = str(t.dtype).replace("torch.", "")
         if name not in dtypes:
-            raise TypeError(f"PlanConv.{what}: dtype {name} does not match the plan's precision (expected {' or '.join(dtypes)})")
+            raise TypeError(f"{cls}.{what}: dtype {name} does not match the plan's precision (expected {' or '.join(dtypes)})")
         if t.numel() != count:
-            raise ValueError(f"PlanConv.{what}: {count} elements expected on this device, got {t.numel()}")
+            raise ValueError(f"{cls}.{what}: {count} elements expected on this device, got {t.numel()}")
         if not t.is_contiguous():
-            raise ValueError(f"PlanConv.{what}: the tensor must be contiguous")
+            raise ValueError(f"{cls}.{what}: the tensor must be contiguous")
         if not t.is_cuda or t.device != self.device:
-            raise ValueError(f"PlanConv.{what}: the tensor must live on the plan's device {self.device}")
+            raise ValueError(f"{cls}.{what}: the tensor must live on the plan's device {self.device}")
 
     def set_filter(self, h) -> None:
         """The filter's spectrum on this device, [y_local][N2][N0] (any shape with that many elements, C order): complex tensor of the
@@ -423,6 +424,59 @@ class PlanConv(Plan):
 
     def buffer1_tensor(self, count: Optional[int] = None):
         raise DfftError(L.EUNSUPPORTED, "PlanConv.buffer1_tensor", "spectral-filter plans have no caller-visible bufferDev1")
+
+
+def conv_real_filter_count(n0, n1, n2, total_devices: int, global_idx: int) -> int:
+    """Elements of device global_idx's share of a PlanConvReal filter: local_n1 * (N2/2 + 1) * N0 (dfft_conv_real_filter_count)."""
+    n = int(L.load().dfft_conv_real_filter_count(n0, n1, n2, total_devices, global_idx))
+    if n < 0:
+        raise ValueError("conv_real_filter_count: bad arguments")
+    return n
+
+
+class PlanConvReal(PlanConv):
+    """Real-field spectral-filter plan (dfft_plan_create_conv_real): y = irfftn(rfftn(x) * H, s=(N0, N1, N2)) with numpy's conventions,
+    inp / out float64 / float32 X slabs [x_local][N1][N2]; out None or inp: in place.  inp is read at every execute.  set_filter takes
+    the filter's half spectrum in a forward PlanR2C's output layout [y_local][N2/2+1][N0] (complex of the matching precision, or a real
+    tensor for a real filter), set_kernel a real-space kernel in the input layout (real dtype of the plan).  Everything else is
+    PlanConv's; describe() reports the width of the plan's private spectrum as width=<Nc>."""
+
+    def __init__(self, n0, n1, n2, inp, out, comm: Optional[Comm], global_idx: int, total_devices: int, flags: int = PLAN_DEFAULT):
+        import torch
+        lib = L.load()
+        if not inp.is_cuda:
+            raise DfftError(L.ENOGPU, "PlanConvReal", "buffers must live on a HIP device (no CPU fallback)")
+        name = str(inp.dtype).replace("torch.", "")
+        if name not in _R2C_PAIRS:
+            raise TypeError(f"PlanConvReal: buffers must be torch.float64 or torch.float32 device tensors, got {name}")
+        self.N = (int(n0), int(n1), int(n2))
+        self.dtype = F64 if name == "float64" else F32
+        self.direction = FORWARD
+        self.total_devices, self.global_idx = total_devices, global_idx
+        self.max_count = get_data_count(self.N, total_devices, global_idx)
+        self.filter_count = conv_real_filter_count(n0, n1, n2, total_devices, global_idx)
+        if inp.numel() < self.max_count or (out is not None and out.numel() < self.max_count):
+            raise ValueError(f"in/out must hold getDataCount = {self.max_count} elements")
+        if out is not None and out.dtype != inp.dtype:
+            raise TypeError("PlanConvReal: inp and out must have the same dtype")
+        if out is not None and out.device != inp.device:
+            raise ValueError(f"PlanConvReal: inp is on {inp.device}, out on {out.device}")
+        self._in, self._out, self._comm = inp, out, comm  # keep alive
+        self.handle = C.c_void_p()
+        torch.cuda.synchronize(inp.device)
+        with torch.cuda.device(inp.device):
+            L.check(lib.dfft_plan_create_conv_real(C.byref(self.handle), n0, n1, n2, self.dtype, inp.data_ptr(),
+                                                   out.data_ptr() if out is not None else None,
+                                                   comm.handle if comm is not None else None, global_idx, total_devices, flags),
+                    "dfft_plan_create_conv_real")
+        self.device = inp.device
+
+    def set_kernel(self, k) -> None:
+        """The filter is rfftn(k): k is a real-space kernel in the plan's input layout [x_local][N1][N2], real dtype of the plan."""
+        import torch
+        self._check_operand(k, "set_kernel", self.max_count, ("float64" if self.dtype == F64 else "float32",))
+        with torch.cuda.device(self.device):
+            L.check(L.load().dfft_conv_set_kernel(self.handle, k.data_ptr()), "dfft_conv_set_kernel")
 
 
 def fft_mpi_plan_dft_c2c_3d(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags=PLAN_DEFAULT) -> Plan:

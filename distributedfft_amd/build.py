@@ -101,6 +101,8 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         units.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-field spectral-filter plans: the filter re-layout into the plan's private half spectrum
+    units.append((CSRC / "dfft_conv_real.hip", OBJ / "dfft_conv_real.o", []))
     units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
     units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
     units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))

@@ -29,6 +29,7 @@
 
 #include "dfft_bluestein.h"
 #include "dfft_conv.h"
+#include "dfft_conv_real.h"
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
@@ -341,6 +342,9 @@ struct dfft_plan_s {
     // execute_forward / execute_backward, minus launch_x), which share the stream and the hand-over buffer; the X stage in between is
     // dfft_conv.hip's.  conv_no_rot: a half plan whose X stage takes the multi route keeps plain rows in its exchange buffers (the in-place
     // C2C column kernels exist for plain rows only).  borrowed: stream and hand-over buffer belong to the other half.
+    // Real-field plans (dfft_plan_create_conv_real) are the same handle over an R2C and a C2R half plan (create_r2c / execute_r2c with
+    // conv_half set: no X pass, nothing captured at plan time, N[2] = the plan's private complex width Nc >= n2r/2 + 1); there `borrowed`
+    // covers the stream and the complex intermediate cbuf.
     struct ConvState*       conv = nullptr;
     bool                    conv_half = false, conv_no_rot = false, borrowed = false;
     std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
@@ -359,12 +363,29 @@ struct ConvState {
     ConvLaunch   L{};                        // the X stage's slab: buffers, strides, rotation
     long long    slab_elems = 0;             // elements of the slab, padding included (= elements of the filter copy)
     double       x_host = 0;                 // host-timed X stage of the last DFFT_EXEC_SYNC_STAGES execute
+    bool         real = false;               // dfft_plan_create_conv_real: R2C / C2R halves, the slab is the half spectrum at width L.ncols
+    long long    nh = 0;                     // real-field plans: N2/2 + 1, the bins per row the caller's filter has
 };
 static int conv_execute(dfft_plan_s* p, unsigned exec_flags);
 static int conv_describe(const dfft_plan_s* p, char* buf, int len);
 static int conv_sync(dfft_plan_s* p);
 static int conv_stage_times(dfft_plan_s* p, double t[4]);
 static int conv_destroy(dfft_plan_s* p);
+// A half plan of dfft_plan_create_conv_real: the plan's complex width, and the forward half whose stream and intermediate the backward
+// half borrows (nullptr: this IS the forward half)
+struct R2cHalf {
+    long long    nc;
+    dfft_plan_s* share;
+};
+// Elements of the two receive buffers of a real-field spectral-filter plan at complex width nc -- the forward one holds [N0][ys][nc], the
+// backward one the packed [q][xs][yl_q][nc] -- as a bound that is the same on every rank (pooled buffers are matched by size)
+static long long conv_real_recv_count(long long n0, long long n1, long long nc, int P) {
+    const Slab sx = make_slab(n0, P), sy = make_slab(n1, P);
+    return std::max(n0 * sy.blk, (long long)P * sx.blk * sy.blk) * nc;
+}
+
+static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
+                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any, const R2cHalf* half = nullptr);
 
 static int fill_exchange(dfft_plan_s* p, ExchangeDesc& x, int direction) {
     const int       P = p->P, me = p->me;
@@ -1035,11 +1056,13 @@ static int execute_r2c(dfft_plan_s* p, bool sync) {
         DFFT_TRY(clk.end_stage());  // t1 folded into t0
         if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
         DFFT_TRY(clk.end_stage());
-        DFFT_TRY(launch_x(p, p->exch ? p->buf1 : p->cbuf, p->buf2, false, 0, p->exch ? nullptr : lc));
+        // (half plans of a real-field spectral-filter plan: the X stage works in place on what t0 / t2 left -- conv_x_stage -- and has
+        // left its result where the inverse X pass would have: the intermediate, or the send buffer of the backward exchange)
+        if (!p->conv_half) DFFT_TRY(launch_x(p, p->exch ? p->buf1 : p->cbuf, p->buf2, false, 0, p->exch ? nullptr : lc));
         DFFT_TRY(clk.end_stage());
         return DFFT_OK;
     }
-    DFFT_TRY(launch_x(p, src, p->cbuf, false, 0, p->exch ? nullptr : lc));
+    if (!p->conv_half) DFFT_TRY(launch_x(p, src, p->cbuf, false, 0, p->exch ? nullptr : lc));
     DFFT_TRY(clk.end_stage());
     if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
     DFFT_TRY(clk.end_stage());
@@ -1850,7 +1873,15 @@ int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices,
 static int conv_alloc_filter(dfft_plan_s* p, int kind) {
     ConvState*   c = p->conv;
     const size_t need = (size_t)c->slab_elems * elem_bytes(p->dtype) / (kind == DFFT_FILTER_REAL ? 2 : 1);
-    if (c->filt && c->filt_bytes >= need) return DFFT_OK;
+    if (c->filt && c->filt_bytes >= need) {
+        // (real-field plans: the forward-only X stage of dfft_conv_set_kernel writes the columns below the plan's width only, and a copy
+        // that held reals before is re-read as complex elements -- whatever it does not write must read as zero)
+        if (c->real) {
+            DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
+            DFFT_HIP_TRY(hipMemsetAsync(c->filt, 0, c->filt_bytes, p->stream));
+        }
+        return DFFT_OK;
+    }
     DFFT_HIP_TRY(hipStreamSynchronize(p->stream));  // an execute that still reads the old copy
     if (c->filt) (void)hipFree(c->filt);
     c->filt = nullptr;
@@ -1938,6 +1969,12 @@ static int conv_describe(const dfft_plan_s* p, char* buf, int len) {
     const char* yz = strstr(half, "yz_stage=");
     char        yzs[64] = "yz_stage=?";
     if (yz) sscanf(yz, "%63s", yzs);
+    if (c->real) {
+        snprintf(buf, (size_t)len, "pipeline=conv-real xconv=%s filter=%s width=%lld bins=%lld pitch=%lld handover=%s chunk_planes=%lld",
+                 c->fused ? "fused" : "multi", c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"),
+                 c->L.ncols, c->nh, c->L.pitch, p->exch ? "receive-buffer" : "intermediate", c->f->chunk_planes);
+        return DFFT_OK;
+    }
     snprintf(buf, (size_t)len, "pipeline=conv xconv=%s filter=%s %s handover=%s rotated_exchange_rows=%d", c->fused ? "fused" : "multi",
              c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"), yzs,
              (!p->exch && c->f->wbuf) ? "padded-buffer" : (p->exch ? "receive-buffer" : "bufferDev1"), c->L.rot);
@@ -2125,6 +2162,120 @@ int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long lo
     return DFFT_OK;
 }
 
+long long dfft_conv_real_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx) {
+    if (n0 < 1 || n1 < 1 || n2 < 1 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return -1;
+    return make_slab(n1, total_devices).size(global_idx) * (n2 / 2 + 1) * n0;
+}
+
+int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
+                               int global_idx, int total_devices, unsigned flags) {
+    const std::string fn = "dfft_plan_create_conv_real";
+    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
+    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
+    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
+    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
+    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
+    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
+    if (flags != DFFT_PLAN_DEFAULT)
+        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT is supported (no OVERLAP, NATURAL, UNFUSED, INPUT_FROM_IN -- which is "
+                                            "implied -- or ANY_LENGTH spectral-filter plans)");
+    for (long long n : {n0, n1})
+        if (length_kind(n) != 1)
+            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) + " -- N0 and N1 must be single-pass lengths (products of 2, 3, 5, 7 up to 4096)");
+    if (!real_length_supported(n2))
+        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) + " -- the real axis must be of dfft_real_form 1 (even, N2/2 a single-pass length)");
+    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
+    if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1) return fail(DFFT_EINVAL, fn + ": slab decomposition leaves the last device empty");
+    const long long nh = n2 / 2 + 1, nc = conv_real_width(nh, dtype);
+    const long long line = 128 / (long long)elem_bytes(dtype), pitch1 = (nc + line - 1) / line * line;
+    if (std::max(conv_real_recv_count(n0, n1, nc, total_devices), sx.blk * n1 * pitch1) >= (1ll << 31))
+        return fail(DFFT_EUNSUPPORTED, fn + ": more than 2^31 complex elements per device");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
+
+    const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
+    const bool  want_fused = !(fe && *fe == '0') && conv_fused_length((int)n0);
+    trace("dfft_plan_create_conv_real", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices);
+    dfft_plan_s* p = new dfft_plan_s;
+    ConvState*   c = new ConvState;
+    p->conv = c;
+    c->real = true;
+    c->nh = nh;
+    p->N[0] = n0;
+    p->N[1] = n1;
+    p->N[2] = n2;  // the REAL length (1 / (N0 N1 N2) in the filter copy); the halves carry the complex width
+    p->dtype = dtype;
+    p->direction = DFFT_FORWARD;
+    p->P = total_devices;
+    p->me = global_idx;
+    p->flags = flags;
+    p->is_last = global_idx == total_devices - 1;
+    p->inplace = out == nullptr || out == in;
+    p->sx = sx;
+    p->sy = sy;
+    p->xs = sx.size(global_idx);
+    p->ys = sy.size(global_idx);
+    p->max_count = p->xs * n1 * pitch1;
+    p->in = in;
+    p->out = p->inplace ? in : out;
+    p->buf1 = p->buf2 = nullptr;
+    p->comm = comm;
+    p->device = 0;
+    p->stream = nullptr;
+    for (auto& e : p->ev) e = nullptr;
+    for (double& t : p->host_t) t = 0;
+    p->host_timed = false;
+    p->chunk_planes = 0;
+    p->grid_x = env_grid("DFFT_X_GRID");
+    auto bail = [&](int rc) {
+        const std::string msg = g_last_error;
+        (void)conv_destroy(p);
+        return fail(rc, msg);
+    };
+    const size_t cs = elem_bytes(dtype);
+    if (total_devices > 1) {  // the forward half packs [d][xs][yl_d][Nc] into a send buffer of the plan's own
+        const hipError_t e = hipMalloc(&c->sbuf, (size_t)total_devices * p->xs * sy.blk * nc * cs);
+        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": send buffer: " + hipGetErrorString(e)));
+    }
+    R2cHalf hf{nc, nullptr};
+    int     rc = create_r2c(&c->f, n0, n1, n2, dtype, DFFT_FORWARD, in, c->sbuf, comm, global_idx, total_devices, DFFT_PLAN_INPUT_FROM_IN, false, &hf);
+    if (rc) return bail(rc);
+    R2cHalf hb{nc, c->f};
+    rc = create_r2c(&c->b, n0, n1, n2, dtype, DFFT_BACKWARD, in, p->out, comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, false, &hb);
+    if (rc) return bail(rc);
+    dfft_plan_s *f = c->f, *b = c->b;
+    p->stream = f->stream;
+    p->device = f->device;
+    p->exch = f->exch;
+    ConvLaunch& L = c->L;
+    L.dtype = dtype;
+    L.n0 = (int)n0;
+    L.ncols = nc;
+    L.scale = 1.0;
+    L.rot = 0;
+    if (p->exch) {
+        // as in dfft_plan_create_conv: the forward exchange's receive layout [x][yl][Nc] IS the backward exchange's send layout, so the X
+        // stage works in place on the forward half's receive buffer and the backward half sends from it
+        for (int q = 0; q < p->P; ++q)
+            if (f->xd.roffset[q] != b->xd.soffset[q] || f->xd.rcount[q] != b->xd.scount[q])
+                return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
+        b->xd.sendbuf = f->buf1;
+        L.in = L.out = f->buf1;
+        L.plane = p->ys * nc;
+        L.pitch = nc;
+        L.rows = p->ys;
+        c->slab_elems = n0 * p->ys * nc;
+    } else {  // the intermediate [N0][N1][pitch], rows padded to whole lines
+        L.in = L.out = f->cbuf;
+        L.plane = f->cl.plane;
+        L.pitch = f->cl.pitch;
+        L.rows = n1;
+        c->slab_elems = p->xs * f->cl.plane;
+    }
+    c->fused = want_fused && conv_fused_applies(L);
+    *plan = p;
+    return DFFT_OK;
+}
+
 static int conv_check_handle(dfft_plan_t plan, const char* fn) {
     if (!plan || !plan->conv) return fail(DFFT_EINVAL, std::string(fn) + ": not a spectral-filter plan");
     return DFFT_OK;
@@ -2139,7 +2290,8 @@ int dfft_conv_set_filter(dfft_plan_t plan, const void* h, int kind) {
     ConvLaunch R = c->L;
     R.filter_real = kind == DFFT_FILTER_REAL;
     R.scale = plan->scale / ((double)plan->N[0] * (double)plan->N[1] * (double)plan->N[2]);
-    DFFT_TRY(check_launch(launch_conv_relayout(R, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
+    if (c->real) DFFT_TRY(check_launch(launch_conv_real_relayout(R, c->nh, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
+    else DFFT_TRY(check_launch(launch_conv_relayout(R, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
     DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
     c->kind = kind;
     return DFFT_OK;
@@ -2168,9 +2320,11 @@ int dfft_conv_set_kernel(dfft_plan_t plan, const void* k) {
 
 }  // extern "C"
 
-// dfft_plan_create_r2c (any = false) and dfft_plan_create_r2c_any (any = true: the real axis of any dfft_real_form != 0)
+// dfft_plan_create_r2c (any = false) and dfft_plan_create_r2c_any (any = true: the real axis of any dfft_real_form != 0); half != nullptr:
+// a half plan of dfft_plan_create_conv_real, which has checked the arguments (`in` / `out`: the real slabs the R2C half reads / the C2R
+// half writes; the forward half's `out` is the plan's send buffer, NULL without an exchange)
 static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any) {
+                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any, const R2cHalf* half) {
     const std::string fn = any ? "dfft_plan_create_r2c_any" : "dfft_plan_create_r2c";
     if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
     if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
@@ -2179,7 +2333,7 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
     if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
     if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
-    if (out == nullptr || out == in) return fail(DFFT_EINVAL, fn + ": real-to-complex plans are out of place (out != NULL, out != in)");
+    if (!half && (out == nullptr || out == in)) return fail(DFFT_EINVAL, fn + ": real-to-complex plans are out of place (out != NULL, out != in)");
     if (flags & ~DFFT_PLAN_INPUT_FROM_IN)
         return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT and DFFT_PLAN_INPUT_FROM_IN are supported "
                                        "(no OVERLAP, NATURAL or UNFUSED real-to-complex plans)");
@@ -2201,10 +2355,12 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     if (std::max(cc0, cc_last) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, fn + ": more than 2^31 complex elements per device");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
 
-    const long long nh = n2 / 2 + 1;
+    const long long nh = half ? half->nc : n2 / 2 + 1;  // the complex width: what the Y pass, the exchange and the X stage see
     trace("dfft_plan_create_r2c", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
     dfft_plan_s* p = new dfft_plan_s;
     p->r2c = true;
+    p->conv_half = half != nullptr;
+    p->borrowed = half && half->share;
     p->n2r = n2;
     p->real_any = any;
     p->real_form = form;
@@ -2255,18 +2411,27 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     }
     // bufferDev1: the real slab (R2C) or the complex input (C2R), and the receive buffer of the exchange -- the same size on every rank
     // (pooled receive buffers of IPC communicators are matched by key and size)
-    const size_t b1 = (size_t)std::max({rc0 * rs, cc0 * cs, rc_last * rs, cc_last * cs});
-    const std::string rkey = "r2c:" + std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" + std::to_string(dtype) + ":" +
-                             std::to_string(total_devices);
-    if (e == hipSuccess && comm_recv_alloc(comm, rkey + ":b1", b1, &p->buf1) != DFFT_OK) e = hipErrorOutOfMemory;
+    // (half plans: a receive buffer alone, and only with a communicator)
+    const size_t b1 = half ? (size_t)conv_real_recv_count(n0, n1, nh, total_devices) * cs : (size_t)std::max({rc0 * rs, cc0 * cs, rc_last * rs, cc_last * cs});
+    const std::string rkey = std::string(half ? "convr:" : "r2c:") + std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" +
+                             std::to_string(dtype) + ":" + std::to_string(total_devices);
+    if (e == hipSuccess && (!half || comm) && comm_recv_alloc(comm, rkey + ":b1", b1, &p->buf1) != DFFT_OK) e = hipErrorOutOfMemory;
     // the intermediate, also the send buffer of the backward exchange ([N0][ys][nh])
-    const size_t cbytes = (size_t)std::max(p->xs * p->cl.plane, n0 * p->ys * nh) * cs;
-    if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    const size_t cbytes = (size_t)(half ? p->xs * p->cl.plane : std::max(p->xs * p->cl.plane, n0 * p->ys * nh)) * cs;
+    if (p->borrowed) {
+        p->cbuf = half->share->cbuf;
+        p->stream = half->share->stream;
+    } else {
+        if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    }
     // input captured at plan time, on the plan's stream (see dfft_plan_create); exactly the caller's elements, nothing beyond them
     const size_t ibytes = direction == DFFT_FORWARD ? (size_t)rc_n * rs : (size_t)(p->ys * nh * n0) * cs;
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyAsync(p->buf1, in, ibytes, hipMemcpyDeviceToDevice, p->stream);
+    if (e == hipSuccess && !half) e = hipMemcpyAsync(p->buf1, in, ibytes, hipMemcpyDeviceToDevice, p->stream);
+    // (half plans capture nothing.  Their intermediate is cleared ONCE: its columns n2/2 + 1 .. nc - 1 and its row padding are never
+    // written with anything but zeros afterwards -- the argument is at the top of dfft_conv_real.hip)
+    if (e == hipSuccess && half && !p->borrowed) e = hipMemsetAsync(p->cbuf, 0, cbytes, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     for (auto& ev : p->ev)
         if (e == hipSuccess) e = hipEventCreate(&ev);
@@ -2774,7 +2939,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     if (plan->lbuf) hipFree(plan->lbuf);
     if (plan->bs.scratch) hipFree(plan->bs.scratch);
     if (plan->rscratch) hipFree(plan->rscratch);
-    if (plan->cbuf) hipFree(plan->cbuf);
+    if (plan->cbuf && !plan->borrowed) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
     if (plan->zy_err) hipHostFree(plan->zy_err);

@@ -221,6 +221,36 @@ int dfft_conv_set_filter(dfft_plan_t plan, const void* h, int kind);
  * forward half on it (collective over the communicator like an execute) and keeps a complex filter copy.  Synchronises. */
 int dfft_conv_set_kernel(dfft_plan_t plan, const void* k);
 
+/* ---- real-field spectral-filter plans ----------------------------------------------------------------------------------------------
+ * y = irfftn( rfftn(x) * H, s = (N0, N1, N2) ), numpy conventions (H == 1 gives y == x), for REAL fields: half the field's memory and half
+ * the bytes of every pass and of both exchanges of dfft_plan_create_conv on the widened field, and no widening / narrowing pass.
+ * in / out: device buffers of the plan's REAL type (double / float) in the X-slab layout [x_local][N1][N2], dfft_local_count reals;
+ * out == in or NULL: in place.  `in` is read at every execute (nothing is captured at plan time) and left alone when out != in.
+ * The result is numpy's for ANY complex H: the inverse runs C2C along X and Y, then C2R along Z, which ignores the imaginary parts of the
+ * kz = 0 and kz = N2/2 bins (the backward order of dfft_plan_create_r2c).
+ * Pipeline: R2C rows + Y columns per cache chunk -> (P > 1: pack, exchange) -> the X stage of dfft_plan_create_conv in place on the half
+ * spectrum -> (exchange, unpack) -> inverse Y columns + C2R rows per cache chunk.  The half spectrum is private to the plan and
+ * Nc >= Nh = N2/2 + 1 bins wide, its extra columns zero (Nc even, and a multiple of up to one 128-byte line where that pads at most
+ * Nh/32 columns: Nh = 257 -> 264); dfft_plan_describe reports it as width=<Nc>.  Execute allocates nothing.
+ * Accepted: N0, N1 of dfft_length_kind 1; N2 of dfft_real_form 1 (even, N2/2 a single-pass length); P >= 1 on any communicator; flags
+ * DFFT_PLAN_DEFAULT only.  Every other flag, N0 / N1 of kind 0, 2 or 3 and N2 of real form 0, 2 or 3 (odd, N2 = 2, N2/2 beyond the
+ * single-pass range: REFUSED, unlike dfft_plan_create_r2c_any): DFFT_EUNSUPPORTED; NULL plan / in, sizes < 1, a bad dtype or device
+ * index: DFFT_EINVAL -- all checked before the device is queried (then DFFT_ENOGPU without one).
+ * The handle is an ordinary plan with the semantics of dfft_plan_create_conv's: dfft_execute (ASYNC / SYNC_STAGES / NO_TIMING;
+ * DFFT_EINVAL before a filter is set), dfft_plan_sync, dfft_plan_stream, dfft_stage_times (the same four stages), dfft_plan_set_scale
+ * (takes effect at the next dfft_conv_set_filter / dfft_conv_set_kernel), dfft_plan_describe ("pipeline=conv-real xconv=fused|multi
+ * filter=complex|real|unset width=<Nc> ...") and dfft_plan_destroy; dfft_plan_tune is a no-op, dfft_kernel_times returns
+ * DFFT_EUNSUPPORTED, dfft_plan_buffer1 / dfft_plan_result / dfft_plan_workbuf NULL.
+ * dfft_conv_set_filter(plan, h, kind) takes h in the layout a forward dfft_plan_create_r2c plan of the same shape / communicator returns
+ * on this device: element (yy*Nh + kz)*N0 + kx = H[kx, y0 + yy, kz], dfft_conv_real_filter_count elements -- of the plan's complex type,
+ * or of its real type with DFFT_FILTER_REAL.  The private copy has 1/(N0*N1*N2) and the plan's scale folded in.
+ * dfft_conv_set_kernel(plan, k) takes a REAL kernel k in the plan's input layout (the real type) and keeps rfftn(k) as a complex filter;
+ * collective like an execute. */
+int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out,
+                               dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* Elements of this device's share of a real-field plan's filter: local_n1 * (N2/2 + 1) * N0 (host-only arithmetic); -1 for bad arguments. */
+long long dfft_conv_real_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx);
+
 /* Elements the caller's buffers of an r2c plan must hold on device global_idx: *real_count reals on the real side (R2C input / C2R
  * output), *complex_count complex elements on the complex side (R2C output / C2R input) -- the result [y_local][Nh][N0] and, for P > 1,
  * the packed send layout of the forward exchange, which the R2C plan writes into `out` before its result.  Pure host arithmetic. */
