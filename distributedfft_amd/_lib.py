@@ -21,6 +21,7 @@ F64, F32 = 0, 1
 PLAN_DEFAULT, PLAN_UNFUSED, PLAN_INPUT_FROM_IN, PLAN_OVERLAP, PLAN_NATURAL, PLAN_ANY_LENGTH = 0, 1, 2, 4, 8, 16
 EXEC_ASYNC, EXEC_SYNC_STAGES, EXEC_PRINT, EXEC_NO_TIMING = 0, 1, 2, 4
 FILTER_COMPLEX, FILTER_REAL = 0, 1
+CONV_MAX_OUTPUTS = 8
 OK, EINVAL, EHIP, ERCCL, ENOGPU, ECOMM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
 _LL = C.c_longlong
@@ -60,6 +61,9 @@ SIGNATURES = {
     "dfft_conv_filter_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
     "dfft_plan_create_conv_real": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_conv_real_filter_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
+    "dfft_plan_create_conv_real_multi": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, C.POINTER(_VP), C.c_int, _VP, C.c_int, C.c_int,
+                                                   C.c_uint]),
+    "dfft_conv_set_factors": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     "dfft_conv_set_filter": (C.c_int, [_VP, _VP, C.c_int]),
     "dfft_conv_set_kernel": (C.c_int, [_VP, _VP]),
     "dfft_plan_buffer1": (_VP, [_VP]),

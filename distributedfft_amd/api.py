@@ -479,6 +479,63 @@ class PlanConvReal(PlanConv):
             L.check(L.load().dfft_conv_set_kernel(self.handle, k.data_ptr()), "dfft_conv_set_kernel")
 
 
+class PlanConvRealMulti(PlanConvReal):
+    """Multi-output real-field spectral-filter plan (dfft_plan_create_conv_real_multi): K real outputs of one real input,
+    outs[k] = irfftn(rfftn(inp) * H * a_k[:, None, None] * b_k[None, :, None] * c_k[None, None, :], s=(N0, N1, N2)), with one base filter H
+    (set_filter / set_kernel as for PlanConvReal) and per-output factors (set_factors; ones until set).  inp and every out: float64 /
+    float32 X slabs [x_local][N1][N2]; one of outs may be inp.  The input is transformed once and the filter kept once; describe() reports
+    pipeline=conv-real-multi outputs=<K>.  Everything else is PlanConvReal's."""
+
+    def __init__(self, n0, n1, n2, inp, outs, comm: Optional[Comm], global_idx: int, total_devices: int, flags: int = PLAN_DEFAULT):
+        import torch
+        lib = L.load()
+        outs = list(outs)
+        if not inp.is_cuda:
+            raise DfftError(L.ENOGPU, "PlanConvRealMulti", "buffers must live on a HIP device (no CPU fallback)")
+        name = str(inp.dtype).replace("torch.", "")
+        if name not in _R2C_PAIRS:
+            raise TypeError(f"PlanConvRealMulti: buffers must be torch.float64 or torch.float32 device tensors, got {name}")
+        if not 1 <= len(outs) <= L.CONV_MAX_OUTPUTS:
+            raise ValueError(f"PlanConvRealMulti: 1 .. {L.CONV_MAX_OUTPUTS} outputs, got {len(outs)}")
+        self.N = (int(n0), int(n1), int(n2))
+        self.dtype = F64 if name == "float64" else F32
+        self.direction = FORWARD
+        self.total_devices, self.global_idx = total_devices, global_idx
+        self.noutputs = len(outs)
+        self.max_count = get_data_count(self.N, total_devices, global_idx)
+        self.filter_count = conv_real_filter_count(n0, n1, n2, total_devices, global_idx)
+        for o in outs:
+            if o.dtype != inp.dtype:
+                raise TypeError("PlanConvRealMulti: inp and every out must have the same dtype")
+            if o.device != inp.device:
+                raise ValueError(f"PlanConvRealMulti: inp is on {inp.device}, an out on {o.device}")
+        if inp.numel() < self.max_count or any(o.numel() < self.max_count for o in outs):
+            raise ValueError(f"in/outs must hold getDataCount = {self.max_count} elements")
+        self._in, self._out, self._outs, self._comm = inp, outs[0], outs, comm  # keep alive
+        self.handle = C.c_void_p()
+        ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        torch.cuda.synchronize(inp.device)
+        with torch.cuda.device(inp.device):
+            L.check(lib.dfft_plan_create_conv_real_multi(C.byref(self.handle), n0, n1, n2, self.dtype, inp.data_ptr(), ptrs, len(outs),
+                                                         comm.handle if comm is not None else None, global_idx, total_devices, flags),
+                    "dfft_plan_create_conv_real_multi")
+        self.device = inp.device
+
+    def set_factors(self, k: int, ax=None, ay=None, az=None) -> None:
+        """The separable factors of output k: device tensors of the plan's complex dtype with N0, N1 (the whole global vector) and N2/2 + 1
+        elements; None: ones.  The plan keeps private copies; the other outputs are left alone."""
+        import torch
+        if not 0 <= int(k) < self.noutputs:
+            raise ValueError(f"PlanConvRealMulti.set_factors: output {k} of {self.noutputs}")
+        cplx = "complex128" if self.dtype == F64 else "complex64"
+        for t, count in ((ax, self.N[0]), (ay, self.N[1]), (az, self.N[2] // 2 + 1)):
+            if t is not None:
+                self._check_operand(t, "set_factors", count, (cplx,))
+        with torch.cuda.device(self.device):
+            L.check(L.load().dfft_conv_set_factors(self.handle, int(k), *[t.data_ptr() if t is not None else None for t in (ax, ay, az)]),
+                    "dfft_conv_set_factors")
+
+
 def fft_mpi_plan_dft_c2c_3d(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags=PLAN_DEFAULT) -> Plan:
     return Plan(n0, n1, n2, inp, out, comm, global_idx, total_devices, direction, flags)
 

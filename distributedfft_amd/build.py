@@ -103,6 +103,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
         units.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # real-field spectral-filter plans: the filter re-layout into the plan's private half spectrum
     units.append((CSRC / "dfft_conv_real.hip", OBJ / "dfft_conv_real.o", []))
+    # multi-output real-field spectral-filter plans: the K-output fused kernels of each group, plus the dispatcher and the factor multiply
+    for g in range(NUM_INST_GROUPS + 1):
+        units.append((CSRC / "dfft_conv_multi.hip", OBJ / f"dfft_conv_multi_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
     units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
     units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))

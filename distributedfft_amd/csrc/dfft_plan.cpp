@@ -30,6 +30,7 @@
 #include "dfft_bluestein.h"
 #include "dfft_conv.h"
 #include "dfft_conv_real.h"
+#include "dfft_conv_multi.h"
 #include "dfft_internal.h"
 #include "dfft_long.h"
 #include "dfft_real.h"
@@ -347,6 +348,7 @@ struct dfft_plan_s {
     // covers the stream and the complex intermediate cbuf.
     struct ConvState*       conv = nullptr;
     bool                    conv_half = false, conv_no_rot = false, borrowed = false;
+    bool                    own_cbuf = false;  // a borrowed half of a multi-output plan that owns its intermediate all the same
     std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
     int                     w_kept = -1;
     float                   w_final_ms = 0.f;  // the kept candidate re-timed after the others were freed
@@ -365,6 +367,19 @@ struct ConvState {
     double       x_host = 0;                 // host-timed X stage of the last DFFT_EXEC_SYNC_STAGES execute
     bool         real = false;               // dfft_plan_create_conv_real: R2C / C2R halves, the slab is the half spectrum at width L.ncols
     long long    nh = 0;                     // real-field plans: N2/2 + 1, the bins per row the caller's filter has
+    // multi-output real-field plans (dfft_plan_create_conv_real_multi): nout > 0 outputs, one C2R half per output (bk[0] == b), the slabs
+    // the X stage writes (M.out[0] == L.in; M.out[k >= 1]: the intermediate of bk[k] at P = 1, a send buffer of the plan's own -- xslab[k] --
+    // at P > 1) and the factor tables: `fact` holds a table of ones and, per output, na + nrow + L.ncols elements (a, this device's part
+    // of b, zero-padded c); M.ax / by / cz point at the ones until dfft_conv_set_factors gives something else
+    int           nout = 0;
+    dfft_plan_s*  bk[CONV_MAX_OUTPUTS] = {};
+    void*         xslab[CONV_MAX_OUTPUTS] = {};
+    void*         fact = nullptr;
+    long long     fa = 0, fb = 0;            // elements reserved for a and b per output (even: every table starts on a 16-byte boundary)
+    ConvMultiArgs M{};
+    bool          unit[CONV_MAX_OUTPUTS] = {};  // all three factors of output k are ones
+    int           backs() const { return nout > 0 ? nout : 1; }
+    dfft_plan_s*  back(int k) const { return nout > 0 ? bk[k] : b; }
 };
 static int conv_execute(dfft_plan_s* p, unsigned exec_flags);
 static int conv_describe(const dfft_plan_s* p, char* buf, int len);
@@ -373,9 +388,14 @@ static int conv_stage_times(dfft_plan_s* p, double t[4]);
 static int conv_destroy(dfft_plan_s* p);
 // A half plan of dfft_plan_create_conv_real: the plan's complex width, and the forward half whose stream and intermediate the backward
 // half borrows (nullptr: this IS the forward half)
+// Multi-output plans: C2R half `output` >= 1 borrows the stream but has a receive buffer of its own (the output index goes into the pool
+// key: peers push into it while this rank may still unpack the previous output's) and, with own_cbuf, an intermediate of its own -- slab
+// `output` of the X stage at P = 1
 struct R2cHalf {
     long long    nc;
     dfft_plan_s* share;
+    int          output = 0;
+    bool         own_cbuf = false;
 };
 // Elements of the two receive buffers of a real-field spectral-filter plan at complex width nc -- the forward one holds [N0][ys][nc], the
 // backward one the packed [q][xs][yl_q][nc] -- as a bound that is the same on every rank (pooled buffers are matched by size)
@@ -1900,6 +1920,40 @@ static int conv_x_stage(dfft_plan_s* p, bool to_filter, double scale) {
     DFFT_TRY(get_twiddles(L.n0, p->dtype, &L.tw));
     L.filt = c->filt;
     L.filter_real = (!to_filter && c->kind == DFFT_FILTER_REAL) ? 1 : 0;
+    if (c->nout > 0 && !to_filter) {
+        if (c->fused) return check_launch(launch_conv_multi_fused(L, c->M, c->nout, p->stream), "X stage of the multi-output spectral-filter plan");
+        // multi route: forward columns and the multiply by the filter copy in place, ONCE; per output the factors out of place into slab k
+        // and the inverse columns there; output 0 last, in place over the product
+        FftLaunch X;
+        std::memset(&X, 0, sizeof(X));
+        X.dtype = p->dtype;
+        X.n = L.n0;
+        X.dir = DFFT_FORWARD;
+        X.cols = 1;
+        X.in = L.in;
+        X.out = const_cast<void*>(L.in);
+        X.tw = L.tw;
+        X.imap = X.omap = plain_axis(L.n0, L.plane, 1);
+        X.itile = X.otile = TileMap{L.pitch, 1};
+        X.na = L.rows;
+        X.ncols = (int)L.ncols;
+        X.scale = 1.0;
+        X.grid_limit = p->grid_x;
+        DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the multi-output spectral-filter plan (forward columns)"));
+        DFFT_TRY(check_launch(launch_conv_mul(p->dtype, L.filter_real, const_cast<void*>(L.in), c->filt, c->slab_elems, p->stream),
+                              "X stage of the multi-output spectral-filter plan (multiply)"));
+        X.dir = DFFT_BACKWARD;
+        for (int i = 0; i < c->nout; ++i) {
+            const int k = i + 1 < c->nout ? i + 1 : 0;
+            void*     slab = c->M.out[k];
+            if (k > 0 || !c->unit[k])
+                DFFT_TRY(check_launch(launch_conv_factor_mul(L, L.in, slab, c->M.ax[k], c->M.by[k], c->M.cz[k], p->stream),
+                                      "X stage of the multi-output spectral-filter plan (factors)"));
+            X.in = X.out = slab;
+            DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the multi-output spectral-filter plan (inverse columns)"));
+        }
+        return DFFT_OK;
+    }
     if (c->fused) {
         if (to_filter) {
             L.forward_only = 1;
@@ -1957,9 +2011,16 @@ static int conv_execute(dfft_plan_s* p, unsigned exec_flags) {
         msg = g_last_error;
     }
     if (rc && !p->exch) return rc;
-    const int rb = dfft_execute(c->b, half_flags);
+    for (int k = 0; k < c->backs(); ++k) {  // one after another on the one stream
+        const int rb = dfft_execute(c->back(k), half_flags);
+        if (rb && !rc) {
+            rc = rb;
+            msg = g_last_error;
+            if (!p->exch) return rc;
+        }
+    }
     if (rc) return fail(rc, msg);
-    return rb;
+    return DFFT_OK;
 }
 
 static int conv_describe(const dfft_plan_s* p, char* buf, int len) {
@@ -1969,6 +2030,12 @@ static int conv_describe(const dfft_plan_s* p, char* buf, int len) {
     const char* yz = strstr(half, "yz_stage=");
     char        yzs[64] = "yz_stage=?";
     if (yz) sscanf(yz, "%63s", yzs);
+    if (c->real && c->nout > 0) {
+        snprintf(buf, (size_t)len, "pipeline=conv-real-multi outputs=%d xconv=%s filter=%s width=%lld bins=%lld pitch=%lld handover=%s chunk_planes=%lld",
+                 c->nout, c->fused ? "fused" : "multi", c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"),
+                 c->L.ncols, c->nh, c->L.pitch, p->exch ? "receive-buffer" : "intermediate", c->f->chunk_planes);
+        return DFFT_OK;
+    }
     if (c->real) {
         snprintf(buf, (size_t)len, "pipeline=conv-real xconv=%s filter=%s width=%lld bins=%lld pitch=%lld handover=%s chunk_planes=%lld",
                  c->fused ? "fused" : "multi", c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"),
@@ -1985,7 +2052,7 @@ static int conv_sync(dfft_plan_s* p) {
     ConvState* c = p->conv;
     DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
     DFFT_TRY(zy_check(c->f));
-    DFFT_TRY(zy_check(c->b));
+    for (int k = 0; k < c->backs(); ++k) DFFT_TRY(zy_check(c->back(k)));
     if (p->comm) return comm_check(p->comm);
     return DFFT_OK;
 }
@@ -1995,12 +2062,18 @@ static int conv_stage_times(dfft_plan_s* p, double t[4]) {
     ConvState* c = p->conv;
     DFFT_TRY(conv_sync(p));
     if (!p->timed) return fail(DFFT_EINVAL, "dfft_stage_times: the last execute ran with DFFT_EXEC_NO_TIMING");
-    const dfft_plan_s *f = c->f, *b = c->b;
+    const dfft_plan_s *f = c->f, *b = c->back(0);
     if (p->host_timed) {
         t[0] = f->host_t[0] + f->host_t[1];
-        t[1] = f->host_t[2] + b->host_t[1];
-        t[2] = f->host_t[3] + c->x_host + b->host_t[0];
-        t[3] = b->host_t[2] + b->host_t[3];
+        t[1] = f->host_t[2];
+        t[2] = f->host_t[3] + c->x_host;
+        t[3] = 0;
+        for (int k = 0; k < c->backs(); ++k) {  // (multi-output plans: all 1 + K exchanges, the sum of the K inverse stages)
+            const dfft_plan_s* bk = c->back(k);
+            t[1] += bk->host_t[1];
+            t[2] += bk->host_t[0];
+            t[3] += bk->host_t[2] + bk->host_t[3];
+        }
         return DFFT_OK;
     }
     auto ms = [](hipEvent_t a, hipEvent_t z, double* out) {
@@ -2016,6 +2089,13 @@ static int conv_stage_times(dfft_plan_s* p, double t[4]) {
     t[1] = x1 + x2;
     DFFT_TRY(ms(f->ev[3], b->ev[1], &t[2]));
     DFFT_TRY(ms(b->ev[2], b->ev[4], &t[3]));
+    for (int k = 1; k < c->backs(); ++k) {
+        const dfft_plan_s* bk = c->back(k);
+        DFFT_TRY(ms(bk->ev[1], bk->ev[2], &x1));
+        DFFT_TRY(ms(bk->ev[2], bk->ev[4], &x2));
+        t[1] += x1;
+        t[3] += x2;
+    }
     return DFFT_OK;
 }
 
@@ -2023,6 +2103,14 @@ static int conv_destroy(dfft_plan_s* p) {
     ConvState* c = p->conv;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     int rc = DFFT_OK;
+    for (int k = CONV_MAX_OUTPUTS - 1; k >= 1; --k) {  // multi-output plans: the halves of outputs K-1 .. 1, their slabs, the factor tables
+        if (c->bk[k]) {
+            const int r = dfft_plan_destroy(c->bk[k]);
+            if (!rc) rc = r;
+        }
+        if (c->xslab[k]) (void)hipFree(c->xslab[k]);
+    }
+    if (c->fact) (void)hipFree(c->fact);
     if (c->b) {  // (the stream and the hand-over buffer are the forward half's)
         const int r = dfft_plan_destroy(c->b);
         if (!rc) rc = r;
@@ -2167,10 +2255,21 @@ long long dfft_conv_real_filter_count(long long n0, long long n1, long long n2, 
     return make_slab(n1, total_devices).size(global_idx) * (n2 / 2 + 1) * n0;
 }
 
-int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
-                               int global_idx, int total_devices, unsigned flags) {
-    const std::string fn = "dfft_plan_create_conv_real";
+// dfft_plan_create_conv_real (nout == 0: one output `out`, NULL or `in` for in place) and dfft_plan_create_conv_real_multi (nout >= 1
+// outputs outs[0 .. nout))
+static int conv_real_create(const std::string& fn, dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out,
+                            void* const* outs, int nout, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
     if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
+    if (outs || nout) {
+        if (!outs || nout < 1 || nout > DFFT_CONV_MAX_OUTPUTS)
+            return fail(DFFT_EINVAL, fn + ": noutputs must be 1 .. " + std::to_string(DFFT_CONV_MAX_OUTPUTS) + " and outs not NULL");
+        for (int k = 0; k < nout; ++k) {
+            if (!outs[k]) return fail(DFFT_EINVAL, fn + ": outs[" + std::to_string(k) + "] is NULL");
+            for (int q = 0; q < k; ++q)
+                if (outs[q] == outs[k]) return fail(DFFT_EINVAL, fn + ": outs[" + std::to_string(q) + "] and outs[" + std::to_string(k) + "] are the same buffer");
+        }
+        out = outs[0];
+    }
     if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
     if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
     if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
@@ -2194,12 +2293,13 @@ int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, lo
 
     const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
     const bool  want_fused = !(fe && *fe == '0') && conv_fused_length((int)n0);
-    trace("dfft_plan_create_conv_real", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices);
+    trace("dfft_plan_create_conv_real", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices * 100 + nout);
     dfft_plan_s* p = new dfft_plan_s;
     ConvState*   c = new ConvState;
     p->conv = c;
     c->real = true;
     c->nh = nh;
+    c->nout = nout;
     p->N[0] = n0;
     p->N[1] = n1;
     p->N[2] = n2;  // the REAL length (1 / (N0 N1 N2) in the filter copy); the halves carry the complex width
@@ -2242,6 +2342,20 @@ int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, lo
     R2cHalf hb{nc, c->f};
     rc = create_r2c(&c->b, n0, n1, n2, dtype, DFFT_BACKWARD, in, p->out, comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, false, &hb);
     if (rc) return bail(rc);
+    c->bk[0] = c->b;
+    // outputs 1 .. K-1: a C2R half each, on the same stream.  P = 1: its intermediate (cleared once, like the forward half's) is slab k of
+    // the X stage.  P > 1: it unpacks into the shared intermediate out of a receive buffer of its own and sends from slab k, a buffer of
+    // the plan's in the received slab's layout [N0][y_local][Nc].
+    for (int k = 1; k < nout; ++k) {
+        R2cHalf hk{nc, c->f, k, total_devices == 1};
+        rc = create_r2c(&c->bk[k], n0, n1, n2, dtype, DFFT_BACKWARD, in, outs[k], comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, false, &hk);
+        if (rc) return bail(rc);
+        if (total_devices > 1) {
+            const size_t     bytes = (size_t)(n0 * p->ys * nc) * cs;
+            const hipError_t e = hipMalloc(&c->xslab[k], bytes);
+            if (e != hipSuccess || hipMemset(c->xslab[k], 0, bytes) != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": slab of output " + std::to_string(k)));
+        }
+    }
     dfft_plan_s *f = c->f, *b = c->b;
     p->stream = f->stream;
     p->device = f->device;
@@ -2272,7 +2386,83 @@ int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, lo
         c->slab_elems = p->xs * f->cl.plane;
     }
     c->fused = want_fused && conv_fused_applies(L);
+    if (nout > 0) {
+        c->M.out[0] = const_cast<void*>(L.in);
+        for (int k = 1; k < nout; ++k) {
+            dfft_plan_s* bk = c->bk[k];
+            if (p->exch) {
+                for (int q = 0; q < p->P; ++q)
+                    if (f->xd.roffset[q] != bk->xd.soffset[q] || f->xd.rcount[q] != bk->xd.scount[q])
+                        return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
+                bk->xd.sendbuf = c->xslab[k];
+                c->M.out[k] = c->xslab[k];
+            } else {
+                if (bk->cl.plane != f->cl.plane || bk->cl.pitch != f->cl.pitch) return bail(fail(DFFT_EINVAL, fn + ": internal: the slabs' layouts differ"));
+                c->M.out[k] = bk->cbuf;
+            }
+        }
+        // the factor tables: ones (as long as the longest factor), then per output a | b (this device's rows) | c (Nc wide)
+        c->fa = (n0 + 1) / 2 * 2;
+        c->fb = (L.rows + 1) / 2 * 2;
+        const long long ones = std::max({c->fa, c->fb, L.ncols}), total = ones + nout * (c->fa + c->fb + L.ncols);
+        hipError_t      e = hipMalloc(&c->fact, (size_t)total * cs);
+        if (e == hipSuccess) e = hipMemset(c->fact, 0, (size_t)total * cs);
+        std::vector<char> host((size_t)ones * cs, 0);
+        for (long long i = 0; i < ones; ++i) {
+            if (dtype == DFFT_F64) reinterpret_cast<double*>(host.data())[2 * i] = 1.0;
+            else reinterpret_cast<float*>(host.data())[2 * i] = 1.f;
+        }
+        if (e == hipSuccess) e = hipMemcpy(c->fact, host.data(), host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": factor tables: " + hipGetErrorString(e)));
+        for (int k = 0; k < nout; ++k) {
+            c->M.ax[k] = c->M.by[k] = c->M.cz[k] = c->fact;
+            c->unit[k] = true;
+        }
+    }
     *plan = p;
+    return DFFT_OK;
+}
+
+int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
+                               int global_idx, int total_devices, unsigned flags) {
+    return conv_real_create("dfft_plan_create_conv_real", plan, n0, n1, n2, dtype, in, out, nullptr, 0, comm, global_idx, total_devices, flags);
+}
+
+int dfft_plan_create_conv_real_multi(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* const* outs,
+                                     int noutputs, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    if (!outs) return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: outs is NULL");
+    if (noutputs < 1 || noutputs > DFFT_CONV_MAX_OUTPUTS)
+        return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: noutputs must be 1 .. " + std::to_string(DFFT_CONV_MAX_OUTPUTS));
+    if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: null plan/in");
+    return conv_real_create("dfft_plan_create_conv_real_multi", plan, n0, n1, n2, dtype, in, nullptr, outs, noutputs, comm, global_idx,
+                            total_devices, flags);
+}
+
+// The separable factors of output k (device pointers to the plan's complex type; NULL: ones): ax[N0], ay[N1] -- the whole vector, the
+// plan takes rows y0 .. y0 + y_local --, az[N2/2 + 1].  Private copies; az zero-padded to the plan's width.
+int dfft_conv_set_factors(dfft_plan_t plan, int k, const void* ax, const void* ay, const void* az) {
+    if (!plan || !plan->conv || plan->conv->nout < 1) return fail(DFFT_EINVAL, "dfft_conv_set_factors: not a multi-output spectral-filter plan");
+    ConvState* c = plan->conv;
+    if (k < 0 || k >= c->nout) return fail(DFFT_EINVAL, "dfft_conv_set_factors: output " + std::to_string(k) + " of " + std::to_string(c->nout));
+    DFFT_HIP_TRY(hipDeviceSynchronize());  // whatever stream produced the vectors, and this plan's executes that read the old tables
+    const size_t    cs = elem_bytes(plan->dtype);
+    const long long ones = std::max({c->fa, c->fb, c->L.ncols}), per = c->fa + c->fb + c->L.ncols;
+    char* const     ta = (char*)c->fact + (size_t)(ones + k * per) * cs;
+    char* const     tb = ta + (size_t)c->fa * cs;
+    char* const     tc = tb + (size_t)c->fb * cs;
+    if (ax) DFFT_HIP_TRY(hipMemcpyAsync(ta, ax, (size_t)plan->N[0] * cs, hipMemcpyDeviceToDevice, plan->stream));
+    if (ay)
+        DFFT_HIP_TRY(hipMemcpyAsync(tb, (const char*)ay + (size_t)plan->sy.start(plan->me) * cs, (size_t)plan->ys * cs, hipMemcpyDeviceToDevice,
+                                    plan->stream));
+    if (az) {
+        DFFT_HIP_TRY(hipMemsetAsync(tc, 0, (size_t)c->L.ncols * cs, plan->stream));
+        DFFT_HIP_TRY(hipMemcpyAsync(tc, az, (size_t)c->nh * cs, hipMemcpyDeviceToDevice, plan->stream));
+    }
+    DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
+    c->M.ax[k] = ax ? ta : c->fact;
+    c->M.by[k] = ay ? tb : c->fact;
+    c->M.cz[k] = az ? tc : c->fact;
+    c->unit[k] = !ax && !ay && !az;
     return DFFT_OK;
 }
 
@@ -2361,6 +2551,7 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     p->r2c = true;
     p->conv_half = half != nullptr;
     p->borrowed = half && half->share;
+    p->own_cbuf = p->borrowed && half->own_cbuf;
     p->n2r = n2;
     p->real_any = any;
     p->real_form = form;
@@ -2414,13 +2605,18 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     // (half plans: a receive buffer alone, and only with a communicator)
     const size_t b1 = half ? (size_t)conv_real_recv_count(n0, n1, nh, total_devices) * cs : (size_t)std::max({rc0 * rs, cc0 * cs, rc_last * rs, cc_last * cs});
     const std::string rkey = std::string(half ? "convr:" : "r2c:") + std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" +
-                             std::to_string(dtype) + ":" + std::to_string(total_devices);
+                             std::to_string(dtype) + ":" + std::to_string(total_devices) +
+                             (half && half->output > 0 ? ":o" + std::to_string(half->output) : std::string());
     if (e == hipSuccess && (!half || comm) && comm_recv_alloc(comm, rkey + ":b1", b1, &p->buf1) != DFFT_OK) e = hipErrorOutOfMemory;
     // the intermediate, also the send buffer of the backward exchange ([N0][ys][nh])
     const size_t cbytes = (size_t)(half ? p->xs * p->cl.plane : std::max(p->xs * p->cl.plane, n0 * p->ys * nh)) * cs;
     if (p->borrowed) {
         p->cbuf = half->share->cbuf;
         p->stream = half->share->stream;
+        if (p->own_cbuf) {
+            p->cbuf = nullptr;
+            if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
+        }
     } else {
         if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
@@ -2431,7 +2627,7 @@ static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n
     if (e == hipSuccess && !half) e = hipMemcpyAsync(p->buf1, in, ibytes, hipMemcpyDeviceToDevice, p->stream);
     // (half plans capture nothing.  Their intermediate is cleared ONCE: its columns n2/2 + 1 .. nc - 1 and its row padding are never
     // written with anything but zeros afterwards -- the argument is at the top of dfft_conv_real.hip)
-    if (e == hipSuccess && half && !p->borrowed) e = hipMemsetAsync(p->cbuf, 0, cbytes, p->stream);
+    if (e == hipSuccess && half && (!p->borrowed || p->own_cbuf)) e = hipMemsetAsync(p->cbuf, 0, cbytes, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     for (auto& ev : p->ev)
         if (e == hipSuccess) e = hipEventCreate(&ev);
@@ -2939,7 +3135,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     if (plan->lbuf) hipFree(plan->lbuf);
     if (plan->bs.scratch) hipFree(plan->bs.scratch);
     if (plan->rscratch) hipFree(plan->rscratch);
-    if (plan->cbuf && !plan->borrowed) hipFree(plan->cbuf);
+    if (plan->cbuf && (!plan->borrowed || plan->own_cbuf)) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
     if (plan->zy_err) hipHostFree(plan->zy_err);

@@ -251,6 +251,33 @@ int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, lo
 /* Elements of this device's share of a real-field plan's filter: local_n1 * (N2/2 + 1) * N0 (host-only arithmetic); -1 for bad arguments. */
 long long dfft_conv_real_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx);
 
+/* ---- multi-output real-field spectral-filter plans ---------------------------------------------------------------------------------
+ * K real outputs of ONE real input through ONE base filter and per-output separable factors:
+ *     y_k = irfftn( rfftn(x) * H * (a_k (x) b_k (x) c_k), s = (N0, N1, N2) ),   k = 0 .. noutputs-1,
+ * a_k, b_k, c_k complex vectors along kx, ky, kz (i*k for a gradient component, a separable window, or ones) -- a potential and its
+ * three force components, say.  The input is transformed once, the filter copy is kept once, the forward exchange runs once; only the
+ * inverse halves run per output.
+ * in and every outs[k]: REAL X slabs [x_local][N1][N2] of dfft_local_count reals, exactly as for dfft_plan_create_conv_real.  `in` is
+ * read at every execute and left alone unless one outs[k] equals it (allowed: the forward half has consumed `in` before anything is
+ * written).  Two equal outs entries, a NULL entry, outs == NULL or noutputs outside 1 .. DFFT_CONV_MAX_OUTPUTS: DFFT_EINVAL.
+ * Everything dfft_plan_create_conv_real refuses is refused here with the same codes (flags, N0 / N1 not single-pass, N2 not of real form
+ * 1, more than 2^31 complex elements per device), every check before the device is queried.
+ * dfft_conv_set_filter, dfft_conv_set_kernel, dfft_conv_real_filter_count and dfft_plan_set_scale work on the handle unchanged: one base
+ * filter, complex or real, 1/(N0*N1*N2) and the scale folded in.  dfft_execute produces all outputs (DFFT_EINVAL before a base filter is
+ * set); dfft_plan_sync, dfft_plan_stream, dfft_plan_destroy, dfft_plan_tune, dfft_kernel_times and the buffer accessors as for
+ * dfft_plan_create_conv_real; dfft_stage_times: forward YZ stage, all 1 + K exchanges, the X stage, the sum of the K inverse stages;
+ * dfft_plan_describe: "pipeline=conv-real-multi outputs=<K> xconv=fused|multi filter=complex|real|unset width=<Nc> ...".  Execute
+ * allocates nothing.  All halves run on one stream, one after another. */
+#define DFFT_CONV_MAX_OUTPUTS 8
+int dfft_plan_create_conv_real_multi(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* const* outs,
+                                     int noutputs, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* The factors of output k: device pointers to elements of the plan's COMPLEX type, ax of N0, ay of N1 and az of N2/2 + 1 elements.  ay is
+ * the whole global vector on every rank; the plan takes its own rows y0 .. y0 + y_local.  NULL means all ones, and before the first call
+ * for an output all three of its factors are ones.  The plan keeps private copies (az zero-padded to the plan's width Nc).  Synchronises
+ * like dfft_conv_set_filter, may be called between executes and leaves the other outputs alone.  DFFT_EINVAL for a handle that is not a
+ * multi-output plan and for k out of range. */
+int dfft_conv_set_factors(dfft_plan_t plan, int k, const void* ax, const void* ay, const void* az);
+
 /* Elements the caller's buffers of an r2c plan must hold on device global_idx: *real_count reals on the real side (R2C input / C2R
  * output), *complex_count complex elements on the complex side (R2C output / C2R input) -- the result [y_local][Nh][N0] and, for P > 1,
  * the packed send layout of the forward exchange, which the R2C plan writes into `out` before its result.  Pure host arithmetic. */
