@@ -21,6 +21,7 @@ F64, F32 = 0, 1
 PLAN_DEFAULT, PLAN_UNFUSED, PLAN_INPUT_FROM_IN, PLAN_OVERLAP, PLAN_NATURAL, PLAN_ANY_LENGTH = 0, 1, 2, 4, 8, 16
 EXEC_ASYNC, EXEC_SYNC_STAGES, EXEC_PRINT, EXEC_NO_TIMING = 0, 1, 2, 4
 FILTER_COMPLEX, FILTER_REAL = 0, 1
+R2R_DCT2, R2R_DCT3, R2R_DST2, R2R_DST3 = 0, 1, 2, 3
 CONV_MAX_OUTPUTS = 8
 OK, EINVAL, EHIP, ERCCL, ENOGPU, ECOMM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -87,6 +88,7 @@ SIGNATURES = {
     "dfft_rfft1d": (C.c_int, [_VP, _VP, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_rfft1d_strided": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_rfft2d_batch": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_r2r1d_strided": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_scale": (C.c_int, [_VP, _LL, C.c_int, C.c_double, _VP]),
     "dfft_trim": (C.c_int, []),
     "dfft_boot_init": (C.c_int, []),

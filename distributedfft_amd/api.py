@@ -676,6 +676,59 @@ def irfft1d(X, n: int, out=None, *, dim: int = -1):
     return out
 
 
+R2R_KINDS = {"dct2": L.R2R_DCT2, "dct3": L.R2R_DCT3, "dst2": L.R2R_DST2, "dst3": L.R2R_DST3}
+
+
+def _r2r_enqueue(src, dst, kind: str, dim: int) -> None:
+    if kind not in R2R_KINDS:
+        raise ValueError(f"kind must be one of {sorted(R2R_KINDS)}, got {kind!r}")
+    import torch
+    batch, n, s, _ = _axis_split(src.shape, dim)
+    code = F64 if src.dtype == torch.float64 else F32
+    L.check(L.load().dfft_r2r1d_strided(src.data_ptr(), dst.data_ptr(), n, s, batch, code, R2R_KINDS[kind], None), "dfft_r2r1d_strided")
+
+
+def r2r(x, kind: str, dim: int = -1, out=None):
+    """DCT / DST of type II or III (kind "dct2" | "dct3" | "dst2" | "dst3") along dimension `dim` of a contiguous float64 / float32
+    device tensor (dfft_r2r1d_strided, the tensor seen as [batch][n][s]), for any n with length_kind(n) != 0.  Unnormalised, scipy.fft's
+    norm=None: type III of type II is 2n x.  Types I and IV are not built.  out=x transforms in place."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    out = _check_out(x, out)
+    with torch.cuda.device(x.device):
+        _r2r_enqueue(x, out, kind, dim)
+        torch.cuda.synchronize()
+    return out
+
+
+def r2rn(x, kinds, dims=None, out=None):
+    """One r2r per listed dimension, in sequence: kinds[i] along dims[i] (dims=None: the last len(kinds) dimensions), the kinds mixed
+    freely -- r2rn(f, ["dct2"] * 3) is the 3-D DCT-II of a single-GPU array.  The first transform goes from x to out, the others run in
+    place on out; out=x transforms in place."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    kinds = list(kinds)
+    dims = list(range(x.dim() - len(kinds), x.dim())) if dims is None else [int(d) for d in dims]
+    if len(kinds) != len(dims) or not kinds:
+        raise ValueError("r2rn: one kind per dimension, at least one")
+    for d in dims:
+        if not -x.dim() <= d < x.dim():
+            raise IndexError(f"dim {d} is out of range for a tensor of {x.dim()} dimensions")
+    if len({d % x.dim() for d in dims}) != len(dims):
+        raise ValueError("r2rn: a dimension is listed twice")
+    for k in kinds:
+        if k not in R2R_KINDS:
+            raise ValueError(f"kind must be one of {sorted(R2R_KINDS)}, got {k!r}")
+    out = _check_out(x, out)
+    with torch.cuda.device(x.device):
+        src = x
+        for k, d in zip(kinds, dims):
+            _r2r_enqueue(src, out, k, d)
+            src = out
+        torch.cuda.synchronize()
+    return out
+
+
 def rfft2d_batch(x, out=None):
     """numpy.fft.rfft2 of every (n1, n2) plane of a contiguous float64 / float32 device tensor [..., n1, n2] -> complex128 / complex64
     [..., n1, n2//2 + 1] (dfft_rfft2d_batch): n2 of any real form, n1 of any length kind.  Unnormalised, out of place."""

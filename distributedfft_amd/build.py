@@ -98,6 +98,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     # real transforms along a strided axis (column pairs): the fused kernels of the tuned lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         units.append((CSRC / "dfft_real_cols.hip", OBJ / f"dfft_real_cols_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-to-real transforms (DCT / DST types II and III): the fused kernels of the tuned lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        units.append((CSRC / "dfft_r2r.hip", OBJ / f"dfft_r2r_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         units.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))

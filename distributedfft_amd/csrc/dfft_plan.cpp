@@ -36,6 +36,7 @@
 #include "dfft_real.h"
 #include "dfft_real_cols.h"
 #include "dfft_real_pair.h"
+#include "dfft_r2r.h"
 #include "dfft_zy.h"
 
 namespace dfft {
@@ -3343,6 +3344,7 @@ int dfft_fft2d_batch_status(void* stream) {
 int dfft_trim(void) {
     long_scratch_trim();
     bluestein_trim();
+    r2r_trim();
     zy2d_trim();
     return DFFT_OK;
 }
@@ -3566,6 +3568,46 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
     L.in = in;
     L.out = out;
     const int rc = real_cols(L, t.get(), bs_fused, scr, need, st);
+    long_scratch_release(lease);
+    return rc;
+}
+
+// Real-to-real transforms (DCT / DST, types II and III) along the middle axis of [batch][n][s] (dfft_r2r.hip)
+int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int kind, void* stream) {
+    if (!in || !out || n < 1 || s < 1 || batch < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3)
+        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: bad arguments");
+    if (length_kind(n) == 0)
+        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: length " + std::to_string(n) + " is outside every form (at most 2^23, or a four-step length)");
+    const uintptr_t bytes = (uintptr_t)batch * n * s * (elem_bytes(dtype) / 2);
+    if (in != out && ranges_overlap(in, bytes, out, bytes))
+        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: in and out overlap partly (the transform runs out of place or exactly in place)");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_r2r1d_strided: no HIP device visible (no CPU fallback)");
+    const hipStream_t  st = (hipStream_t)stream;
+    const bool         three = kind == DFFT_R2R_DCT3 || kind == DFFT_R2R_DST3;
+    const bool         fused_on = r2r_fused_env();
+    R2rTablePtr        w;
+    BluesteinTablesPtr t;
+    if (int rc = r2r_table(n, dtype, &w)) return rc;
+    if (length_kind(n) == 3)
+        if (int rc = bluestein_tables(n, dtype, three ? DFFT_BACKWARD : DFFT_FORWARD, &t)) return rc;
+    const bool bs_fused = bluestein_fused_env();
+    R2rLaunch  L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.kind = kind;
+    L.n = n;
+    L.s = s;
+    L.batch = batch;
+    L.in = in;
+    L.out = out;
+    const size_t     need = r2r_scratch_bytes(L, fused_on, t.get(), bs_fused);
+    LongScratchLease lease = nullptr;
+    void*            scr = nullptr;
+    if (need) {
+        scr = long_scratch(need, st, &lease);
+        if (!scr) return fail(DFFT_EHIP, "dfft_r2r1d_strided: cannot allocate the scratch buffer");
+    }
+    const int rc = r2r(L, *w, fused_on, t.get(), bs_fused, scr, need, st);
     long_scratch_release(lease);
     return rc;
 }

@@ -377,6 +377,26 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
  * into a scratch group, then C2R rows into `out`.  Arguments are checked before the device is queried. */
 int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream);
 
+/* Real-to-real transforms along the middle axis of reals [batch][n][s] (s = 1: contiguous rows), for ANY n of dfft_length_kind 1, 2 or 3
+ * (n = 1 included).  Unnormalised, scipy.fft's norm=None and FFTW's REDFT10 / REDFT01 / RODFT10 / RODFT01:
+ *   DFFT_R2R_DCT2  y[k] = 2 sum_j x[j] cos(pi k (2j+1) / 2n)
+ *   DFFT_R2R_DCT3  y[j] = x[0] + 2 sum_{k>=1} x[k] cos(pi k (2j+1) / 2n)
+ *   DFFT_R2R_DST2  y[k] = 2 sum_j x[j] sin(pi (k+1) (2j+1) / 2n)
+ *   DFFT_R2R_DST3  y[j] = (-1)^j x[n-1] + 2 sum_{k<n-1} x[k] sin(pi (k+1) (2j+1) / 2n)
+ * so type III of type II is 2n x.  Types I and IV are NOT built.  dtype DFFT_F64 (double) or DFFT_F32 (float).  Out of place or exactly
+ * in place (out == in); byte ranges that overlap only partly: DFFT_EINVAL; with out != in, `in` is never written.  Any s >= 1 and any
+ * element-aligned pointers.  Adjacent columns 2c, 2c + 1 (s > 1) or rows 2p, 2p + 1 (s = 1) share one n-point complex transform (an odd
+ * last one is paired with zeros), so each one's rounding error is bounded relative to its pair's combined magnitude.  Tuned single-pass
+ * n (for s > 1: n * s < 2^31) run as ONE launch that moves the field once in and once out (csrc/dfft_r2r.hip); every other n, and every n
+ * under DFFT_R2R_FUSED=0 (read per call), runs pre kernel -> n-point transform -> post kernel in batch chunks.  Scratch, the quarter-wave
+ * tables and the Bluestein tables come from the caches dfft_trim frees; a call allocates nothing once they are warm.  Arguments are
+ * checked before the device is queried. */
+#define DFFT_R2R_DCT2 0
+#define DFFT_R2R_DCT3 1
+#define DFFT_R2R_DST2 2
+#define DFFT_R2R_DST3 3
+int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int kind, void* stream);
+
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
  * `batch` planes of [n1][n2] complex elements (n2 contiguous), each transformed along both axes, in place (out == in) or out
@@ -394,8 +414,8 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
 int dfft_fft2d_batch_status(void* stream);
 
 /* Frees the scratch buffers the 1-D entry points cache per (device, stream) for lengths above 4096 (four-step transforms) and for
- * Bluestein transforms, the cached Bluestein tables (a plan keeps those of its own axes until it is destroyed) and the
- * control blocks of dfft_fft2d_batch.
+ * Bluestein transforms, the cached Bluestein tables (a plan keeps those of its own axes until it is destroyed), the quarter-wave
+ * tables of dfft_r2r1d_strided and the control blocks of dfft_fft2d_batch.
  * Buffers in use by a call in progress are left alone.  No counterpart in the reference. */
 int dfft_trim(void);
 
