@@ -60,6 +60,7 @@ SIGNATURES = {
     "dfft_r2c_counts": (C.c_int, [_LL, _LL, _LL, C.c_int, C.c_int, _LLP, _LLP]),
     "dfft_plan_create_conv": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_conv_filter_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
+    "dfft_conv_fused_applies": (C.c_int, [C.c_int, _LL, _LL, _LL, _LL, _LL, C.c_int, _VP, _VP]),
     "dfft_plan_create_conv_real": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_uint]),
     "dfft_conv_real_filter_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),
     "dfft_plan_create_conv_real_multi": (C.c_int, [C.POINTER(_VP), _LL, _LL, _LL, C.c_int, _VP, C.POINTER(_VP), C.c_int, _VP, C.c_int, C.c_int,

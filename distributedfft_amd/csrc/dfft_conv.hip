@@ -281,6 +281,9 @@ bool conv_fused_applies(const ConvLaunch& L) {
     if (!conv_fused_n(L.n0) || L.rows < 1 || L.ncols < 1) return false;
     if (L.rot > 0 && (L.ncols & (L.ncols - 1)) != 0) return false;
     if (L.dtype == F32 && ((L.ncols | L.plane | L.pitch | (long long)L.rot) & 1)) return false;  // fp32 runs on column pairs
+    // ... with 16-byte accesses on both sides: a caller's buffer that is only 8-byte aligned (the P = 1 natural layout stores into `out`)
+    // takes the multi route, whose column launches fall back per base (make_pair_launch)
+    if (L.dtype == F32 && (((uintptr_t)L.in | (uintptr_t)L.out) & 15)) return false;
     const long long lanes = L.dtype == F32 ? 2 : 1;
     return (long long)L.n0 * (L.plane / lanes) + L.pitch / lanes < (1ll << 32) && L.rows * ((L.ncols / lanes + 7) / 8) < (1ll << 31);
 }

@@ -250,6 +250,11 @@ hipError_t launch_conv_multi_fused(const ConvLaunch& L, const ConvMultiArgs& M, 
     if (!conv_fused_applies(L) || L.rot != 0 || K < 1 || K > CONV_MAX_OUTPUTS) return hipErrorInvalidValue;
     for (int k = 0; k < K; ++k)
         if (!M.out[k] || !M.ax[k] || !M.by[k] || !M.cz[k]) return hipErrorInvalidValue;
+    // fp32 stores column pairs: every slab on a 16-byte boundary, like L.in (conv_fused_applies).  The slabs are the plan's own
+    // allocations today; a caller's 8-byte-aligned buffer here must fail loudly instead of taking 16-byte stores
+    if (L.dtype == F32)
+        for (int k = 0; k < K; ++k)
+            if ((uintptr_t)M.out[k] & 15) return hipErrorInvalidValue;
     switch (L.n0) {
 #define DFFT_XM_CASE(N, GRP, E, ...) \
     case N: return xm_run<N>(L, M, K, stream);

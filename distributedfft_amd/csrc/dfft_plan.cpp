@@ -1252,6 +1252,15 @@ static int place_recv_buffer(dfft_plan_s* p) {
     return rc;
 }
 
+// the byte ranges [a, a + ab) and [b, b + bb) overlap (or start at the same address)
+static bool ranges_overlap(const void* a, uintptr_t ab, const void* b, uintptr_t bb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 == b0 || (a0 < b0 + bb && b0 < a0 + ab);
+}
+// The complex entry points and plans run out of place or exactly in place: two different pointers whose `bytes`-long ranges overlap
+// would have one pass read what another has already overwritten.
+static bool partly_overlap(const void* in, const void* out, uintptr_t bytes) { return in != out && ranges_overlap(in, bytes, out, bytes); }
+
 extern "C" {
 
 const char* dfft_version(void) { return "dfft-mi355x 0.1 (gfx950)"; }
@@ -1868,6 +1877,11 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
 
 int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                      void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
+    // in place (out == NULL or out == in) or out of place: `in` and `out` of dfft_max_count elements each must not overlap partly
+    if (plan && in && out && n0 >= 1 && n1 >= 1 && n2 >= 1 && (dtype == DFFT_F64 || dtype == DFFT_F32) && total_devices >= 1 && global_idx >= 0 &&
+        global_idx < total_devices &&
+        partly_overlap(in, out, (uintptr_t)dfft_max_count(n0, n1, n2, total_devices, global_idx == total_devices - 1) * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, "dfft_plan_create: in and out overlap partly (a plan runs out of place or exactly in place)");
     return plan_create_impl(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, 0);
 }
 
@@ -2134,6 +2148,23 @@ long long dfft_conv_filter_count(long long n0, long long n1, long long n2, int t
     return make_slab(n1, total_devices).size(global_idx) * n2 * n0;
 }
 
+int dfft_conv_fused_applies(int dtype, long long n0, long long rows, long long ncols, long long plane, long long pitch, int rot, const void* in,
+                            const void* out) {
+    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || n0 < 1 || n0 > 4096 || rows < 1 || ncols < 1 || plane < 1 || pitch < 1 || rot < 0) return 0;
+    ConvLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.n0 = (int)n0;
+    L.rows = rows;
+    L.ncols = ncols;
+    L.plane = plane;
+    L.pitch = pitch;
+    L.rot = rot;
+    L.in = in;
+    L.out = const_cast<void*>(out);
+    return conv_fused_applies(L) ? 1 : 0;
+}
+
 int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
                           int global_idx, int total_devices, unsigned flags) {
     const std::string fn = "dfft_plan_create_conv";
@@ -2151,6 +2182,9 @@ int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long lo
             return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) + " -- every axis must be a single-pass length (products of 2, 3, 5, 7 up to 4096)");
     const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
     if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1) return fail(DFFT_EINVAL, fn + ": slab decomposition leaves the last device empty");
+    // (the X slabs the caller's buffers hold: dfft_local_count elements)
+    if (out && partly_overlap(in, out, (uintptr_t)(sx.size(global_idx) * n1 * n2) * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, fn + ": in and out overlap partly (a plan runs out of place or exactly in place)");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
 
     const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
@@ -2419,6 +2453,9 @@ static int conv_real_create(const std::string& fn, dfft_plan_t* plan, long long 
             c->M.ax[k] = c->M.by[k] = c->M.cz[k] = c->fact;
             c->unit[k] = true;
         }
+        // the fused K-output kernel stores fp32 column pairs into every slab (16-byte accesses, like conv_fused_applies asks of L.in)
+        for (int k = 0; k < nout && dtype == DFFT_F32; ++k)
+            if ((uintptr_t)c->M.out[k] & 15) c->fused = false;
     }
     *plan = p;
     return DFFT_OK;
@@ -3148,6 +3185,8 @@ int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype
     if (!in || !out || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
         return fail(DFFT_EINVAL, "dfft_fft1d_rows: bad arguments");
     if (!dfft_length_supported(n)) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_rows: unsupported length");
+    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, "dfft_fft1d_rows: in and out overlap partly (the transform runs out of place or exactly in place)");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_rows: no HIP device visible (no CPU fallback)");
     return fft_rows(in, out, (int)n, batch, dtype, direction, (hipStream_t)stream);
 }
@@ -3208,6 +3247,8 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
     if (!in || !out || n1 < 1 || n2 < 1 || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
         return fail(DFFT_EINVAL, "dfft_fft2d_batch: bad arguments");
     if (!dfft_length_supported(n1) || !dfft_length_supported(n2)) return fail(DFFT_EUNSUPPORTED, "dfft_fft2d_batch: unsupported length");
+    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n1 * (uintptr_t)n2 * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, "dfft_fft2d_batch: in and out overlap partly (the transform runs out of place or exactly in place)");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft2d_batch: no HIP device visible (no CPU fallback)");
     if (batch == 0) return DFFT_OK;
     hipStream_t     s = (hipStream_t)stream;
@@ -3362,6 +3403,8 @@ int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batc
         return fail(DFFT_EINVAL, "dfft_fft1d_any: bad arguments");
     const int kind = length_kind(n);
     if (kind == 0) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_any: length " + std::to_string(n) + " is outside every form (at most 2^23, or a four-step length)");
+    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * (uintptr_t)s * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, "dfft_fft1d_any: in and out overlap partly (the transform runs out of place or exactly in place)");
     if (kind != 3)  // single-pass and four-step lengths: exactly the existing entry points
         return s == 1 ? dfft_fft1d_rows(in, out, n, batch, dtype, direction, stream) : dfft_fft1d_cols(in, out, n, s, batch, dtype, direction, stream);
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_any: no HIP device visible (no CPU fallback)");
@@ -3495,12 +3538,6 @@ static int any_run(const AnyPass& A, const void* in, void* out, long long batch,
     if (A.kind == 3) return bluestein_fft(*A.t, in, out, A.s, batch, 1.0, A.bs_fused, scr, A.need, st);
     if (A.kind == 2) return long_fft(in, out, A.n, A.s, batch, A.dtype, A.dir, 1.0, scr, st);
     return A.s == 1 ? dfft_fft1d_rows((void*)in, out, A.n, batch, A.dtype, A.dir, st) : dfft_fft1d_cols((void*)in, out, A.n, A.s, batch, A.dtype, A.dir, st);
-}
-
-// the byte ranges [a, a + ab) and [b, b + bb) overlap (or start at the same address)
-static bool ranges_overlap(const void* a, uintptr_t ab, const void* b, uintptr_t bb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 == b0 || (a0 < b0 + bb && b0 < a0 + ab);
 }
 
 extern "C" {
@@ -3673,6 +3710,8 @@ int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long
         (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
         return fail(DFFT_EINVAL, "dfft_fft1d_cols: bad arguments");
     if (!dfft_length_supported(n)) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_cols: unsupported length");
+    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * (uintptr_t)width * elem_bytes(dtype)))
+        return fail(DFFT_EINVAL, "dfft_fft1d_cols: in and out overlap partly (the transform runs out of place or exactly in place)");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_cols: no HIP device visible (no CPU fallback)");
     if (n > 4096) {
         if (batch == 0) return DFFT_OK;

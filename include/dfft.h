@@ -161,7 +161,11 @@ int dfft_free(void* p, int flag);
  * fft_mpi_plan_dft_c2c_3d (fft_mpi_3d_api.cpp:41-141).  `in`/`out` are device buffers of dfft_max_count elements owned
  * by the caller; out == NULL or out == in selects in-place (bufferDev2 = in).  The plan allocates bufferDev1 and copies
  * `in` into it (input is captured at plan time or by writing dfft_plan_buffer1()).  comm may be NULL when
- * total_devices == 1.  The calling thread's current HIP device is the plan's device. */
+ * total_devices == 1.  The calling thread's current HIP device is the plan's device.
+ * Buffer contract: any element-aligned pointers (fp32 buffers that are only 8-byte aligned run the scalar column kernels instead of the
+ * column-pair ones: same results to rounding, lower bandwidth); in place (out == in or NULL) or out of place; byte ranges that overlap
+ * only partly: DFFT_EINVAL, checked over dfft_max_count elements before the device is queried; with out != in and
+ * DFFT_PLAN_INPUT_FROM_IN, `in` is never written; nothing outside the dfft_max_count elements of `in` and `out` is written. */
 int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                      void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
 /* Real-to-complex (direction DFFT_FORWARD) / complex-to-real (DFFT_BACKWARD) slab plan: the C2C contract above with the last axis
@@ -204,11 +208,20 @@ int dfft_plan_create_r2c_any(dfft_plan_t* plan, long long n0, long long n1, long
  * ("pipeline=conv xconv=fused|multi filter=complex|real|unset ...") and dfft_plan_destroy work on it.  dfft_plan_set_scale(s) multiplies
  * the output by s; the factor is folded into the filter copy, so it TAKES EFFECT AT THE NEXT dfft_conv_set_filter / dfft_conv_set_kernel
  * (the stored copy is not re-folded).  dfft_plan_tune is a no-op (the X stage works in place: no placement to choose);
- * dfft_kernel_times returns DFFT_EUNSUPPORTED, dfft_plan_buffer1 / dfft_plan_result / dfft_plan_workbuf NULL. */
+ * dfft_kernel_times returns DFFT_EUNSUPPORTED, dfft_plan_buffer1 / dfft_plan_result / dfft_plan_workbuf NULL.
+ * Buffer contract: any element-aligned pointers; in place (out == in or NULL) or out of place; byte ranges that overlap only partly:
+ * DFFT_EINVAL (over dfft_local_count elements, before the device is queried); with out != in, `in` is never written; nothing outside
+ * the dfft_local_count elements of `out` is written.  The one-kernel X stage moves fp32 elements in pairs: a P = 1 plan whose fp32 `out`
+ * is only 8-byte aligned runs the three-launch stage instead (dfft_plan_describe: xconv=multi; dfft_conv_fused_applies). */
 #define DFFT_FILTER_COMPLEX 0
 #define DFFT_FILTER_REAL 1
 int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out,
                           dfft_comm_t comm, int global_idx, int total_devices, unsigned flags);
+/* Diagnostics (host-only arithmetic): 1 if the one-kernel X stage serves a slab of `rows` rows per X plane, `ncols` columns, element
+ * strides plane / pitch and row rotation `rot` at the addresses in / out, else 0 (the plan then runs the three-launch stage).  A fused
+ * length N0; DFFT_F32 runs on column PAIRS with 16-byte accesses: even ncols, plane, pitch and rot, and in / out on 16-byte boundaries. */
+int dfft_conv_fused_applies(int dtype, long long n0, long long rows, long long ncols, long long plane, long long pitch, int rot,
+                            const void* in, const void* out);
 /* Elements of this device's share of the filter: local_n1 * N2 * N0 (host-only arithmetic, no device needed); -1 for bad arguments. */
 long long dfft_conv_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx);
 /* The filter's spectrum, given in the layout a forward dfft_plan_create plan of the same shape / communicator returns on this device:
@@ -336,6 +349,11 @@ int dfft_kernel_times(dfft_plan_t plan, double t[3]);
 int dfft_plan_destroy(dfft_plan_t plan);
 
 /* ---- batched 1D building block (the kernels behind t0/t3; templateFFT batchTest-style checks) ---------------------------
+ * Buffer contract of dfft_fft1d_rows, dfft_fft1d_cols, dfft_fft1d_any and dfft_fft2d_batch: any element-aligned pointers (fp32 column
+ * launches whose `in` or `out` is only 8-byte aligned run the scalar float2 kernels instead of the column-pair ones); in place
+ * (out == in) or out of place; byte ranges that overlap only partly: DFFT_EINVAL, checked before the device is queried; with out != in,
+ * `in` is never written (the four-step and Bluestein forms work through scratch); nothing outside the batch * n (* width) elements of
+ * `out` is written; batch == 0 writes nothing and returns DFFT_OK.
  * In-place or out-of-place length-n C2C FFT of `batch` contiguous rows (stride n). */
 int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
 /* Length-n FFT down the columns of a [n][width] row-major matrix, `batch` matrices back to back. */
