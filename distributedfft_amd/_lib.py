@@ -39,6 +39,14 @@ SIGNATURES = {
     "dfft_length_kind": (C.c_int, [_LL]),
     "dfft_bluestein_length": (_LL, [_LL]),
     "dfft_real_form": (C.c_int, [_LL]),
+    "dfft_cols_extent_supported": (C.c_int, [_LL, _LL, C.c_int, C.c_int]),
+    "dfft_fft1d_any_extent_supported": (C.c_int, [_LL, _LL, C.c_int, C.c_int, C.c_int]),
+    "dfft_bluestein_fused_applies": (C.c_int, [_LL, _LL]),
+    "dfft_rfft_cols_fused_applies": (C.c_int, [_LL, _LL, C.c_int]),
+    "dfft_r2r_fused_applies": (C.c_int, [_LL, _LL, C.c_int, C.c_int, C.c_int]),
+    "dfft_fft1d_any_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int]),
+    "dfft_rfft1d_strided_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int]),
+    "dfft_r2r1d_strided_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int, C.c_int, C.c_int]),
     "dfft_proper_device_count": (C.c_int, [_LLP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dfft_local_count": (_LL, [_LLP, C.c_int, C.c_int]),
     "dfft_max_count": (_LL, [_LL, _LL, _LL, C.c_int, C.c_int]),

@@ -36,6 +36,9 @@ void bluestein_trim();
 
 // DFFT_BLUESTEIN_FUSED (default 1): 0 forces the multi-pass form for n <= 2048 (A/B and measurement switch; same M, same tables)
 bool bluestein_fused_env();
+// Whether bluestein_fft runs [batch][n][s] as one launch (`fused`: the caller's DFFT_BLUESTEIN_FUSED reading): n <= 2048 and, for s > 1,
+// n * s < 2^31; otherwise the multi-pass form in batch chunks.
+bool bluestein_runs_fused(long long n, long long s, bool fused);
 // Scratch bytes a call of bluestein_fft on [batch][n][s] needs (0 for the fused form); batch chunks keep it at most
 // max(256 MiB, what one transform needs).
 size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused);

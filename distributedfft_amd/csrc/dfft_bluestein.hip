@@ -518,10 +518,16 @@ static size_t per_transform_bytes(const BluesteinTables& T, long long s) {
     return (size_t)T.M * (size_t)s * elem_bytes(T.dtype) * (T.M > 4096 ? 2 : 1);  // padded data (+ long_fft's scratch)
 }
 
-static bool runs_fused(const BluesteinTables& T, bool fused) { return T.n == 1 || (fused && T.n <= kBluesteinFusedMaxLength); }
+// The one-launch column kernel keeps a batch item's point offsets in 32 bits: n * s >= 2^31 runs the multi-pass form (as the real-column
+// and r2r rules send that extent to their composed routes).  The decision never looks at the batch, so a scratch size asked for one
+// chunk holds for every other; a one-launch call of 2^31 or more rows or column tiles (upwards of 170 GB) is turned down by launch_bluestein.
+bool bluestein_runs_fused(long long n, long long s, bool fused) {
+    return n == 1 || (fused && n <= kBluesteinFusedMaxLength && (s <= 1 || n * s < (1ll << 31)));
+}
+static bool runs_fused(const BluesteinTables& T, long long s, bool fused) { return bluestein_runs_fused(T.n, s, fused); }
 
 size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused) {
-    if (runs_fused(T, fused) || batch <= 0 || s <= 0) return 0;
+    if (runs_fused(T, s, fused) || batch <= 0 || s <= 0) return 0;
     const size_t    per = per_transform_bytes(T, s);
     const long long fit = std::max<long long>(1, (long long)(std::max(kScratchCap, per) / per));
     return (size_t)std::min(batch, fit) * per;
@@ -544,7 +550,7 @@ int bluestein_fft(const BluesteinTables& T, const void* in, void* out, long long
         DFFT_HIP_TRY(hipGetLastError());
         return DFFT_OK;
     }
-    if (runs_fused(T, fused)) {
+    if (runs_fused(T, s, fused)) {
         FusedLaunch F;
         F.dtype = T.dtype;
         F.n = (int)T.n;

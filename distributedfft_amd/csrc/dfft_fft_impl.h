@@ -685,6 +685,14 @@ inline long long axis_max_offset(const AxisMap& m, int n) {
     }
     return mx;
 }
+// the rule of dfft_kernels.h (kTileColsMax): every offset a thread of fft_tiles_kernel forms relative to its tile base fits 32 bits
+inline bool tile_offsets_fit32(const FftLaunch& L) {
+    auto fits = [&](const AxisMap& m) {
+        const long long c = m.cstride < 0 ? -m.cstride : m.cstride;
+        return axis_max_offset(m, L.n) + (kTileColsMax - 1) * c < (1ll << 32);
+    };
+    return fits(L.imap) && fits(L.omap);
+}
 // GENERAL = ragged last column tile and/or uneven last slab (slow-path address terms compiled in).
 // All offsets, strides and column counts are in units of one V (for cpair: 16 bytes = two fp32 columns).
 template <class V, class P, int CB, int G, int DIR, bool GENERAL, class Tune>
@@ -2082,7 +2090,7 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
     L.tiles_per_a = (L.ncols + CBC - 1) / CBC;
     L.ntiles = L.na * L.tiles_per_a;
     if (L.ntiles <= 0) return hipSuccess;
-    if (L.ntiles >= (1ll << 31)) return hipErrorInvalidValue;
+    if (L.ntiles >= (1ll << 31) || !tile_offsets_fit32(L)) return hipErrorInvalidValue;
     const bool general = (L.ncols % CBC) != 0 || L.imap.last_delta != 0 || L.omap.last_delta != 0;
     // rotated rows (RotMap): whole tiles move inside their rows, so the rotation and the row length must be multiples of the
     // widest tile used below (a full line), sides must have unit column stride, and the launch must be a fast-path one
@@ -2490,7 +2498,7 @@ template <class P> hipError_t launch_scalar32(const FftLaunch& Lin, hipStream_t 
     L.tiles_per_a = (L.ncols + CBC - 1) / CBC;
     L.ntiles = L.na * L.tiles_per_a;
     if (L.ntiles <= 0) return hipSuccess;
-    if (L.ntiles >= (1ll << 31)) return hipErrorInvalidValue;
+    if (L.ntiles >= (1ll << 31) || !tile_offsets_fit32(L)) return hipErrorInvalidValue;
     const bool general = (L.ncols % CBC) != 0 || L.imap.last_delta != 0 || L.omap.last_delta != 0;
     if (L.rot.in_mode != 0 || L.rot.out_mode != 0) {  // same admission rule as launch_plan (whole 128-byte lines move)
         constexpr int LINE = 128 / (int)sizeof(V);

@@ -77,6 +77,13 @@ enum {
     FFT_HINT_EARLY_WAIT = 8,     // wait for the prefetched tile before this tile's stores are issued
 };
 
+// fft_tiles_kernel keeps a thread's point offsets relative to its tile base in 32 bits, in units of one V (16 bytes for fp64 and for the
+// fp32 column pairs, 8 bytes for scalar fp32): the tuned column launchers turn a launch down (hipErrorInvalidValue) whose largest such
+// offset, axis_max_offset + (kTileColsMax - 1) * cstride, does not stay below 2^32.  cols_offsets_fit32 is that rule for the plain
+// [n][stride_v] columns of dfft_fft1d_cols (dfft_cols_extent_supported exports it); tile bases are 64-bit products and have no limit.
+constexpr long long kTileColsMax = 64;  // no tile is wider (staged stores address 2 * CB <= 32 scalar columns)
+inline bool cols_offsets_fit32(long long n, long long stride_v) { return (n - 1) * stride_v + (kTileColsMax - 1) < (1ll << 32); }
+
 bool fft_length_supported(int n);
 bool fft_length_tuned(int n);  // served by a static plan of dfft_plans.h (not by the run-time-scheduled kernel)
 // run-time-scheduled kernel for 7-smooth lengths <= 4096 that have no tuned plan (dfft_generic.hip)

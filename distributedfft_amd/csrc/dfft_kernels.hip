@@ -38,6 +38,8 @@ bool fft_length_tuned(int n) {
 
 hipError_t launch_fft(const FftLaunch& L, hipStream_t stream) {
     if ((L.cols ? L.na : L.ntiles) <= 0) return hipSuccess;
+    // the kernels take the first slice / row and the tile count as 32-bit unsigned values (a launch's own tile count stays below 2^31)
+    if (L.a_first < 0 || L.a_first + (L.cols ? L.na : L.ntiles) > (1ll << 32)) return hipErrorInvalidValue;
     switch (L.n) {
 #define DFFT_CASE(N, GRP, E, ...) \
     case N: return launch_n<N>(L, stream);

@@ -166,6 +166,54 @@ static int real_form(long long n) {
     return k == 1 ? 2 : (k == 0 ? 0 : 3);
 }
 
+// ---- supported extent of the plan-less column transforms (include/dfft.h, "Supported extent") ------------------------------------------------
+// The tuned column kernels keep a thread's offsets inside one [n][width] matrix in 32 bits, in units of one V (cols_offsets_fit32,
+// dfft_kernels.h): 16 bytes for fp64 and for fp32 column pairs (even width, both pointers 16-byte aligned), 8 bytes for scalar fp32.
+// Every route that ends in those kernels is judged here, before the device is queried and before any scratch is leased.
+// DFFT_NO_PAIRS (make_pair_launch's measurement switch): fp32 columns on the scalar kernels whatever their width
+static bool pairs_disabled_env() {
+    const char* e = getenv("DFFT_NO_PAIRS");
+    return e && *e && *e != '0';
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0 && !pairs_disabled_env(); }
+static bool scratch16() { return !pairs_disabled_env(); }  // the leased scratch is 16-byte aligned
+// one launch of the tuned n-point column kernels on [n][width]
+static bool tuned_cols_ok(long long n, long long width, int dtype, bool pairs) {
+    if (width + kTileColsMax > (1ll << 31)) return false;  // column indices are ints, a ragged last tile counts up to one tile further
+    const bool paired = dtype == DFFT_F32 && pairs && width % 2 == 0;
+    return cols_offsets_fit32(n, paired ? width / 2 : width);
+}
+// long_fft on [n][s], n = N1 * N2: pass A runs N1-point columns of width N2 * s from `in` into the scratch, pass B N2-point columns of
+// width s in place on the scratch (s = 1: rows)
+static bool four_step_ok(long long n, long long s, int dtype, bool in16) {
+    int N1 = 0, N2 = 0;
+    if (!long_split(n, &N1, &N2)) return false;
+    return tuned_cols_ok(N1, (long long)N2 * s, dtype, in16 && scratch16()) && (s == 1 || tuned_cols_ok(N2, s, dtype, scratch16()));
+}
+// dfft_fft1d_cols on [n][width], kinds 1 and 2
+static bool cols_extent_ok(long long n, long long width, int dtype, bool in16, bool out16) {
+    if (width + kTileColsMax > (1ll << 31)) return false;
+    if (n > 4096) return four_step_ok(n, width, dtype, in16);
+    return !fft_length_tuned((int)n) || tuned_cols_ok(n, width, dtype, in16 && out16);  // run-time-scheduled kernel: 64-bit offsets
+}
+// bluestein_fft on [n][s]: one launch, or pad -> M-point transforms in place on the scratch -> finish.  (The pad buffer of a chunk and,
+// M > 4096, long_fft's scratch behind it are 16-byte aligned for fp32 only where M * s is even.)
+static bool bluestein_extent_ok(long long n, long long s, int dtype) {
+    if (s == 1 || bluestein_runs_fused(n, s, bluestein_fused_env())) return true;
+    const long long M = bluestein_padded_length(n);
+    if (M <= 4096) return tuned_cols_ok(M, s, dtype, scratch16());
+    return four_step_ok(M, s, dtype, scratch16() && (M * s) % 2 == 0);
+}
+// n-point transforms along the middle axis of [batch][n][s] (dfft_fft1d_any, and the inner transforms of the real and r2r composed routes)
+static bool any_extent_ok(long long n, long long s, int dtype, bool in16, bool out16) {
+    if (s == 1) return true;  // rows: tile bases only
+    return length_kind(n) == 3 ? (s + kTileColsMax <= (1ll << 31) && bluestein_extent_ok(n, s, dtype)) : cols_extent_ok(n, s, dtype, in16, out16);
+}
+static std::string extent_message(const char* fn, long long n, long long s) {
+    return std::string(fn) + ": n = " + std::to_string(n) + ", width = " + std::to_string(s) +
+           ": a column pass would span 2^32 or more 16-byte (fp32, odd width or unaligned: 8-byte) units, or width > 2^31 - 64";
+}
+
 // Length-n Bluestein transforms of data[batch][n][s] (dfft_bluestein.hip): with the executing plan's tables and scratch, or -- plan-less
 // callers -- the cached tables and the per-(device, stream) scratch lease of the four-step transforms
 static int bluestein_pass(const void* in, void* out, long long n, long long s, long long batch, int dtype, int dir, double scale,
@@ -1289,6 +1337,56 @@ int dfft_length_supported(long long n) {
 int dfft_length_kind(long long n) { return length_kind(n); }
 
 long long dfft_bluestein_length(long long n) { return length_kind(n) == 3 ? bluestein_padded_length(n) : 0; }
+
+// Route predicates of the plan-less entry points (read-only; the environment switches are read as a call would read them)
+int dfft_bluestein_fused_applies(long long n, long long s) { return length_kind(n) == 3 && s >= 1 && bluestein_runs_fused(n, s, bluestein_fused_env()); }
+int dfft_rfft_cols_fused_applies(long long n, long long s, int dtype) {
+    return (dtype == DFFT_F64 || dtype == DFFT_F32) && s > 1 && real_cols_fused(n, s, dtype);
+}
+int dfft_r2r_fused_applies(long long n, long long s, int dtype, int kind, int vec) {
+    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3 || n < 1 || s < 1) return 0;
+    return r2r_fused_env() && r2r_fused(n, s, dtype, kind, vec != 0);
+}
+
+// Scratch bytes a plan-less call leases from the per-(device, stream) buffer (0: none), by the routines' own rules and without a device:
+// the sizes depend on a Bluestein length's n, M and dtype only, so tables without device arrays stand in for the cached ones.
+static void scratch_tables(BluesteinTables* T, long long n, int dtype, int dir) {
+    T->n = n;
+    T->M = bluestein_padded_length(n);
+    T->dtype = dtype;
+    T->dir = dir;
+}
+unsigned long long dfft_fft1d_any_scratch_bytes(long long n, long long s, long long batch, int dtype) {
+    const int kind = length_kind(n);
+    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || s < 1 || batch < 1 || kind < 2) return 0;
+    if (kind == 2) return (unsigned long long)batch * n * s * elem_bytes(dtype);
+    if (!bluestein_extent_ok(n, s, dtype)) return 0;  // refused before any lease
+    BluesteinTables T;
+    scratch_tables(&T, n, dtype, DFFT_FORWARD);
+    return bluestein_scratch_bytes(T, s, batch, bluestein_fused_env());
+}
+unsigned long long dfft_rfft1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype) {
+    const int kind = length_kind(n);
+    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || s < 2 || batch < 1 || kind == 0) return 0;
+    BluesteinTables T;
+    scratch_tables(&T, n, dtype, DFFT_FORWARD);
+    return real_cols_scratch_bytes(n, s, batch, dtype, kind == 3 ? &T : nullptr, bluestein_fused_env());
+}
+unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype, int kind, int vec) {
+    const int lk = length_kind(n);
+    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3 || s < 1 || batch < 1 || lk == 0) return 0;
+    BluesteinTables T;
+    scratch_tables(&T, n, dtype, DFFT_FORWARD);
+    R2rLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.kind = kind;
+    L.n = n;
+    L.s = s;
+    L.batch = batch;
+    L.in = L.out = (void*)(uintptr_t)(vec ? 64 : elem_bytes(dtype) / 2);  // r2r_vec looks at the alignment only
+    return r2r_scratch_bytes(L, r2r_fused_env(), lk == 3 ? &T : nullptr, bluestein_fused_env());
+}
 
 int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,
                              int* new_total, int* new_in_rank) {
@@ -3407,6 +3505,7 @@ int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batc
         return fail(DFFT_EINVAL, "dfft_fft1d_any: in and out overlap partly (the transform runs out of place or exactly in place)");
     if (kind != 3)  // single-pass and four-step lengths: exactly the existing entry points
         return s == 1 ? dfft_fft1d_rows(in, out, n, batch, dtype, direction, stream) : dfft_fft1d_cols(in, out, n, s, batch, dtype, direction, stream);
+    if (!any_extent_ok(n, s, dtype, aligned16(in), aligned16(out))) return fail(DFFT_EUNSUPPORTED, extent_message("dfft_fft1d_any", n, s));
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_any: no HIP device visible (no CPU fallback)");
     if (batch == 0) return DFFT_OK;
     return bluestein_pass(in, out, n, s, batch, dtype, direction, 1.0, (hipStream_t)stream);
@@ -3581,6 +3680,13 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
     if (ranges_overlap(in, fwd ? rb : cb, out, fwd ? cb : rb))
         return fail(DFFT_EINVAL, "dfft_rfft1d_strided: in and out overlap (the transform is out of place)");
     if (s == 1) return dfft_rfft1d(in, out, n, batch, dtype, direction, stream);
+    if (!real_cols_fused(n, s, dtype)) {  // multi-pass: n-point columns of the (s + 1) / 2 packed pairs, straight from `in` / into `out` where
+                                          // s is even and that pointer is aligned to a complex element, else on the scratch
+        const bool direct = s % 2 == 0 && (uintptr_t)(fwd ? in : out) % cs == 0;
+        const bool p16 = direct ? aligned16(fwd ? in : out) : scratch16();
+        if (!any_extent_ok(n, (s + 1) / 2, dtype, fwd ? p16 : scratch16(), fwd ? scratch16() : p16))
+            return fail(DFFT_EUNSUPPORTED, extent_message("dfft_rfft1d_strided (packed pairs)", n, (s + 1) / 2));
+    }
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d_strided: no HIP device visible (no CPU fallback)");
     if (batch == 0) return DFFT_OK;
     const hipStream_t  st = (hipStream_t)stream;
@@ -3618,6 +3724,9 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
     const uintptr_t bytes = (uintptr_t)batch * n * s * (elem_bytes(dtype) / 2);
     if (in != out && ranges_overlap(in, bytes, out, bytes))
         return fail(DFFT_EINVAL, "dfft_r2r1d_strided: in and out overlap partly (the transform runs out of place or exactly in place)");
+    if (s > 1 && !(r2r_fused_env() && r2r_fused(n, s, dtype, kind, r2r_vec(in, out, s, dtype))) &&
+        !any_extent_ok(n, (s + 1) / 2, dtype, scratch16(), scratch16()))  // composed route: n-point columns in place on the scratch
+        return fail(DFFT_EUNSUPPORTED, extent_message("dfft_r2r1d_strided (packed pairs)", n, (s + 1) / 2));
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_r2r1d_strided: no HIP device visible (no CPU fallback)");
     const hipStream_t  st = (hipStream_t)stream;
     const bool         three = kind == DFFT_R2R_DCT3 || kind == DFFT_R2R_DST3;
@@ -3704,6 +3813,17 @@ int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long
     return rc;
 }
 
+// The extent rule of dfft_fft1d_cols (include/dfft.h; any_extent_ok above).  `pairs`: both pointers are 16-byte aligned.
+int dfft_cols_extent_supported(long long n, long long width, int dtype, int pairs) {
+    if (n < 1 || width < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || length_kind(n) == 0 || length_kind(n) == 3) return 0;
+    return cols_extent_ok(n, width, dtype, pairs != 0, pairs != 0) ? 1 : 0;
+}
+// The same for dfft_fft1d_any along the middle axis of [batch][n][s], every kind of length; in16 / out16: that pointer is 16-byte aligned.
+int dfft_fft1d_any_extent_supported(long long n, long long s, int dtype, int in16, int out16) {
+    if (n < 1 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || length_kind(n) == 0) return 0;
+    return any_extent_ok(n, s, dtype, in16 != 0, out16 != 0) ? 1 : 0;
+}
+
 int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,
                     void* stream) {
     if (!in || !out || batch < 0 || width < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) ||
@@ -3712,6 +3832,7 @@ int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long
     if (!dfft_length_supported(n)) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_cols: unsupported length");
     if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * (uintptr_t)width * elem_bytes(dtype)))
         return fail(DFFT_EINVAL, "dfft_fft1d_cols: in and out overlap partly (the transform runs out of place or exactly in place)");
+    if (!cols_extent_ok(n, width, dtype, aligned16(in), aligned16(out))) return fail(DFFT_EUNSUPPORTED, extent_message("dfft_fft1d_cols", n, width));
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_cols: no HIP device visible (no CPU fallback)");
     if (n > 4096) {
         if (batch == 0) return DFFT_OK;

@@ -356,9 +356,27 @@ int dfft_plan_destroy(dfft_plan_t plan);
  * `out` is written; batch == 0 writes nothing and returns DFFT_OK.
  * In-place or out-of-place length-n C2C FFT of `batch` contiguous rows (stride n). */
 int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
-/* Length-n FFT down the columns of a [n][width] row-major matrix, `batch` matrices back to back. */
+/* Length-n FFT down the columns of a [n][width] row-major matrix, `batch` matrices back to back.
+ * SUPPORTED EXTENT of the column transforms (this statement holds for dfft_fft1d_cols, dfft_fft1d_any and the inner transforms of
+ * dfft_rfft1d_strided / dfft_r2r1d_strided; beyond it: DFFT_EUNSUPPORTED, before the device is queried and before scratch is leased).
+ * The batch has no limit beyond memory and 2^31 tiles per launch (tile bases are 64-bit).  Inside ONE matrix the tuned kernels keep a
+ * thread's offsets in 32 bits, counted in kernel units of w columns: w = width for fp64 (16 bytes) and for fp32 of odd width or with a
+ * pointer that is only 8-byte aligned (8 bytes), w = width / 2 for fp32 column pairs (16 bytes).  A pass of n' points over w units is
+ * served iff (n' - 1) * w + 63 < 2^32, and width <= 2^31 - 64 always:
+ *   - tuned single-pass n (the plan table, <= 4096): the one pass (n, width);
+ *   - run-time-scheduled n (other 7-smooth n <= 4096): 64-bit offsets, no further limit;
+ *   - four-step n = N1 * N2 (> 4096): pass A (N1, N2 * width) from `in` into the 16-byte-aligned scratch -- pairs iff `in` is aligned --
+ *     and pass B (N2, width) on the scratch;
+ *   - Bluestein n along [n][s], s > 1: one launch iff n <= 2048 and n * s < 2^31; else the M-point passes in place on the scratch:
+ *     (M, s) for M <= 4096, the four-step rule of (M, s) above that.  With M >= 2n - 1 this serves, past n * s = 2^31, fp32 with even
+ *     s up to about M * s < 2^33 and nothing in fp64 or with odd s.  A one-launch call of 2^31 or more rows or column tiles: split the batch.
+ * dfft_cols_extent_supported / dfft_fft1d_any_extent_supported are this rule. */
 int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,
                     void* stream);
+/* 1 when dfft_fft1d_cols accepts [n][width] columns of `dtype`; pairs != 0: both pointers are 16-byte aligned. */
+int dfft_cols_extent_supported(long long n, long long width, int dtype, int pairs);
+/* 1 when dfft_fft1d_any accepts [batch][n][s] of `dtype`, for every kind of n; in16 / out16 != 0: that pointer is 16-byte aligned. */
+int dfft_fft1d_any_extent_supported(long long n, long long s, int dtype, int in16, int out16);
 
 /* Length-n C2C FFT along the middle axis of data[batch][n][s] (s = 1: contiguous rows), unnormalised, in place (out == in) or out of
  * place, for ANY n of kind 1, 2 or 3 (dfft_length_kind).  Kinds 1 and 2 run exactly what dfft_fft1d_rows (s = 1) / dfft_fft1d_cols
@@ -366,8 +384,23 @@ int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long
  * keeps the padded M-point transforms in registers and LDS (the HBM traffic of an n-point transform), above that a multi-pass form on
  * the four-step transforms with scratch from the same per-(device, stream) buffer the four-step lengths use.  The chirp and B^ tables
  * are built on the first call for (device, n, dtype, direction) and cached; dfft_trim frees them and the scratch.
- * DFFT_BLUESTEIN_FUSED=0 (read per call) runs the multi-pass form for n <= 2048 as well (A/B and measurement switch). */
+ * DFFT_BLUESTEIN_FUSED=0 (read per call) runs the multi-pass form for n <= 2048 as well (A/B and measurement switch), and so does a
+ * column call with n * s >= 2^31 (the one-launch kernel keeps an item's offsets in 32 bits) where the M-point passes can serve it: see
+ * SUPPORTED EXTENT at dfft_fft1d_cols.  dfft_bluestein_fused_applies tells the form, dfft_fft1d_any_extent_supported whether the call
+ * is served. */
 int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream);
+int dfft_bluestein_fused_applies(long long n, long long s);
+/* The one-launch rules of dfft_rfft1d_strided (s > 1) and dfft_r2r1d_strided (vec: s even and both pointers aligned to two reals); 0: the
+ * composed / multi-pass route in batch chunks.  Both send n * s >= 2^31 (s > 1) to that route. */
+int dfft_rfft_cols_fused_applies(long long n, long long s, int dtype);
+int dfft_r2r_fused_applies(long long n, long long s, int dtype, int kind, int vec);
+/* Scratch bytes the call leases from the per-(device, stream) buffer dfft_trim frees (0: none, or a call beyond the supported extent,
+ * which leases nothing; no device is queried).  Batch chunks keep
+ * the Bluestein multi-pass, real-column and r2r composed routes at max(256 MiB, one item's) of packed data plus the inner transform's own
+ * scratch; a four-step dfft_fft1d_any takes as much as its data. */
+unsigned long long dfft_fft1d_any_scratch_bytes(long long n, long long s, long long batch, int dtype);
+unsigned long long dfft_rfft1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype);
+unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype, int kind, int vec);
 
 /* Real transforms of `batch` contiguous rows, for ANY n with dfft_real_form(n) != 0.  Forward: reals [batch][n] -> bins [batch][n/2+1]
  * (= numpy.fft.rfft).  Backward: bins -> reals, = n * numpy.fft.irfft(row, n) for ANY input (the imaginary parts of bin 0 and, n even,

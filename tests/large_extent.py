@@ -1,0 +1,359 @@
+"""Helpers of the large-extent tests (tests/test_large_extent_host.py, tests/test_gpu_large_extent.py and the chunk-edge cases of
+tests/test_gpu_bluestein.py / tests/test_gpu_r2r.py): tensors of tens of GiB whose every line is checked, without a reference of that size.
+
+TILED INPUTS.  A tensor is seen as [batch][m][s]; its lines run along the middle axis, line L = b * s + c (rows: s = 1, L = the row).
+Line L holds base line L mod K of K distinct base lines (accuracy_ref's complex_lines / real_lines / half_spectra / r2r_lines /
+complex_planes, whose longdouble transforms are the reference); K is a small prime, 61 unless wrap_distinct rejects it for a shape.
+
+CHECKS.  (1) The first K output lines against the longdouble reference, as accuracy_ref.nu under the family's BOUND (accuracy_ref.check:
+no new tolerance).  (2) EVERY output line against output line L mod K, per line, relative L2 in fp64, in slices on the device: both are
+within BOUND eps sqrt(log2 n) of the same true line, so they differ by at most 2 BOUND eps sqrt(log2 n) -- derived, not tuned.  The worst
+line and its (b, c) are reported.  (3) Out of place: `out` starts as NaN (an unwritten line fails (2)) and the input is rebuilt and
+compared bit for bit afterwards.  In place an unwritten line still holds its input and fails (2).  (4) wrap_distinct: an access that lands
+2^31, 2^32 or 2^33 elements (or 2^31 / 2^32 bytes) away from where it should finds a DIFFERENT value there, a different (L mod K, k).
+
+Everything takes torch tensors on any device: the host tests run the same code on CPU tensors with numpy standing in for the transform.
+Temporaries stay under 1 GiB (SLICE_BYTES per temporary, a handful alive at once).
+
+The mirrors of the library's chunk rules at the end size the chunk-edge cases and the peak memory of a case; tests/test_large_extent_host.py
+holds them against the library's own dfft_*_scratch_bytes exports."""
+import math
+import time
+
+import numpy as np
+
+import accuracy_ref as A
+
+K_DEFAULT = 61
+K_CANDIDATES = (61, 67, 71, 73, 79, 83, 89, 97)
+GIB = 1 << 30
+SLICE_BYTES = 96 << 20
+WRAPS_ELEMS = (1 << 31, 1 << 32, 1 << 33)      # 2^33 elements: 2^32 column pairs of fp32
+WRAPS_BYTES = (1 << 31, 1 << 32)
+CAP_80 = 80 * GIB                              # no case may need more
+
+
+# ---- the wrap assertion ------------------------------------------------------------------------------------------------------------------
+def wrap_hits(batch, m, s, K, shift):
+    """The (carry, line delta) pairs at which flat element e and e + shift of [batch][m][s] hold the same (L mod K, k); [] is a pass.
+    e = (b m + k) s + c; shift = q s + r moves c to c + r - carry s and the row b m + k by q + carry: k is kept iff m divides q + carry,
+    and then the line index moves by (q + carry) / m * s + r - carry s, which must not be a multiple of K."""
+    if shift >= batch * m * s:
+        return []                                # no two elements of the tensor are that far apart
+    q, r = divmod(shift, s)
+    hits = []
+    for carry in ((0, 1) if r else (0,)):
+        rows = q + carry
+        if rows % m == 0:
+            dl = rows // m * s + r - carry * s
+            if dl % K == 0:
+                hits.append((carry, dl))
+    return hits
+
+
+def wrap_distinct(batch, m, s, K, elem_bytes):
+    """True iff no shift of WRAPS_ELEMS elements or WRAPS_BYTES bytes (where that is whole elements) maps an element onto an equal one."""
+    shifts = list(WRAPS_ELEMS) + [w // elem_bytes for w in WRAPS_BYTES if w % elem_bytes == 0]
+    return all(not wrap_hits(batch, m, s, K, d) for d in shifts)
+
+
+def pick_k(shapes):
+    """The first K of K_CANDIDATES that wrap_distinct accepts for every (batch, m, s, elem_bytes) of `shapes`."""
+    for K in K_CANDIDATES:
+        if all(wrap_distinct(b, m, s, K, eb) for b, m, s, eb in shapes):
+            return K
+    raise AssertionError(f"no K of {K_CANDIDATES} keeps wrapped accesses apart for {shapes}")
+
+
+# ---- slices --------------------------------------------------------------------------------------------------------------------------------
+def blocks(batch, m, s, elem_bytes, budget=None):
+    """(b0, b1, c0, c1) blocks covering [batch][m][s], each at most `budget` bytes (whole items, or column ranges of one item)."""
+    budget = SLICE_BYTES if budget is None else budget
+    item = m * s * elem_bytes
+    if item <= budget:
+        nb = max(1, budget // item)
+        for b0 in range(0, batch, nb):
+            yield b0, min(batch, b0 + nb), 0, s
+    else:
+        nc = max(1, budget // (m * elem_bytes))
+        for b in range(batch):
+            for c0 in range(0, s, nc):
+                yield b, b + 1, c0, min(s, c0 + nc)
+
+
+def _line_ids(b0, b1, c0, c1, s, K, device):
+    import torch
+    b = torch.arange(b0, b1, device=device, dtype=torch.int64)[:, None]
+    c = torch.arange(c0, c1, device=device, dtype=torch.int64)[None, :]
+    return (b * s + c) % K                       # [nb][nc]
+
+
+def _tiled_block(baseT, ids):
+    """baseT [m][K], ids [nb][nc] -> [nb][m][nc] (a view of the gathered [m][nb][nc]: the column index stays the fast one)"""
+    return baseT[:, ids].permute(1, 0, 2)
+
+
+def torch_dtype(prec, complex_):
+    import torch
+    return {("f64", True): torch.complex128, ("f32", True): torch.complex64, ("f64", False): torch.float64,
+            ("f32", False): torch.float32}[(prec, bool(complex_))]
+
+
+def base_tensor(base, prec, device):
+    """numpy [K][m] base lines (float32-exact values) -> their transpose [m][K] in the working type on `device`."""
+    import torch
+    b = np.ascontiguousarray(np.asarray(base).T)
+    return torch.from_numpy(b).to(device).to(torch_dtype(prec, np.iscomplexobj(b)))
+
+
+def fill(t, baseT, K):
+    """t [batch][m][s] <- line L = base line L mod K, in slices."""
+    batch, m, s = t.shape
+    assert baseT.shape == (m, K) and baseT.dtype == t.dtype
+    for b0, b1, c0, c1 in blocks(batch, m, s, t.element_size()):
+        t[b0:b1, :, c0:c1] = _tiled_block(baseT, _line_ids(b0, b1, c0, c1, s, K, t.device))
+    return t
+
+
+def _bits(v):
+    """a tensor's elements as integers of the same width (complex: [..., 2]): bit-for-bit comparison, NaN included"""
+    import torch
+    v = torch.view_as_real(v.contiguous()) if v.is_complex() else v.contiguous()
+    return v.view(torch.int64 if v.dtype == torch.float64 else torch.int32)
+
+
+def _block_differs(t, baseT, K, blk):
+    b0, b1, c0, c1 = blk
+    want = _tiled_block(baseT, _line_ids(b0, b1, c0, c1, t.shape[2], K, t.device))
+    ne = _bits(t[b0:b1, :, c0:c1]) != _bits(want)
+    return ne.any(-1) if t.is_complex() else ne
+
+
+def input_intact(t, baseT, K):
+    """None if t still holds exactly what fill wrote (bit for bit), else the first differing (b, k, c)."""
+    import torch
+    batch, m, s = t.shape
+    blks = list(blocks(batch, m, s, t.element_size()))
+    counts = torch.stack([_block_differs(t, baseT, K, blk).sum() for blk in blks]).cpu().tolist()   # one host round trip
+    for blk, n in zip(blks, counts):
+        if n:
+            i = torch.nonzero(_block_differs(t, baseT, K, blk))[0].cpu().tolist()
+            return blk[0] + i[0], i[1], blk[2] + i[2]
+    return None
+
+
+def first_lines(t, K):
+    """The first K lines of [batch][m][s] -> [K][m] (lines L = 0 ... K-1, i.e. (b, c) = divmod(L, s))."""
+    import torch
+    batch, m, s = t.shape
+    assert batch * s >= K, "the tensor has fewer than K lines"
+    if s >= K:
+        return t[0, :, :K].T.contiguous()
+    nb = -(-K // s)
+    return t[:nb].permute(0, 2, 1).reshape(nb * s, m)[:K].contiguous()
+
+
+def worst_line(out, K):
+    """Every line of out [batch][m][s] against line L mod K of out itself: (worst per-line relative L2 difference in fp64, (b, c) of
+    that line).  A line holding a NaN or an infinity counts as infinitely far."""
+    import torch
+    batch, m, s = out.shape
+    wide = torch.complex128 if out.is_complex() else torch.float64
+    first = first_lines(out, K).to(wide)
+    firstT = first.T.contiguous()
+
+    def sq(v):                                   # sum over the line axis (1) of |v|^2
+        return torch.view_as_real(v).pow(2).sum((1, -1)) if v.is_complex() else v.pow(2).sum(1)
+
+    den = sq(first)                              # [K]
+    found = []
+    for b0, b1, c0, c1 in blocks(batch, m, s, 16 if out.is_complex() else 8, SLICE_BYTES // 2):
+        ids = _line_ids(b0, b1, c0, c1, s, K, out.device)
+        d = out[b0:b1, :, c0:c1].to(wide) - _tiled_block(firstT, ids)
+        rel = torch.sqrt(sq(d) / den[ids])
+        rel = torch.nan_to_num(rel, nan=math.inf, posinf=math.inf)
+        v, i = rel.reshape(-1).max(0)
+        found.append((v, i, b0, c0, c1 - c0))
+    vals = torch.stack([f[0] for f in found]).cpu().tolist()
+    idxs = torch.stack([f[1] for f in found]).cpu().tolist()
+    j = max(range(len(found)), key=lambda q: vals[q])
+    _, _, b0, c0, nc = found[j]
+    return float(vals[j]), (b0 + idxs[j] // nc, c0 + idxs[j] % nc)
+
+
+def line_limit(family, prec, n_eff):
+    """2 BOUND eps sqrt(log2 n): two results within BOUND eps sqrt(log2 n) (relative L2) of one true line."""
+    return 2 * A.BOUND[family][prec] * A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
+
+
+WORST_LINES = {}   # (family, prec) -> (worst line difference in units of its limit's eps sqrt(log2 n), case) of this process
+
+
+def check_output(out, ref, K, family, prec, n_eff, what):
+    """Checks (1) and (2) of the module's docstring on out [batch][m][s]; `ref` is the longdouble reference [K][m] of the base lines."""
+    got = first_lines(out, K).cpu().numpy()
+    per_line = [A.nu(got[i:i + 1], ref[i:i + 1], n_eff, prec, (1,)) for i in range(K)]
+    i = max(range(K), key=lambda q: per_line[q] if per_line[q] == per_line[q] else math.inf)   # a NaN line is the worst
+    try:
+        A.check(family, prec, max(per_line[i], A.nu(got, ref, n_eff, prec, (1,))), f"{what} base lines")
+    except AssertionError as e:
+        raise AssertionError((what, "worst base line", i, "at (b, c) =", divmod(i, out.shape[2]), per_line[i]) + tuple(e.args)) from None
+    worst, (b, c) = worst_line(out, K)
+    unit = A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
+    print(f"large-extent {family} {prec} {what}: worst line (b={b}, c={c}) differs from its base line by {worst / unit:.3f} eps sqrt(log2 n)"
+          f" (limit {2 * A.BOUND[family][prec]})")
+    if worst / unit > WORST_LINES.get((family, prec), (-1.0, ""))[0]:
+        WORST_LINES[(family, prec)] = (worst / unit, what)
+    assert worst <= line_limit(family, prec, n_eff), (what, "line", (b, c), "base line", (b * out.shape[2] + c) % K, worst / unit,
+                                                     2 * A.BOUND[family][prec])
+
+
+def case_plan(prec, base_in, ref, batch, s, inplace, scratch=0, K=None):
+    """What a case allocates, before anything is allocated: (K, peak bytes, input dtype, output dtype).  The peak is the buffers, the
+    library's scratch and 1 GiB; it never exceeds the 80 GiB a case may need."""
+    import torch
+    m_in, m_out = base_in.shape[1], ref.shape[1]
+    tin, tout = torch_dtype(prec, np.iscomplexobj(base_in)), torch_dtype(prec, np.iscomplexobj(ref))
+    eb_in, eb_out = torch.empty(0, dtype=tin).element_size(), torch.empty(0, dtype=tout).element_size()
+    if inplace:
+        assert (m_in, tin) == (m_out, tout)
+    shapes = [(batch, m_in, s, eb_in)] + ([] if inplace else [(batch, m_out, s, eb_out)])
+    K = pick_k(shapes) if K is None else K
+    assert base_in.shape[0] == K and ref.shape[0] == K
+    assert all(wrap_distinct(b, m, s_, K, eb) for b, m, s_, eb in shapes), (shapes, K)
+    peak = peak_bytes(batch * m_in * s * eb_in, 0 if inplace else batch * m_out * s * eb_out, scratch)
+    assert peak <= CAP_80, peak
+    return K, peak, tin, tout
+
+
+def run_case(device, what, family, prec, n_eff, base_in, ref, batch, s, call, inplace, K=None, scratch=0, offset=False):
+    """One tiled case.  base_in [K][m_in] and ref [K][m_out] (numpy; complex or real each) fix the two tensors [batch][m][s];
+    call(x, out) runs the transform (out is x in place).  Prints the seconds of the call, the peak bytes and the wall time of the whole
+    case (fill, call, checks); returns (seconds of the call, peak bytes).  offset: the input starts one element past a 16-byte boundary
+    (complex64: 8-byte aligned only, the scalar fp32 kernels)."""
+    import torch
+    t_case = time.perf_counter()
+    K, peak, tin, tout = case_plan(prec, base_in, ref, batch, s, inplace, scratch, K)
+    m_in, m_out = base_in.shape[1], ref.shape[1]
+    baseT = base_tensor(base_in, prec, device)
+    if offset:
+        x = torch.empty(batch * m_in * s + 1, dtype=tin, device=device)[1:].view(batch, m_in, s)
+        assert x.data_ptr() % 16 == x.element_size() % 16
+    else:
+        x = torch.empty((batch, m_in, s), dtype=tin, device=device)
+    fill(x, baseT, K)
+    out = x if inplace else torch.full((batch, m_out, s), math.nan, dtype=tout, device=device)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    call(x, out)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"large-extent {what}: call {dt:.3f} s, peak {peak} bytes = {peak / 2**30:.1f} GiB (K = {K})")
+    try:
+        if not inplace:
+            hit = input_intact(x, baseT, K)
+            assert hit is None, (what, "the input changed at (b, k, c) =", hit)
+        check_output(out, ref, K, family, prec, n_eff, what)
+    finally:
+        del x, out, baseT
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+        print(f"large-extent {what}: case wall time {time.perf_counter() - t_case:.2f} s")
+    return dt, peak
+
+
+def peak_bytes(in_bytes, out_bytes, scratch_bytes):
+    """Buffers + the library's scratch + 1 GiB (the checks' slices, the allocator's slack, the tables)."""
+    return in_bytes + out_bytes + scratch_bytes + GIB
+
+
+# ---- base lines ----------------------------------------------------------------------------------------------------------------------------
+def complex_base(n, K, direction):
+    """-> (x [K][n], longdouble transform [K][n]) in `direction` (+1 forward, -1 unnormalised backward)"""
+    x, F = A.complex_lines(n, (K, n), 1, 11000 + n)
+    return x, (F if direction > 0 else A.reverse_bins(F, [1]))
+
+
+def real_base(n, K):
+    x, F = A.real_lines(n, K, 1, 12000 + n)
+    return x[:, :, 0], F[:, :, 0]
+
+
+def half_base(n, K):
+    X, b = A.half_spectra(n, K, 1, 13000 + n)
+    return X[:, :, 0], b[:, :, 0]
+
+
+def r2r_base(n, K, kind):
+    case = A.r2r_lines(n, K, 1, 14000 + n)
+    return case[0][:, :, 0], case[1 + A.R2R_KINDS.index(kind)][:, :, 0]
+
+
+def planes_base(n1, n2, K, direction):
+    """planes as lines of n1 * n2 points"""
+    x, F = A.complex_planes(n1, n2, K, 15000 + n1)
+    F = F if direction > 0 else A.reverse_bins(F, (1, 2))
+    return x.reshape(K, n1 * n2), F.reshape(K, n1 * n2)
+
+
+def real_planes_base(n1, n2, K):
+    x, F = A.real_planes(n1, n2, K, 16000 + n1)
+    return x.reshape(K, n1 * n2), F.reshape(K, n1 * (n2 // 2 + 1))
+
+
+def half_planes_base(n1, n2, K):
+    X, b = A.half_planes(n1, n2, K, 17000 + n1)
+    return X.reshape(K, n1 * (n2 // 2 + 1)), b.reshape(K, n1 * n2)
+
+
+# ---- mirrors of the library's chunk rules ---------------------------------------------------------------------------------------------------
+SCRATCH_CAP = 256 << 20                       # kScratchCap / kR2rScratchCap / kColsScratchCap
+CBYTES = {"f64": 16, "f32": 8}                # one complex element
+
+
+def bluestein_per_transform_bytes(M, s, prec):
+    """dfft_bluestein.hip per_transform_bytes: the padded data of one batch item, twice for a four-step M (long_fft's scratch)"""
+    return M * s * CBYTES[prec] * (2 if M > 4096 else 1)
+
+
+def bluestein_chunk(M, s, batch, prec):
+    """batch items per chunk of the multi-pass form"""
+    per = bluestein_per_transform_bytes(M, s, prec)
+    return min(batch, max(1, max(SCRATCH_CAP, per) // per))
+
+
+def bluestein_scratch(M, s, batch, prec, fused):
+    return 0 if fused else bluestein_chunk(M, s, batch, prec) * bluestein_per_transform_bytes(M, s, prec)
+
+
+def pair_units(s, batch):
+    """dfft_r2r.hip r2r_units / r2r_sp: (units, packed pairs per row of a unit) -- batch items, or row pairs at s = 1"""
+    return ((batch + 1) // 2, 1) if s == 1 else (batch, (s + 1) // 2)
+
+
+def chunk_units(n, sp, prec, units):
+    """units per chunk of the composed r2r route / items per chunk of the multi-pass real columns: packed pairs within max(256 MiB, one unit's)"""
+    zb = n * sp * CBYTES[prec]
+    return max(1, min(units, max(SCRATCH_CAP, zb) // zb))
+
+
+def chunk_bytes(n, sp, prec, nu, M, bs_fused):
+    """scratch of one chunk: the packed pairs plus the inner transform's (M: the Bluestein padded length, 0 for kinds 1 and 2)"""
+    zb = nu * n * sp * CBYTES[prec]
+    if M:
+        return zb + bluestein_scratch(M, sp, nu, prec, bs_fused)
+    return 2 * zb if n > 4096 else zb
+
+
+def composed_scratch(n, s, batch, prec, M, bs_fused, rows_pair=True):
+    """r2r_scratch_bytes (rows_pair: s = 1 pairs rows) / real_cols_scratch_bytes (s > 1) of a call that does NOT run fused"""
+    units, sp = pair_units(s, batch) if rows_pair else (batch, (s + 1) // 2)
+    return chunk_bytes(n, sp, prec, chunk_units(n, sp, prec, units), M, bs_fused)
+
+
+def ragged_batch(cu):
+    """two whole chunks and a ragged third"""
+    return 2 * cu + max(1, cu // 3)

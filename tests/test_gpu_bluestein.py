@@ -275,3 +275,29 @@ def test_distfftopt_any_length(gpu, tmp_path):
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "t0:" in r.stdout
     assert float(re.search(r"Max error:\s*([0-9.eE+-]+)", r.stdout).group(1)) < 1e-11
+
+
+# ---- the multi-pass form's batch chunks (tests/large_extent.py: tiled inputs, every line checked) ------------------------------------------
+# (n, s, prec, DFFT_BLUESTEIN_FUSED): two whole scratch chunks and a ragged third, by the mirrored chunk rule
+CHUNK_EDGE = [(4099, 5, "f64", None), (4099, 1, "f32", None), (1009, 3, "f64", "0")]
+
+
+@pytest.mark.parametrize("inplace", [True, False], ids=["in-place", "out-of-place"])
+@pytest.mark.parametrize("n,s,prec,fused_env", CHUNK_EDGE)
+def test_multi_pass_chunk_edges(gpu, n, s, prec, fused_env, inplace, monkeypatch):
+    """The chunk loop of bluestein_fft with more than one chunk: the b0 offsets of in, out and the ragged last chunk."""
+    import large_extent as LE
+    from distributedfft_amd import _lib, api
+    if fused_env is not None:
+        monkeypatch.setenv("DFFT_BLUESTEIN_FUSED", fused_env)
+    lib, code = _lib.load(), {"f64": api.F64, "f32": api.F32}[prec]
+    assert lib.dfft_bluestein_fused_applies(n, s) == 0
+    M = lib.dfft_bluestein_length(n)
+    cu = LE.bluestein_chunk(M, s, 1 << 40, prec)
+    batch = LE.ragged_batch(cu)
+    scratch = int(lib.dfft_fft1d_any_scratch_bytes(n, s, batch, code))
+    assert cu > 1 and scratch == cu * LE.bluestein_per_transform_bytes(M, s, prec)   # the library chunks at the mirrored size
+    K = LE.pick_k([(batch, n, s, LE.CBYTES[prec])])
+    x, ref = LE.complex_base(n, K, +1)
+    LE.run_case(gpu, f"any n={n} s={s} batch={batch} ({cu} per chunk) {'in place' if inplace else 'out of place'}", "bluestein", prec, n, x, ref,
+                batch, s, lambda t, o: api.fft1d_any(t, 1, api.FORWARD, out=o), inplace, scratch=scratch)

@@ -326,3 +326,56 @@ def test_neumann_poisson_solve(gpu):
     fh[0, 0, 0] = 0.0
     got = api.r2rn(fh.contiguous(), ["dct3"] * 3) / (2 * n) ** 3
     assert _rel(got.cpu().numpy(), u) < TOL["f64"]
+
+
+# ---- the composed route's batch chunks (tests/large_extent.py: tiled inputs, every line checked) ------------------------------------------------
+# (n, s, prec, kinds, environment, odd rows): two whole scratch chunks and a ragged third, by the mirrored chunk rule.  375 points: the
+# run-time-scheduled inner transform; s = 1 with an odd row count: the last pair of the last chunk is half empty; 16384: four-step inner,
+# scratch 2 zb; 1009: Bluestein inner, one launch, and -- DFFT_BLUESTEIN_FUSED=0 -- its own chunks inside an r2r chunk; 512 points are a
+# fused length that DFFT_R2R_FUSED=0 sends to the composed route.
+CHUNK_EDGE = [
+    (375, 1000, "f64", ("dct2", "dct3", "dst2", "dst3"), {}, False),
+    (375, 1, "f64", ("dct2", "dst3"), {}, True),
+    (16384, 6, "f64", ("dct3", "dst2"), {}, False),
+    (1009, 7, "f64", ("dct2", "dst3"), {}, False),
+    (1009, 7, "f64", ("dct3", "dst2"), {"DFFT_BLUESTEIN_FUSED": "0"}, False),
+    (512, 64, "f32", ("dct2", "dst3"), {"DFFT_R2R_FUSED": "0"}, False),
+]
+
+
+def _chunk_edge_params():
+    for n, s, prec, kinds, env, odd in CHUNK_EDGE:
+        for kind in kinds:
+            for inplace in (True, False):
+                tag = "".join(f"-{k}={v}" for k, v in env.items())
+                yield pytest.param(n, s, prec, kind, env, odd, inplace, id=f"n{n}-s{s}-{prec}-{kind}{tag}-{'in-place' if inplace else 'out-of-place'}")
+
+
+@pytest.mark.parametrize("n,s,prec,kind,env,odd,inplace", list(_chunk_edge_params()))
+def test_composed_route_chunk_edges(gpu, n, s, prec, kind, env, odd, inplace, monkeypatch):
+    """The chunk loop of dfft::r2r with more than one chunk: the u0 offsets, the ragged last chunk and (s = 1, odd rows) the half-empty
+    last row pair.  The plan-less entry point leases exactly r2r_scratch_bytes, so the halving loop for a short scratch has no caller
+    (DESIGN.md, "32-bit guards of the plan-less routes")."""
+    import large_extent as LE
+    from distributedfft_amd import _lib, api
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    lib, code = _lib.load(), {"f64": api.F64, "f32": api.F32}[prec]
+    vec = int(s > 1 and s % 2 == 0)
+    assert lib.dfft_r2r_fused_applies(n, s, code, api.R2R_KINDS[kind], vec) == 0
+    sp = LE.pair_units(s, 2)[1]
+    cu = LE.chunk_units(n, sp, prec, 1 << 40)
+    units = LE.ragged_batch(cu)
+    batch = 2 * units - 1 if s == 1 else units        # s = 1: units are row pairs, the last one half empty
+    assert (batch % 2 == 1) or not odd
+    M = lib.dfft_bluestein_length(n)
+    bs_fused = bool(M) and bool(lib.dfft_bluestein_fused_applies(n, sp))
+    scratch = int(lib.dfft_r2r1d_strided_scratch_bytes(n, s, batch, code, api.R2R_KINDS[kind], vec))
+    assert cu > 1 and scratch == LE.chunk_bytes(n, sp, prec, cu, M, bs_fused)   # the library chunks at the mirrored size
+    if env.get("DFFT_BLUESTEIN_FUSED") == "0":
+        assert LE.bluestein_chunk(M, sp, cu, prec) < cu                        # the inner transform takes its own chunks inside one
+    K = LE.pick_k([(batch, n, s, LE.CBYTES[prec] // 2)])
+    x, ref = LE.r2r_base(n, K, kind)
+    family = "r2r-bluestein" if api.length_kind(n) == 3 else "r2r"
+    LE.run_case(gpu, f"r2r {kind} n={n} s={s} batch={batch} ({cu} units per chunk) {'in place' if inplace else 'out of place'}", family, prec, n,
+                x, ref, batch, s, lambda t, o: api.r2r(t, kind, dim=1, out=o), inplace, scratch=scratch)
