@@ -22,6 +22,9 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 HIPCC = str(ROCM / "bin" / "hipcc")
 ARCH = "gfx950"
 NUM_INST_GROUPS = 12  # keep in sync with csrc/dfft_plans.h
+# host-side units (csrc/<name>.cpp).  All of them are compiled as HIP: the plan units take DFFT_ZY_ROW_PITCH and friends from dfft_zy.h
+HOST_UNITS = ["dfft_core", "dfft_passes", "dfft_plan", "dfft_plan_tune", "dfft_plan_r2c", "dfft_plan_conv", "dfft_batch",
+              "dfft_exchange", "dfft_bootstrap", "dfft_alloc", "dfft_trace"]
 
 # --offload-compress: the gfx950 code objects are stored zstd-compressed and unpacked by the HIP runtime when the library is loaded
 # (65 MB -> 18.5 MB per .so; process start and the benchmark unchanged, profiles/r05/experiments/compress_smoke.log)
@@ -80,41 +83,46 @@ def _deps(src: Path, seen=None):
     return seen
 
 
+def units():
+    """(source, object, extra flags) of every unit of the library."""
+    out = []
+    for g in range(NUM_INST_GROUPS):
+        out.append((CSRC / "dfft_fft_inst.hip", OBJ / f"dfft_fft_inst_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-to-complex / complex-to-real rows: the same groups of lengths, plus the dispatcher (group NUM_INST_GROUPS)
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_real.hip", OBJ / f"dfft_real_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # Bluestein (any-length) transforms: the fused kernels of the same groups of padded lengths, plus the dispatcher (group NUM_INST_GROUPS)
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_bluestein.hip", OBJ / f"dfft_bluestein_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # any-length real rows (two-for-one pairs): the fused kernels of the odd tuned lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_real_pair.hip", OBJ / f"dfft_real_pair_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real transforms along a strided axis (column pairs): the fused kernels of the tuned lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_real_cols.hip", OBJ / f"dfft_real_cols_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-to-real transforms (DCT / DST types II and III): the fused kernels of the tuned lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_r2r.hip", OBJ / f"dfft_r2r_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # real-field spectral-filter plans: the filter re-layout into the plan's private half spectrum
+    out.append((CSRC / "dfft_conv_real.hip", OBJ / "dfft_conv_real.o", []))
+    # multi-output real-field spectral-filter plans: the K-output fused kernels of each group, plus the dispatcher and the factor multiply
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_conv_multi.hip", OBJ / f"dfft_conv_multi_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    out.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
+    out.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
+    out.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))
+    out.append((CSRC / "dfft_zy.hip", OBJ / "dfft_zy.o", []))
+    for name in HOST_UNITS:
+        out.append((CSRC / f"{name}.cpp", OBJ / f"{name}.o", ["-x", "hip"]))
+    return out
+
+
 def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -> Path:
     OBJ.mkdir(parents=True, exist_ok=True)
     hdrs = _headers()
-    units = []  # (source, object, extra flags)
-    for g in range(NUM_INST_GROUPS):
-        units.append((CSRC / "dfft_fft_inst.hip", OBJ / f"dfft_fft_inst_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # real-to-complex / complex-to-real rows: the same groups of lengths, plus the dispatcher (group NUM_INST_GROUPS)
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_real.hip", OBJ / f"dfft_real_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # Bluestein (any-length) transforms: the fused kernels of the same groups of padded lengths, plus the dispatcher (group NUM_INST_GROUPS)
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_bluestein.hip", OBJ / f"dfft_bluestein_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # any-length real rows (two-for-one pairs): the fused kernels of the odd tuned lengths of each group, plus the dispatcher
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_real_pair.hip", OBJ / f"dfft_real_pair_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # real transforms along a strided axis (column pairs): the fused kernels of the tuned lengths of each group, plus the dispatcher
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_real_cols.hip", OBJ / f"dfft_real_cols_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # real-to-real transforms (DCT / DST types II and III): the fused kernels of the tuned lengths of each group, plus the dispatcher
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_r2r.hip", OBJ / f"dfft_r2r_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # real-field spectral-filter plans: the filter re-layout into the plan's private half spectrum
-    units.append((CSRC / "dfft_conv_real.hip", OBJ / "dfft_conv_real.o", []))
-    # multi-output real-field spectral-filter plans: the K-output fused kernels of each group, plus the dispatcher and the factor multiply
-    for g in range(NUM_INST_GROUPS + 1):
-        units.append((CSRC / "dfft_conv_multi.hip", OBJ / f"dfft_conv_multi_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    units.append((CSRC / "dfft_kernels.hip", OBJ / "dfft_kernels.o", []))
-    units.append((CSRC / "dfft_generic.hip", OBJ / "dfft_generic.o", []))
-    units.append((CSRC / "dfft_long.hip", OBJ / "dfft_long.o", []))
-    units.append((CSRC / "dfft_zy.hip", OBJ / "dfft_zy.o", []))
-    for name in ("dfft_plan", "dfft_exchange", "dfft_bootstrap", "dfft_alloc", "dfft_trace"):
-        units.append((CSRC / f"{name}.cpp", OBJ / f"{name}.o", ["-x", "hip"]))
 
     def compile_one(u):
         src, obj, extra = u
@@ -128,10 +136,10 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
 
     jobs = jobs or min(8, os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
-        rebuilt = list(ex.map(compile_one, units))
+        rebuilt = list(ex.map(compile_one, units()))
 
     lib = LIBDIR / LIB_NAME
-    objs = [str(u[1]) for u in units]
+    objs = [str(u[1]) for u in units()]
     if force or any(rebuilt) or _newer(lib, objs):
         _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", str(lib)] + objs +
              ["-L" + str(ROCM / "lib"), "-lrccl", "-Wl,-rpath," + str(ROCM / "lib")])

@@ -1,4 +1,5 @@
-// dfft_plan.cpp -- slab bookkeeping, plan object and the t0..t3 execute sequence behind the C-ABI (include/dfft.h).
+// dfft_plan.cpp -- C2C slab plans behind the C-ABI (include/dfft.h): create, the t0..t3 execute sequences, describe / sync / times /
+// destroy.  The plan object and what the other host units share with this one: dfft_plan_impl.h.
 //
 // Reference being replaced (behaviour, not code): /root/reference/3dmpifft_opt/include/fft_mpi_3d_api.cpp
 //   fft_mpi_init :3-39, fft_mpi_plan_dft_c2c_3d :41-141, fft_mpi_destroy_plan :143-179,
@@ -13,450 +14,14 @@
 //   * P == 1 short-circuits the exchange (the reference does a full-size self copy);
 //   * everything is enqueued on one HIP stream, stage boundaries are HIP events; host-blocking per-stage timing is
 //     opt-in (DFFT_EXEC_SYNC_STAGES) for drop-in comparability with the reference's MPI_Wtime brackets.
-#include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstdint>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <numeric>
-#include <string>
-#include <tuple>
-#include <thread>
 
-#include "dfft_bluestein.h"
-#include "dfft_conv.h"
-#include "dfft_conv_real.h"
-#include "dfft_conv_multi.h"
-#include "dfft_internal.h"
-#include "dfft_long.h"
-#include "dfft_real.h"
-#include "dfft_real_cols.h"
-#include "dfft_real_pair.h"
-#include "dfft_r2r.h"
-#include "dfft_zy.h"
+#include "dfft_plan_impl.h"
 
 namespace dfft {
 
-static thread_local std::string g_last_error;
-void set_error(const std::string& msg) { g_last_error = msg; }
-int  fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    trace_on_error(code, msg);  // communication failures print the process's last control-plane events (dfft_trace.cpp)
-    return code;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// twiddle tables
-struct TwKey {
-    int  dev, n, dtype;
-    bool operator<(const TwKey& o) const {
-        if (dev != o.dev) return dev < o.dev;
-        if (n != o.n) return n < o.n;
-        return dtype < o.dtype;
-    }
-};
-static std::mutex               g_tw_mutex;
-static std::map<TwKey, void*>   g_tw_cache;
-
-int get_twiddles(int n, int dtype, const void** table) {
-    int dev = 0;
-    DFFT_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_tw_mutex);
-    TwKey key{dev, n, dtype};
-    auto it = g_tw_cache.find(key);
-    if (it != g_tw_cache.end()) {
-        *table = it->second;
-        return DFFT_OK;
-    }
-    // e^{-2 pi i k / n} evaluated in extended precision and rounded once (the reference builds its LUT with host
-    // double cos/sin, templateFFT.cpp:5120-5141).
-    const long double two_pi = 6.283185307179586476925286766559005768L;
-    void*             dptr = nullptr;
-    if (dtype == DFFT_F64) {
-        std::vector<double> h(2 * (size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const long double a = two_pi * (long double)k / (long double)n;
-            h[2 * k] = (double)cosl(a);
-            h[2 * k + 1] = (double)(-sinl(a));
-        }
-        DFFT_HIP_TRY(hipMalloc(&dptr, h.size() * sizeof(double)));
-        DFFT_HIP_TRY(hipMemcpy(dptr, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> h(2 * (size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const long double a = two_pi * (long double)k / (long double)n;
-            h[2 * k] = (float)cosl(a);
-            h[2 * k + 1] = (float)(-sinl(a));
-        }
-        DFFT_HIP_TRY(hipMalloc(&dptr, h.size() * sizeof(float)));
-        DFFT_HIP_TRY(hipMemcpy(dptr, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    g_tw_cache[key] = dptr;
-    *table = dptr;
-    return DFFT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// launch helpers: the three passes expressed as address maps of the one FFT kernel template
-static AxisMap plain_axis(long long n, long long stride, long long cstride) {
-    AxisMap m;
-    m.blk = (int)n;
-    m.nblk = 1;
-    m.blk_stride = 0;
-    m.stride = stride;
-    m.cstride = cstride;
-    m.last_delta = 0;
-    m.sub = 1;
-    m.sub_stride = 0;
-    return m;
-}
-
-// experiment knobs: DFFT_Z_GRID / DFFT_Y_GRID / DFFT_X_GRID cap the persistent grid of the respective pass -- a tuning knob and the
-// tests' way to give a workgroup many tiles.  Read ONCE per plan (dfft_plan_create), never on the launch path: getenv is not safe
-// against a concurrent setenv of another device thread.
-static int env_grid(const char* name) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : 0;
-}
-
-static int check_launch(hipError_t e, const char* what) {
-    if (e == hipSuccess) return DFFT_OK;
-    if (e == hipErrorInvalidValue) return fail(DFFT_EUNSUPPORTED, std::string(what) + ": no gfx950 kernel for this length/precision");
-    return fail(DFFT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Where the rows of an [x][y][z] slab sit: elements between consecutive rows and between consecutive planes.  The natural
-// layout is {N2, N1*N2}; the plan's padded work buffer (dfft_plan_s::wbuf) uses {N2 + one line, N1*pitch + one line}.
-struct SlabLayout {
-    long long pitch, plane;
-};
-
-// scratch slab of the plan that is executing on this thread (long-axis plans; set by dfft_execute)
-static thread_local void* t_plan_scratch = nullptr;
-static thread_local int   t_plan_zgrid = 0;  // the executing plan's cap on its row launches' grids (dfft_plan_s::grid_z)
-
-// Bluestein axes of the plan that is executing on this thread (set by dfft_execute): the tables of its kind-3 axes, built when the
-// plan was created, and the plan's scratch for the multi-pass form -- so that an execute allocates nothing
-struct PlanBluestein {
-    std::vector<BluesteinTablesPtr> tables;
-    void*                           scratch = nullptr;
-    size_t                          bytes = 0;
-    bool                            fused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
-};
-static thread_local const PlanBluestein* t_plan_bs = nullptr;
-
-// dfft_length_kind without the range checks' cost on the hot path: single-pass lengths answer at the first test
-static int length_kind(long long n) {
-    if (n >= 1 && n <= 4096 && fft_length_supported((int)n)) return 1;
-    if (n < 1 || n >= (1ll << 30)) return 0;
-    int a, b;
-    if (long_split(n, &a, &b)) return 2;
-    return n <= kBluesteinMaxLength ? 3 : 0;
-}
-
-// dfft_real_form: 1 the half-length kernels of dfft_real.hip (n even, n/2 single-pass); 2 two-for-one pairs on an n-point single-pass
-// transform (the odd 7-smooth n <= 4096, and n = 2); 3 two-for-one pairs on the n-point four-step or Bluestein transform; 0 none
-static int real_form(long long n) {
-    if (real_length_supported(n)) return 1;
-    const int k = length_kind(n);
-    return k == 1 ? 2 : (k == 0 ? 0 : 3);
-}
-
-// ---- supported extent of the plan-less column transforms (include/dfft.h, "Supported extent") ------------------------------------------------
-// The tuned column kernels keep a thread's offsets inside one [n][width] matrix in 32 bits, in units of one V (cols_offsets_fit32,
-// dfft_kernels.h): 16 bytes for fp64 and for fp32 column pairs (even width, both pointers 16-byte aligned), 8 bytes for scalar fp32.
-// Every route that ends in those kernels is judged here, before the device is queried and before any scratch is leased.
-// DFFT_NO_PAIRS (make_pair_launch's measurement switch): fp32 columns on the scalar kernels whatever their width
-static bool pairs_disabled_env() {
-    const char* e = getenv("DFFT_NO_PAIRS");
-    return e && *e && *e != '0';
-}
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0 && !pairs_disabled_env(); }
-static bool scratch16() { return !pairs_disabled_env(); }  // the leased scratch is 16-byte aligned
-// one launch of the tuned n-point column kernels on [n][width]
-static bool tuned_cols_ok(long long n, long long width, int dtype, bool pairs) {
-    if (width + kTileColsMax > (1ll << 31)) return false;  // column indices are ints, a ragged last tile counts up to one tile further
-    const bool paired = dtype == DFFT_F32 && pairs && width % 2 == 0;
-    return cols_offsets_fit32(n, paired ? width / 2 : width);
-}
-// long_fft on [n][s], n = N1 * N2: pass A runs N1-point columns of width N2 * s from `in` into the scratch, pass B N2-point columns of
-// width s in place on the scratch (s = 1: rows)
-static bool four_step_ok(long long n, long long s, int dtype, bool in16) {
-    int N1 = 0, N2 = 0;
-    if (!long_split(n, &N1, &N2)) return false;
-    return tuned_cols_ok(N1, (long long)N2 * s, dtype, in16 && scratch16()) && (s == 1 || tuned_cols_ok(N2, s, dtype, scratch16()));
-}
-// dfft_fft1d_cols on [n][width], kinds 1 and 2
-static bool cols_extent_ok(long long n, long long width, int dtype, bool in16, bool out16) {
-    if (width + kTileColsMax > (1ll << 31)) return false;
-    if (n > 4096) return four_step_ok(n, width, dtype, in16);
-    return !fft_length_tuned((int)n) || tuned_cols_ok(n, width, dtype, in16 && out16);  // run-time-scheduled kernel: 64-bit offsets
-}
-// bluestein_fft on [n][s]: one launch, or pad -> M-point transforms in place on the scratch -> finish.  (The pad buffer of a chunk and,
-// M > 4096, long_fft's scratch behind it are 16-byte aligned for fp32 only where M * s is even.)
-static bool bluestein_extent_ok(long long n, long long s, int dtype) {
-    if (s == 1 || bluestein_runs_fused(n, s, bluestein_fused_env())) return true;
-    const long long M = bluestein_padded_length(n);
-    if (M <= 4096) return tuned_cols_ok(M, s, dtype, scratch16());
-    return four_step_ok(M, s, dtype, scratch16() && (M * s) % 2 == 0);
-}
-// n-point transforms along the middle axis of [batch][n][s] (dfft_fft1d_any, and the inner transforms of the real and r2r composed routes)
-static bool any_extent_ok(long long n, long long s, int dtype, bool in16, bool out16) {
-    if (s == 1) return true;  // rows: tile bases only
-    return length_kind(n) == 3 ? (s + kTileColsMax <= (1ll << 31) && bluestein_extent_ok(n, s, dtype)) : cols_extent_ok(n, s, dtype, in16, out16);
-}
-static std::string extent_message(const char* fn, long long n, long long s) {
-    return std::string(fn) + ": n = " + std::to_string(n) + ", width = " + std::to_string(s) +
-           ": a column pass would span 2^32 or more 16-byte (fp32, odd width or unaligned: 8-byte) units, or width > 2^31 - 64";
-}
-
-// Length-n Bluestein transforms of data[batch][n][s] (dfft_bluestein.hip): with the executing plan's tables and scratch, or -- plan-less
-// callers -- the cached tables and the per-(device, stream) scratch lease of the four-step transforms
-static int bluestein_pass(const void* in, void* out, long long n, long long s, long long batch, int dtype, int dir, double scale,
-                          hipStream_t st) {
-    if (const PlanBluestein* pb = t_plan_bs) {
-        for (const auto& t : pb->tables)
-            if (t->n == n && t->dtype == dtype && t->dir == dir) return bluestein_fft(*t, in, out, s, batch, scale, pb->fused, pb->scratch, pb->bytes, st);
-        return fail(DFFT_EINVAL, "Bluestein pass: the plan has no tables for length " + std::to_string(n));
-    }
-    BluesteinTablesPtr t;
-    int                rc = bluestein_tables(n, dtype, dir, &t);
-    if (rc) return rc;
-    const bool       fused = bluestein_fused_env();
-    const size_t     need = bluestein_scratch_bytes(*t, s, batch, fused);
-    LongScratchLease lease = nullptr;
-    void*            scr = nullptr;
-    if (need) {
-        scr = long_scratch(need, st, &lease);
-        if (!scr) return fail(DFFT_EHIP, "Bluestein pass: cannot allocate the scratch buffer");
-    }
-    rc = bluestein_fft(*t, in, out, s, batch, scale, fused, scr, need, st);
-    long_scratch_release(lease);
-    return rc;
-}
-
-// contiguous rows: `rows` FFTs of length n; row pitch n, or (lin/lout given) rows_per_plane rows per plane in the given layouts
-static int fft_rows(const void* in, void* out, int n, long long rows, int dtype, int dir, hipStream_t s,
-                    long long first_row = 0, int hints = 0, double scale = 1.0, const SlabLayout* lin = nullptr,
-                    const SlabLayout* lout = nullptr, long long rows_per_plane = 0, void* long_scratch_buf = nullptr, int grid_limit = 0) {
-    if (length_kind(n) == 3) {  // Bluestein (DFFT_PLAN_ANY_LENGTH plans, which run un-fused): plain contiguous rows only
-        if (lin || lout) return fail(DFFT_EINVAL, "fft_rows: Bluestein axes use the natural layout");
-        if (rows <= 0) return DFFT_OK;
-        const size_t off = (size_t)first_row * n * elem_bytes(dtype);
-        return bluestein_pass((const char*)in + off, (char*)out + off, n, 1, rows, dtype, dir, scale, s);
-    }
-    if (n > 4096) {  // beyond the single-pass range: four-step decomposition (dfft_long.hip), plain contiguous rows only
-        if (lin || lout) return fail(DFFT_EINVAL, "fft_rows: long axes use the natural layout");
-        if (rows <= 0) return DFFT_OK;
-        const size_t off = (size_t)first_row * n * elem_bytes(dtype);
-        void*        scr = long_scratch_buf ? long_scratch_buf : t_plan_scratch;
-        const bool   own = !scr;
-        LongScratchLease lease = nullptr;
-        if (own) scr = long_scratch((size_t)rows * n * elem_bytes(dtype), s, &lease);
-        if (!scr) return fail(DFFT_EHIP, "fft_rows: cannot allocate the scratch buffer of the four-step transform");
-        const int rc = long_fft((const char*)in + off, (char*)out + off, n, 1, rows, dtype, dir, scale, scr, s);
-        long_scratch_release(lease);
-        return rc;
-    }
-    const void* tw = nullptr;
-    int         rc = get_twiddles(n, dtype, &tw);
-    if (rc) return rc;
-    FftLaunch L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.n = n;
-    L.dir = dir;
-    L.cols = 0;
-    L.in = in;
-    L.out = out;
-    L.tw = tw;
-    L.imap = L.omap = plain_axis(n, 1, 0);
-    L.itile = L.otile = TileMap{(long long)n, 0};
-    L.ntiles = rows;
-    L.a_first = first_row;
-    L.hints = hints;
-    L.scale = scale;
-    L.tiles_per_a = 1;
-    L.ncols = 1;
-    if (lin && lout && rows_per_plane > 0) {  // tile = (plane a, row b): base = a * plane + b * pitch (CB = 1 for rows)
-        if (first_row % rows_per_plane != 0 || rows_per_plane >= (1ll << 31)) return fail(DFFT_EINVAL, "fft_rows: chunk is not whole planes");
-        L.itile = TileMap{lin->plane, lin->pitch};
-        L.otile = TileMap{lout->plane, lout->pitch};
-        L.tiles_per_a = (int)rows_per_plane;
-        L.a_first = first_row / rows_per_plane;
-    }
-    L.grid_limit = grid_limit ? grid_limit : t_plan_zgrid;  // (dfft_plan_s::grid_z: DFFT_Z_GRID when the plan was created)
-    return check_launch(launch_fft(L, s), "fft_rows");
-}
-
-}  // namespace dfft
-
-using namespace dfft;
-
-// ---------------------------------------------------------------------------------------------------------------
-struct dfft_plan_s {
-    long long   N[3];
-    int         dtype, direction;
-    int         P, me;
-    unsigned    flags;
-    bool        inplace, is_last;
-    double      scale = 1.0;  // folded into the X pass (dfft_plan_set_scale)
-    bool        exch = false;  // t2 runs: P > 1, or DFFT_FORCE_EXCHANGE=1 with an RCCL communicator (single-GPU tests)
-    long long   max_count;
-    Slab        sx, sy;       // X slabs (before), Y slabs (after)
-    long long   xs, ys;       // this device's extents
-    void *      in, *out, *buf1, *buf2;
-    dfft_comm_t comm;
-    int         device;
-    hipStream_t stream;
-    hipEvent_t  ev[6];  // [0..4] stage boundaries, [5] between the two FFT kernels of the YZ stage
-    double      host_t[4];
-    bool        host_timed;
-    bool        timed = true;  // the last execute recorded its stage events (false: DFFT_EXEC_NO_TIMING)
-    ExchangeDesc xd;
-    ExchangeDesc xd2;        // DFFT_PLAN_NATURAL: the second (Y -> X) exchange
-    long long   chunk_planes;  // planes per Z+Y chunk (Infinity-Cache blocking); 0 = whole slab in one launch pair
-    // DFFT_PLAN_OVERLAP (forward, P > 1): exchange parts on a second stream behind the plane-chunked Z+Y passes
-    long long               part_planes = 0;  // planes per exchange part, identical on every rank; 0 = overlap off
-    hipStream_t             stream2 = nullptr;
-    void*                   rbuf = nullptr;  // dedicated receive buffer of the overlapped exchange
-    hipEvent_t              join_ev = nullptr;
-    std::vector<hipEvent_t> part_ev;
-    // t2/t3 overlap inside DFFT_PLAN_OVERLAP: the Y range of every destination is cut into `ycuts` sub-blocks; the last
-    // X-plane part is exchanged sub-block by sub-block and the X pass of sub-block k runs while sub-block k+1 is in flight
-    int                     ycuts = 1;
-    std::vector<hipEvent_t> y_ev;
-    // Padded work buffer for the Z <-> Y (and, on a single GPU, Y <-> X) intermediate of the fused pipeline: rows one
-    // cache line longer than N2 and planes one more line apart, so that the column kernels' 128-byte segments -- N1 of
-    // them one row pitch apart (Y pass), N0 of them one plane apart (X pass) -- do not all fall on the same memory
-    // channels.  With power-of-two extents the natural strides (8 KiB, 4 MiB at 512^3 fp64) cost 11-15 % of the passes'
-    // data rate (tools/membench4.hip, profiles/r02/README.md section 1).  Caller-visible buffers keep the reference layouts.
-    void*                   wbuf = nullptr;
-    SlabLayout              wl{0, 0};
-    // an axis beyond the single-pass range (> 4096 points, dfft_long.hip): the plan runs the un-fused stage structure (only
-    // contiguous rows and natural-layout columns need the four-step form then) and owns the scratch slab it needs
-    bool                    long_axis = false;
-    void*                   lbuf = nullptr;
-    // axes of dfft_length_kind 3 (DFFT_PLAN_ANY_LENGTH): Bluestein transforms on the un-fused structure, tables and scratch owned here
-    PlanBluestein           bs;
-    // Placement of the hand-over buffer (dfft_plan_tune).  The X pass runs 5-8 % faster when the buffer it reads and the
-    // buffer it writes lie in different regions of the device's physical memory (regions are 4 ... 70 GiB long, consecutive
-    // allocations usually share one; profiles/r03/README.md section 1, tools/xprobe.hip), so tuning times the X-pass kernel
-    // alone on candidate allocations made one after the other -- all kept alive, so that each moves the next one on -- until
-    // one behaves differently, and keeps the one on which it ran fastest.
-    // t0 as one persistent launch (dfft_zy.hip) instead of two launches per cache chunk: single-GPU fused plans in fp64 whose Y and
-    // Z lengths the kernel is built for.  zy_ctl: its control block (ticket counter, per-plane counters, error word).
-    ZyCtl*                  zy_ctl = nullptr;
-    // the plan's shape and flags select the one-launch stage (whether or not THIS device could allocate its control block): the same
-    // on every device of a communicator, so it -- and not zy_ctl -- decides who takes part in the agreement round of dfft_execute
-    bool                    zy_eligible = false;
-    unsigned*               zy_err = nullptr;   // pinned host word the kernel writes ZY_ERR_* to when it gives up (read without a copy)
-    unsigned                zy_spin_polls = 0;  // bound of a consumer unit's wait (polls; DFFT_ZY_SPIN_POLLS)
-    int                     zy_fault = 0;       // DFFT_ZY_FAULT=n (test hook): launch number n of the stage waits for producers that never come
-    unsigned                zy_launches = 0;
-    bool                    zy_on = false;
-    unsigned                zy_ticket = 0;  // value of the control block's ticket counter when the next launch starts
-    unsigned                zy_execs = 0, zy_cur = 0;  // executes that have used the stage; index of the current one (per-plane counters)
-    // overlapped forward plans: ONE launch of the stage over the whole slab that counts, per X-plane part, the column units whose results
-    // are in memory (dfft_zy.hip, SIG); the exchange stream waits for a part's count and ships it while the launch computes the next part
-    unsigned*               zy_part_done = nullptr;    // device: one counter per part (never reset: targets run on from execute to execute)
-    unsigned                zy_sig_execs = 0;
-    bool                    zy_lazy = false;           // lazy-publish form of the one-launch kernel (un-packed launches; DFFT_ZY_LAZY=0: eager)
-    bool                    zy_inv_rows_first = true;  // backward single-GPU plans: inverse stage rows first (DFFT_ZY_INV_ROWS_FIRST=0: columns first)
-    int                     x_hints = 0;               // DFFT_X_VARIANT when the plan was created: FFT_HINT_HALF_PREFETCH / _EARLY_WAIT
-    int                     grid_x = 0, grid_y = 0, grid_z = 0;  // DFFT_X_GRID / DFFT_Y_GRID / DFFT_Z_GRID when the plan was created (0 = no cap)
-    // Rows of the exchange buffers rotated by rot_elems elements per X plane (RotMap, dfft_kernels.h): P > 1 fused plans whose
-    // received planes are a power-of-two distance apart.  0 = off.
-    int                     rot_elems = 0;
-    // real-to-complex / complex-to-real plans (dfft_plan_create_r2c): N[2] is the COMPLEX width n2/2 + 1 -- what the Y pass, the exchange
-    // and the X pass see -- and n2r the real length.  The Z rows run into / out of the plan's own complex intermediate cbuf ([xs][N1][cl.pitch],
-    // rows padded to whole cache lines; also the send buffer of the backward exchange): an R2C row is wider on output than on input.
-    bool                    r2c = false;
-    long long               n2r = 0;
-    void*                   cbuf = nullptr;
-    SlabLayout              cl{0, 0};
-    // dfft_plan_create_r2c_any: the form of the real axis (dfft_real_form; 1 = exactly dfft_plan_create_r2c's plan) and, forms 2 / 3, the
-    // two-for-one rows' Bluestein tables (Bluestein n2r only) and scratch, sized for one cache chunk of rows (dfft_real_pair.hip)
-    bool                    real_any = false;
-    int                     real_form = 1;
-    BluesteinTablesPtr      rtab;
-    bool                    rfused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
-    void*                   rscratch = nullptr;
-    size_t                  rscratch_bytes = 0;
-    // spectral-filter plans (dfft_plan_create_conv).  The handle the caller holds has `conv` set and owns two HALF plans: a forward plan
-    // that stops in front of its X pass and a backward plan that starts behind its inverse X pass (conv_half; the stage code of
-    // execute_forward / execute_backward, minus launch_x), which share the stream and the hand-over buffer; the X stage in between is
-    // dfft_conv.hip's.  conv_no_rot: a half plan whose X stage takes the multi route keeps plain rows in its exchange buffers (the in-place
-    // C2C column kernels exist for plain rows only).  borrowed: stream and hand-over buffer belong to the other half.
-    // Real-field plans (dfft_plan_create_conv_real) are the same handle over an R2C and a C2R half plan (create_r2c / execute_r2c with
-    // conv_half set: no X pass, nothing captured at plan time, N[2] = the plan's private complex width Nc >= n2r/2 + 1); there `borrowed`
-    // covers the stream and the complex intermediate cbuf.
-    struct ConvState*       conv = nullptr;
-    bool                    conv_half = false, conv_no_rot = false, borrowed = false;
-    bool                    own_cbuf = false;  // a borrowed half of a multi-output plan that owns its intermediate all the same
-    std::vector<float>      w_ms;            // report: X-pass time of every candidate tried (w_ms[w_kept] is the kept one)
-    int                     w_kept = -1;
-    float                   w_final_ms = 0.f;  // the kept candidate re-timed after the others were freed
-};
-
-// state of a spectral-filter plan (dfft_plan_s::conv)
-struct ConvState {
-    dfft_plan_s *f = nullptr, *b = nullptr;  // the forward / backward half plans
-    void*        sbuf = nullptr;             // send buffer of the forward exchange (plans with a communicator)
-    void*        filt = nullptr;             // the filter copy, in the hand-over slab's physical layout
-    size_t       filt_bytes = 0;
-    int          kind = -1;                  // DFFT_FILTER_*; -1: no filter yet
-    bool         fused = false;              // xconv_cols_kernel (else the multi route)
-    ConvLaunch   L{};                        // the X stage's slab: buffers, strides, rotation
-    long long    slab_elems = 0;             // elements of the slab, padding included (= elements of the filter copy)
-    double       x_host = 0;                 // host-timed X stage of the last DFFT_EXEC_SYNC_STAGES execute
-    bool         real = false;               // dfft_plan_create_conv_real: R2C / C2R halves, the slab is the half spectrum at width L.ncols
-    long long    nh = 0;                     // real-field plans: N2/2 + 1, the bins per row the caller's filter has
-    // multi-output real-field plans (dfft_plan_create_conv_real_multi): nout > 0 outputs, one C2R half per output (bk[0] == b), the slabs
-    // the X stage writes (M.out[0] == L.in; M.out[k >= 1]: the intermediate of bk[k] at P = 1, a send buffer of the plan's own -- xslab[k] --
-    // at P > 1) and the factor tables: `fact` holds a table of ones and, per output, na + nrow + L.ncols elements (a, this device's part
-    // of b, zero-padded c); M.ax / by / cz point at the ones until dfft_conv_set_factors gives something else
-    int           nout = 0;
-    dfft_plan_s*  bk[CONV_MAX_OUTPUTS] = {};
-    void*         xslab[CONV_MAX_OUTPUTS] = {};
-    void*         fact = nullptr;
-    long long     fa = 0, fb = 0;            // elements reserved for a and b per output (even: every table starts on a 16-byte boundary)
-    ConvMultiArgs M{};
-    bool          unit[CONV_MAX_OUTPUTS] = {};  // all three factors of output k are ones
-    int           backs() const { return nout > 0 ? nout : 1; }
-    dfft_plan_s*  back(int k) const { return nout > 0 ? bk[k] : b; }
-};
-static int conv_execute(dfft_plan_s* p, unsigned exec_flags);
-static int conv_describe(const dfft_plan_s* p, char* buf, int len);
-static int conv_sync(dfft_plan_s* p);
-static int conv_stage_times(dfft_plan_s* p, double t[4]);
-static int conv_destroy(dfft_plan_s* p);
-// A half plan of dfft_plan_create_conv_real: the plan's complex width, and the forward half whose stream and intermediate the backward
-// half borrows (nullptr: this IS the forward half)
-// Multi-output plans: C2R half `output` >= 1 borrows the stream but has a receive buffer of its own (the output index goes into the pool
-// key: peers push into it while this rank may still unpack the previous output's) and, with own_cbuf, an intermediate of its own -- slab
-// `output` of the X stage at P = 1
-struct R2cHalf {
-    long long    nc;
-    dfft_plan_s* share;
-    int          output = 0;
-    bool         own_cbuf = false;
-};
-// Elements of the two receive buffers of a real-field spectral-filter plan at complex width nc -- the forward one holds [N0][ys][nc], the
-// backward one the packed [q][xs][yl_q][nc] -- as a bound that is the same on every rank (pooled buffers are matched by size)
-static long long conv_real_recv_count(long long n0, long long n1, long long nc, int P) {
-    const Slab sx = make_slab(n0, P), sy = make_slab(n1, P);
-    return std::max(n0 * sy.blk, (long long)P * sx.blk * sy.blk) * nc;
-}
-
-static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any, const R2cHalf* half = nullptr);
-
-static int fill_exchange(dfft_plan_s* p, ExchangeDesc& x, int direction) {
+int fill_exchange(dfft_plan_s* p, ExchangeDesc& x, int direction) {
     const int       P = p->P, me = p->me;
     const long long n2 = p->N[2];
     x.dtype = p->dtype;
@@ -512,10 +77,8 @@ static void packed_map(const dfft_plan_s* p, AxisMap* packed, TileMap* tile) {
     *tile = TileMap{ysub * n2, 1};
 }
 
-// Y pass.  Natural side: [xs][N1][N2].  Packed side: [d][xs][yl_d][N2].
-// lay_in / lay_out: layout of the natural side(s) (nullptr = {N2, N1*N2}); ignored for a packed side.
-static int launch_y(dfft_plan_s* p, const void* in, void* out, bool packed_side_is_out, bool use_packed, long long x0,
-                    long long nx, int hints = 0, const SlabLayout* lay_in = nullptr, const SlabLayout* lay_out = nullptr) {
+int launch_y(dfft_plan_s* p, const void* in, void* out, bool packed_side_is_out, bool use_packed, long long x0, long long nx, int hints,
+             const SlabLayout* lay_in, const SlabLayout* lay_out) {
     const int       n1 = (int)p->N[1];
     const long long n2 = p->N[2];
     if (length_kind(n1) == 3) {  // Bluestein: natural layout on both sides only (such plans run un-fused)
@@ -574,12 +137,7 @@ static int launch_y(dfft_plan_s* p, const void* in, void* out, bool packed_side_
     return check_launch(launch_fft(L, p->stream), "Y pass");
 }
 
-// X pass.  Slab side: [N0][ys][N2] (x slowest).  Transposed side: [ys][N2][N0] (kx fastest).
-// keep_slab: store [x][ys][N2] again instead of the transposed [ys][N2][kx] (natural-order plans)
-// ys_part > 0: only a [N0][ys_part][N2] sub-slab (in/out already point at it)
-// slab_lay: layout of the slab side when it is the plan's padded work buffer (single GPU: ys == N1), else [x][ys][N2]
-static int launch_x(dfft_plan_s* p, const void* in, void* out, bool keep_slab = false, long long ys_part = 0,
-                    const SlabLayout* slab_lay = nullptr) {
+int launch_x(dfft_plan_s* p, const void* in, void* out, bool keep_slab, long long ys_part, const SlabLayout* slab_lay) {
     const int       n0 = (int)p->N[0];
     const long long n2 = p->N[2];
     const long long ys = ys_part > 0 ? ys_part : p->ys;
@@ -626,41 +184,27 @@ static int launch_x(dfft_plan_s* p, const void* in, void* out, bool keep_slab = 
     return check_launch(launch_fft(L, p->stream), "X pass");
 }
 
-namespace {
-struct StageClock {
-    dfft_plan_s* p;
-    bool         sync;
-    int          idx = 0;
-    std::chrono::steady_clock::time_point t;
-    int begin() {
-        if (sync) {
-            DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
-            t = std::chrono::steady_clock::now();
-        } else if (p->timed) {
-            DFFT_HIP_TRY(hipEventRecord(p->ev[0], p->stream));
-        }
-        return DFFT_OK;
+int StageClock::begin() {
+    if (sync) {
+        DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
+        t = std::chrono::steady_clock::now();
+    } else if (p->timed) {
+        DFFT_HIP_TRY(hipEventRecord(p->ev[0], p->stream));
     }
-    int end_stage() {
-        if (sync) {
-            DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
-            auto now = std::chrono::steady_clock::now();
-            p->host_t[idx] = std::chrono::duration<double>(now - t).count();
-            t = now;
-        } else if (p->timed) {
-            DFFT_HIP_TRY(hipEventRecord(p->ev[idx + 1], p->stream));
-        }
-        ++idx;
-        return DFFT_OK;
+    return DFFT_OK;
+}
+int StageClock::end_stage() {
+    if (sync) {
+        DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
+        auto now = std::chrono::steady_clock::now();
+        p->host_t[idx] = std::chrono::duration<double>(now - t).count();
+        t = now;
+    } else if (p->timed) {
+        DFFT_HIP_TRY(hipEventRecord(p->ev[idx + 1], p->stream));
     }
-};
-}  // namespace
-
-#define DFFT_TRY(stmt)        \
-    do {                      \
-        int rc_ = (stmt);     \
-        if (rc_) return rc_;  \
-    } while (0)
+    ++idx;
+    return DFFT_OK;
+}
 
 // Planes per phase of the one-launch YZ stage for a slab (or part) of nx planes: one that fits the 256 MiB Infinity Cache is ONE
 // phase; larger ones are cut into equal phases of at most 230 MiB -- head-room instead of the largest possible size, see
@@ -751,7 +295,7 @@ static int launch_zy_stage(dfft_plan_s* p, const void* src, void* w, long long w
 // an execute is queued, after a drained one, in sync / stage_times / destroy.  The word is sticky on the device side (every later
 // launch on the block returns at once), so nothing computed after the failure can pass for a result; the stage is switched off for
 // good here and the plan continues on two launches per chunk.
-static int zy_check(dfft_plan_s* p) {
+int zy_check(dfft_plan_s* p) {
     if (!p->zy_on || !p->zy_err) return DFFT_OK;
     const unsigned err = *(volatile unsigned*)p->zy_err;
     if (err == 0) return DFFT_OK;
@@ -1063,486 +607,81 @@ static int execute_backward(dfft_plan_s* p, bool sync) {
     return DFFT_OK;
 }
 
-// ---- real-to-complex / complex-to-real plans -------------------------------------------------------------------------------------
-// The Z rows of planes [x0, x0 + nx): R2C real slab `in` ([x][N1][n2r] reals) -> intermediate, or C2R intermediate -> real slab `out`.
-static int real_rows(dfft_plan_s* p, const void* in, void* out, int dir, long long x0, long long nx) {
-    const long long n1 = p->N[1];
-    const size_t    cs = elem_bytes(p->dtype), rs = cs / 2;
-    if (p->real_form != 1) {  // two-for-one pairs (rows pair up across plane boundaries)
-        RealPairLaunch R;
-        std::memset(&R, 0, sizeof(R));
-        R.dtype = p->dtype;
-        R.n = p->n2r;
-        R.dir = dir;
-        const size_t roff = (size_t)x0 * n1 * p->n2r * rs, coff = (size_t)x0 * p->cl.plane * cs;
-        R.in = (const char*)in + (dir > 0 ? roff : coff);
-        R.out = (char*)out + (dir > 0 ? coff : roff);
-        R.rows = nx * n1;
-        R.rows_per_plane = n1;
-        R.rpitch = p->n2r;
-        R.rplane = n1 * p->n2r;
-        R.cpitch = p->cl.pitch;
-        R.cplane = p->cl.plane;
-        return real_pair_rows(R, p->rtab.get(), p->rfused, p->rscratch, p->rscratch_bytes, p->stream);
-    }
-    RealLaunch      L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = p->dtype;
-    L.n2 = (int)p->n2r;
-    L.dir = dir;
-    const size_t roff = (size_t)x0 * n1 * p->n2r * rs, coff = (size_t)x0 * p->cl.plane * cs;
-    L.in = (const char*)in + (dir > 0 ? roff : coff);
-    L.out = (char*)out + (dir > 0 ? coff : roff);
-    L.rows = nx * n1;
-    L.rows_per_plane = n1;
-    L.rpitch = p->n2r;
-    L.rplane = n1 * p->n2r;
-    L.cpitch = p->cl.pitch;
-    L.cplane = p->cl.plane;
-    L.scale = 1.0;  // dfft_plan_set_scale: folded into the X pass, as in C2C plans
-    return check_launch(launch_real_rows(L, p->stream), dir > 0 ? "R2C rows" : "C2R rows");
-}
-
-// Forward: R2C rows -> intermediate, Y columns (in place, or packing into the send buffer `out`) per cache chunk | exchange into
-// bufferDev1 | X pass -> out.  Backward: inverse X pass (into the intermediate, or the send buffer = the intermediate) | exchange into
-// bufferDev1 | per cache chunk: Y columns (in place, or unpacking bufferDev1 into the intermediate), then C2R rows -> out -- Z last, as
-// numpy's irfftn (inverse C2C along X and Y, then C2R along Z).
-static int execute_r2c(dfft_plan_s* p, bool sync) {
-    StageClock      clk{p, sync};
-    DFFT_TRY(clk.begin());
-    const void*     src = (p->flags & DFFT_PLAN_INPUT_FROM_IN) ? p->in : p->buf1;
-    const long long cp = p->chunk_planes > 0 ? p->chunk_planes : p->xs;
-    const bool      chunked = cp < p->xs;
-    const SlabLayout* lc = &p->cl;
-    if (p->direction == DFFT_FORWARD) {
-        for (long long x0 = 0; x0 < p->xs; x0 += cp) {
-            const long long nx = std::min(cp, p->xs - x0);
-            DFFT_TRY(real_rows(p, src, p->cbuf, +1, x0, nx));
-            if (p->exch) DFFT_TRY(launch_y(p, p->cbuf, p->buf2, true, true, x0, nx, chunked ? FFT_HINT_STREAM_OUT : 0, lc));
-            else DFFT_TRY(launch_y(p, p->cbuf, p->cbuf, true, false, x0, nx, 0, lc, lc));
-        }
-        DFFT_TRY(clk.end_stage());
-        DFFT_TRY(clk.end_stage());  // t1 folded into t0
-        if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
-        DFFT_TRY(clk.end_stage());
-        // (half plans of a real-field spectral-filter plan: the X stage works in place on what t0 / t2 left -- conv_x_stage -- and has
-        // left its result where the inverse X pass would have: the intermediate, or the send buffer of the backward exchange)
-        if (!p->conv_half) DFFT_TRY(launch_x(p, p->exch ? p->buf1 : p->cbuf, p->buf2, false, 0, p->exch ? nullptr : lc));
-        DFFT_TRY(clk.end_stage());
-        return DFFT_OK;
-    }
-    if (!p->conv_half) DFFT_TRY(launch_x(p, src, p->cbuf, false, 0, p->exch ? nullptr : lc));
-    DFFT_TRY(clk.end_stage());
-    if (p->exch) DFFT_TRY(comm_exchange(p->comm, p->xd, p->stream));
-    DFFT_TRY(clk.end_stage());
-    DFFT_TRY(clk.end_stage());  // unpack folded into the Y pass
-    for (long long x0 = 0; x0 < p->xs; x0 += cp) {
-        const long long nx = std::min(cp, p->xs - x0);
-        if (p->exch) DFFT_TRY(launch_y(p, p->buf1, p->cbuf, false, true, x0, nx, chunked ? FFT_HINT_STREAM_IN : 0, nullptr, lc));
-        else DFFT_TRY(launch_y(p, p->cbuf, p->cbuf, false, false, x0, nx, 0, lc, lc));
-        DFFT_TRY(real_rows(p, p->cbuf, p->buf2, -1, x0, nx));
-    }
-    DFFT_TRY(clk.end_stage());
+// ---- plan creation: what the four kinds of plan share -------------------------------------------------------------------------
+int check_plan_args(const std::string& fn, const void* plan, const void* in, const void* out, long long n0, long long n1, long long n2, int dtype,
+                    dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, const PlanArgRules& rules) {
+    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
+    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
+    if (!valid_dtype(dtype)) return fail(DFFT_EINVAL, fn + ": dtype");
+    if (rules.direction && !valid_direction(*rules.direction)) return fail(DFFT_EINVAL, fn + ": direction");
+    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
+    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
+    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
+    if (rules.out_of_place && (out == nullptr || out == in)) return fail(DFFT_EINVAL, fn + ": " + rules.out_of_place);
+    if (flags & ~rules.flags_allowed) return fail(DFFT_EUNSUPPORTED, fn + ": " + rules.flags_text);
     return DFFT_OK;
 }
 
-// Placement of the RECEIVE buffer of a P > 1 forward plan -- the P > 1 twin of dfft_plan_tune.  The X pass reads
-// the receive buffer and writes the caller's `out`; like the hand-over buffer of a single-GPU plan the two normally come out of the
-// same region of physical memory, the slow mode of any kernel that streams from one buffer into another.  The
-// peers push into this buffer, so it has to be chosen BEFORE it is registered with the communicator: here, inside dfft_plan_create,
-// for out-of-place fused forward plans whose received slab is larger than the Infinity Cache, and only while the buffer is still
-// unknown to the peers (a pooled buffer of an IPC communicator was placed when its first plan was created).  Same walk as
-// dfft_plan_tune: the plan's X-pass launches alone on the current buffer and on fresh allocations made one after the other, all
-// kept until the end; stops at a confirmed 3.5 % gap; the probes write garbage into `out`, whose contents are set aside and put back.
-// Every rank walks on its own (the registration that follows is the collective).
-// Measured (round 5, per rank of 512^3 fp64 with the exchange switched off, profiles/r05/README.md section 6): X pass at P = 2 0.373 ->
-// 0.341 ms (-8 %), at P = 4 0.176 vs 0.177 (nothing: no candidate in 5-8 differs from the first by more than noise once the pass runs
-// inside the pipeline), config 4's rank at P = 8: 128 candidates within 3 % of each other.  A gain in one shape, plan-time cost and a
-// transient footprint of many slabs in all of them, on a path that has never run on real links: OPT-IN, DFFT_TUNE_RECV=1 (at most
-// DFFT_TUNE_TRIES, default 24, candidates).
-// Bytes of a buffer that is (or may be) registered as a receive buffer: the larger of the last / not-last device's element count, so
-// that every rank of a communicator asks its pool for the same size (comm_recv_alloc: pooled entries are matched by size).
-static size_t recv_buffer_bytes(const dfft_plan_s* p) {
-    const long long a = dfft_max_count(p->N[0], p->N[1], p->N[2], p->P, 0), b = dfft_max_count(p->N[0], p->N[1], p->N[2], p->P, 1);
-    return (size_t)std::max(a, b) * elem_bytes(p->dtype);
-}
-static int place_recv_buffer(dfft_plan_s* p) {
-    const char* te = getenv("DFFT_TUNE_RECV");
-    if (!(te && *te == '1')) return DFFT_OK;
-    if (!p->exch || p->P < 2 || p->direction != DFFT_FORWARD || p->inplace || p->long_axis || (p->flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL)))
-        return DFFT_OK;
-    const size_t eb = elem_bytes(p->dtype);
-    if ((size_t)p->N[0] * p->ys * p->N[2] * eb <= ((size_t)256 << 20)) return DFFT_OK;  // a cache-resident slab has no placement
-    const bool is_rbuf = p->xd.recvbuf == p->rbuf && p->rbuf;
-    void*      cur = is_rbuf ? p->rbuf : p->buf1;
-    if (!cur || !comm_recv_is_fresh(p->comm, cur)) return DFFT_OK;
-    const size_t bytes = (size_t)p->max_count * eb;
-    DFFT_HIP_TRY(hipDeviceSynchronize());
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        return DFFT_OK;
-    }
-    const bool  alone = total_b > 0 && free_b >= total_b / 10 * 9;
-    int         max_tries = 24, pct = alone ? 70 : 25;
-    const char* mt = getenv("DFFT_TUNE_TRIES");
-    if (mt && atoi(mt) > 0) max_tries = atoi(mt);
-    const char* pe = getenv("DFFT_TUNE_MEM_PCT");
-    if (pe && atoi(pe) >= 1 && atoi(pe) <= 90) pct = atoi(pe);
-    const size_t budget = free_b / 100 * (size_t)pct;
-    void*        saved_out = nullptr;
-    if (2 * bytes > budget || hipMalloc(&saved_out, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return DFFT_OK;
-    }
-    if (hipMemcpyAsync(saved_out, p->buf2, bytes, hipMemcpyDeviceToDevice, p->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(saved_out);
-        return DFFT_OK;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        (void)hipStreamSynchronize(p->stream);
-        (void)hipFree(saved_out);
-        return DFFT_OK;
-    }
-    const long long ysub = p->ys / std::max(1, p->ycuts);
-    const size_t    sub = (size_t)p->N[0] * ysub * p->N[2] * eb;
-    auto x_launches = [&](void* cand) -> int {  // exactly what execute_forward queues for t3
-        if (p->part_planes > 0 && p->ycuts > 1) {
-            for (int y = 0; y < p->ycuts; ++y) {
-                const int rc = launch_x(p, (const char*)cand + y * sub, (char*)p->buf2 + y * sub, false, ysub);
-                if (rc) return rc;
-            }
-            return DFFT_OK;
-        }
-        return launch_x(p, cand, p->buf2);
-    };
-    auto probe = [&](void* cand, float* ms_out) -> int {
-        float t[5];
-        for (int i = 0; i < 7; ++i) {
-            if (hipEventRecord(e0, p->stream) != hipSuccess) return fail(DFFT_EHIP, "receive-buffer placement: event");
-            const int rc = x_launches(cand);
-            if (rc) return rc;
-            float ms = 0.f;
-            if (hipEventRecord(e1, p->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-                return fail(DFFT_EHIP, "receive-buffer placement: timing");
-            if (i >= 2) t[i - 2] = ms;
-        }
-        std::sort(t, t + 5);
-        *ms_out = t[2];
-        return DFFT_OK;
-    };
-    std::vector<void*> cand(1, cur);
-    p->w_ms.clear();
-    float ms = 0.f;
-    int   rc = probe(cur, &ms);
-    if (rc == DFFT_OK) p->w_ms.push_back(ms);
-    float  lo = ms, hi = ms;
-    size_t used = bytes;
-    while (rc == DFFT_OK && (int)cand.size() < max_tries && used + bytes <= budget) {
-        if (lo < 0.97f * hi) {  // both behaviours seen?  confirm on a second timing of the extremes (dfft_plan_tune)
-            int ilo = 0, ihi = 0;
-            for (int i = 1; i < (int)p->w_ms.size(); ++i) {
-                if (p->w_ms[i] < p->w_ms[ilo]) ilo = i;
-                if (p->w_ms[i] > p->w_ms[ihi]) ihi = i;
-            }
-            for (int idx : {ilo, ihi}) {
-                float again = 0.f;
-                if (probe(cand[idx], &again) == DFFT_OK && again > 0.f) p->w_ms[idx] = std::min(p->w_ms[idx], again);
-            }
-            lo = *std::min_element(p->w_ms.begin(), p->w_ms.end());
-            hi = *std::max_element(p->w_ms.begin(), p->w_ms.end());
-            if (lo < 0.965f * hi) break;
-        }
-        void* nw = nullptr;
-        if (hipMalloc(&nw, recv_buffer_bytes(p)) != hipSuccess) {  // (the size the pool was asked for: the candidate may take the buffer's place)
-            (void)hipGetLastError();
-            break;
-        }
-        used += bytes;
-        cand.push_back(nw);
-        rc = probe(nw, &ms);
-        if (rc) break;
-        p->w_ms.push_back(ms);
-        lo = std::min(lo, ms);
-        hi = std::max(hi, ms);
-    }
-    (void)hipStreamSynchronize(p->stream);
-    int best = 0;
-    for (int i = 1; i < (int)p->w_ms.size(); ++i)
-        if (p->w_ms[i] < 0.985f * p->w_ms[best]) best = i;  // a later candidate must be clearly faster
-    for (int i = 1; i < (int)cand.size(); ++i)
-        if (i != best) (void)hipFree(cand[i]);
-    if (best != 0) {
-        // the chosen allocation takes the place of the plan's buffer; bufferDev1 carries the input captured at plan time
-        if (!is_rbuf && hipMemcpyAsync(cand[best], p->in, bytes, hipMemcpyDeviceToDevice, p->stream) != hipSuccess) (void)hipGetLastError();
-        (void)hipStreamSynchronize(p->stream);
-        const int src = comm_recv_swap(p->comm, cur, cand[best]);
-        if (src) rc = src;
-        if (is_rbuf) p->rbuf = cand[best];
-        else p->buf1 = cand[best];
-        p->xd.recvbuf = cand[best];
-    }
-    p->w_kept = best;
-    (void)hipMemcpyAsync(p->buf2, saved_out, bytes, hipMemcpyDeviceToDevice, p->stream);
-    (void)hipStreamSynchronize(p->stream);
-    (void)hipFree(saved_out);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (getenv("DFFT_DEBUG")) {
-        fprintf(stderr, "[dfft] receive-buffer placement (rank %d): X pass", p->me);
-        for (float v : p->w_ms) fprintf(stderr, " %.4f", v);
-        fprintf(stderr, " ms, kept candidate %d\n", p->w_kept);
-    }
-    return rc;
+// experiment knobs: DFFT_Z_GRID / DFFT_Y_GRID / DFFT_X_GRID cap the persistent grid of the respective pass -- a tuning knob and the
+// tests' way to give a workgroup many tiles.  Read ONCE per plan (plan_new), never on the launch path: getenv is not safe
+// against a concurrent setenv of another device thread.
+static int env_grid(const char* name) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : 0;
 }
 
-// the byte ranges [a, a + ab) and [b, b + bb) overlap (or start at the same address)
-static bool ranges_overlap(const void* a, uintptr_t ab, const void* b, uintptr_t bb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 == b0 || (a0 < b0 + bb && b0 < a0 + ab);
-}
-// The complex entry points and plans run out of place or exactly in place: two different pointers whose `bytes`-long ranges overlap
-// would have one pass read what another has already overwritten.
-static bool partly_overlap(const void* in, const void* out, uintptr_t bytes) { return in != out && ranges_overlap(in, bytes, out, bytes); }
-
-extern "C" {
-
-const char* dfft_version(void) { return "dfft-mi355x 0.1 (gfx950)"; }
-const char* dfft_last_error(void) { return g_last_error.c_str(); }
-
-int dfft_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int dfft_device_pci_bus_id(int device, char* buf, int len) {
-    if (!buf || len < 16) return fail(DFFT_EINVAL, "dfft_device_pci_bus_id: buffer too small");
-    if (device < 0) DFFT_HIP_TRY(hipGetDevice(&device));
-    DFFT_HIP_TRY(hipDeviceGetPCIBusId(buf, len, device));
-    return DFFT_OK;
-}
-
-int dfft_length_supported(long long n) {
-    if (n <= 0 || n >= (1ll << 30)) return 0;
-    if (fft_length_supported((int)n)) return 1;
-    int a, b;
-    return long_split(n, &a, &b) ? 1 : 0;  // two-pass (four-step) plans above 4096
-}
-
-int dfft_length_kind(long long n) { return length_kind(n); }
-
-long long dfft_bluestein_length(long long n) { return length_kind(n) == 3 ? bluestein_padded_length(n) : 0; }
-
-// Route predicates of the plan-less entry points (read-only; the environment switches are read as a call would read them)
-int dfft_bluestein_fused_applies(long long n, long long s) { return length_kind(n) == 3 && s >= 1 && bluestein_runs_fused(n, s, bluestein_fused_env()); }
-int dfft_rfft_cols_fused_applies(long long n, long long s, int dtype) {
-    return (dtype == DFFT_F64 || dtype == DFFT_F32) && s > 1 && real_cols_fused(n, s, dtype);
-}
-int dfft_r2r_fused_applies(long long n, long long s, int dtype, int kind, int vec) {
-    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3 || n < 1 || s < 1) return 0;
-    return r2r_fused_env() && r2r_fused(n, s, dtype, kind, vec != 0);
-}
-
-// Scratch bytes a plan-less call leases from the per-(device, stream) buffer (0: none), by the routines' own rules and without a device:
-// the sizes depend on a Bluestein length's n, M and dtype only, so tables without device arrays stand in for the cached ones.
-static void scratch_tables(BluesteinTables* T, long long n, int dtype, int dir) {
-    T->n = n;
-    T->M = bluestein_padded_length(n);
-    T->dtype = dtype;
-    T->dir = dir;
-}
-unsigned long long dfft_fft1d_any_scratch_bytes(long long n, long long s, long long batch, int dtype) {
-    const int kind = length_kind(n);
-    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || s < 1 || batch < 1 || kind < 2) return 0;
-    if (kind == 2) return (unsigned long long)batch * n * s * elem_bytes(dtype);
-    if (!bluestein_extent_ok(n, s, dtype)) return 0;  // refused before any lease
-    BluesteinTables T;
-    scratch_tables(&T, n, dtype, DFFT_FORWARD);
-    return bluestein_scratch_bytes(T, s, batch, bluestein_fused_env());
-}
-unsigned long long dfft_rfft1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype) {
-    const int kind = length_kind(n);
-    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || s < 2 || batch < 1 || kind == 0) return 0;
-    BluesteinTables T;
-    scratch_tables(&T, n, dtype, DFFT_FORWARD);
-    return real_cols_scratch_bytes(n, s, batch, dtype, kind == 3 ? &T : nullptr, bluestein_fused_env());
-}
-unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype, int kind, int vec) {
-    const int lk = length_kind(n);
-    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3 || s < 1 || batch < 1 || lk == 0) return 0;
-    BluesteinTables T;
-    scratch_tables(&T, n, dtype, DFFT_FORWARD);
-    R2rLaunch L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.kind = kind;
-    L.n = n;
-    L.s = s;
-    L.batch = batch;
-    L.in = L.out = (void*)(uintptr_t)(vec ? 64 : elem_bytes(dtype) / 2);  // r2r_vec looks at the alignment only
-    return r2r_scratch_bytes(L, r2r_fused_env(), lk == 3 ? &T : nullptr, bluestein_fused_env());
-}
-
-int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,
-                             int* new_total, int* new_in_rank) {
-    if (!N || !new_total || !new_in_rank || nranks < 1 || rank < 0 || rank >= nranks || ini_devices_in_rank < 1)
-        return fail(DFFT_EINVAL, "dfft_proper_device_count: bad arguments");
-    int ini = ini_devices_in_rank;
-    if (real_devices >= 0 && ini > real_devices) ini = real_devices;  // fft_mpi_3d_api.cpp:236-239
-    if (ini < 1) return fail(DFFT_ENOGPU, "dfft_proper_device_count: no device available");
-    int total = ini * nranks, in_rank = ini;
-    if (N[0] % total != 0) {  // :244-259
-        const long long per = N[0] / total + 1;
-        total = (int)(N[0] / per);
-        if (N[0] % per != 0) total += 1;
-        in_rank = total / nranks;
-        const int rem = total % nranks;
-        if (rem != 0 && rank < rem) in_rank += 1;
-    }
-    *new_total = total;
-    *new_in_rank = in_rank;
-    if (in_rank == 0) return fail(DFFT_EINVAL, "could not support this distribution of data");  // :266-269
-    return DFFT_OK;
-}
-
-long long dfft_local_count(const long long N[3], int total_devices, int global_idx) {
-    if (!N || total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return -1;
-    const Slab sx = make_slab(N[0], total_devices);
-    return sx.size(global_idx) * N[1] * N[2];
-}
-
-long long dfft_max_count(long long n0, long long n1, long long n2, int total_devices, int is_last_device) {
-    if (total_devices < 1) return -1;
-    const Slab      sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
-    const int       g = is_last_device ? total_devices - 1 : 0;
-    const long long a = sx.size(g) * n1 * n2, b = n0 * sy.size(g) * n2;
-    return a > b ? a : b;
-}
-
-int dfft_local_size(long long n0, long long n1, long long n2, int total_devices, int global_idx, long long* local_n0,
-                    long long* local_0_start, long long* local_n1, long long* local_1_start) {
-    (void)n2;
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices)
-        return fail(DFFT_EINVAL, "dfft_local_size: bad arguments");
-    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
-    if (local_n0) *local_n0 = sx.size(global_idx);
-    if (local_0_start) *local_0_start = sx.start(global_idx);
-    if (local_n1) *local_n1 = sy.size(global_idx);
-    if (local_1_start) *local_1_start = sy.start(global_idx);
-    return DFFT_OK;
-}
-
-int dfft_exchange_layout(long long n0, long long n1, long long n2, int total_devices, int global_idx, int direction,
-                         long long* scount, long long* soffset, long long* rcount, long long* roffset) {
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices ||
-        (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_exchange_layout: bad arguments");
-    dfft_plan_s tmp;
-    tmp.N[0] = n0;
-    tmp.N[1] = n1;
-    tmp.N[2] = n2;
-    tmp.P = total_devices;
-    tmp.me = global_idx;
-    tmp.direction = direction;
-    tmp.dtype = DFFT_F64;
-    tmp.sx = make_slab(n0, total_devices);
-    tmp.sy = make_slab(n1, total_devices);
-    if (tmp.sx.size(total_devices - 1) < 1 || tmp.sy.size(total_devices - 1) < 1)
-        return fail(DFFT_EINVAL, "dfft_exchange_layout: last slab would be empty");
-    fill_exchange(&tmp, tmp.xd, direction);
-    for (int q = 0; q < total_devices; ++q) {
-        if (scount) scount[q] = tmp.xd.scount[q];
-        if (soffset) soffset[q] = tmp.xd.soffset[q];
-        if (rcount) rcount[q] = tmp.xd.rcount[q];
-        if (roffset) roffset[q] = tmp.xd.roffset[q];
-    }
-    return DFFT_OK;
-}
-
-int dfft_exchange_part_layout(long long n0, long long n1, long long n2, int total_devices, int global_idx, int direction,
-                              long long part_planes, int part, int ycuts, int ycut, int max_msgs, int* peer,
-                              long long* soffset, long long* scount, long long* roffset, long long* rcount) {
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices || part_planes < 1 || part < 0 || ycuts < 1 ||
-        ycut >= ycuts || max_msgs < 0 || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_exchange_part_layout: bad arguments");
-    if (ycuts > 1 && (n0 % total_devices != 0 || n1 % total_devices != 0 || (n1 / total_devices) % ycuts != 0))
-        return fail(DFFT_EINVAL, "dfft_exchange_part_layout: Y sub-blocks need even X and Y splits divisible by ycuts");
-    dfft_plan_s tmp;
-    tmp.N[0] = n0;
-    tmp.N[1] = n1;
-    tmp.N[2] = n2;
-    tmp.P = total_devices;
-    tmp.me = global_idx;
-    tmp.direction = direction;
-    tmp.dtype = DFFT_F64;
-    tmp.sx = make_slab(n0, total_devices);
-    tmp.sy = make_slab(n1, total_devices);
-    if (tmp.sx.size(total_devices - 1) < 1 || tmp.sy.size(total_devices - 1) < 1)
-        return fail(DFFT_EINVAL, "dfft_exchange_part_layout: last slab would be empty");
-    fill_exchange(&tmp, tmp.xd, direction);
-    tmp.xd.ycuts = ycuts;
-    std::vector<int>       pe;
-    std::vector<long long> so, sc, ro, rc;
-    comm_part_messages(tmp.xd, part, part_planes, ycut, pe, so, sc, ro, rc);
-    const int n = (int)pe.size();
-    if (n > max_msgs) return fail(DFFT_EINVAL, "dfft_exchange_part_layout: more messages than max_msgs");
-    for (int i = 0; i < n; ++i) {
-        if (peer) peer[i] = pe[i];
-        if (soffset) soffset[i] = so[i];
-        if (scount) scount[i] = sc[i];
-        if (roffset) roffset[i] = ro[i];
-        if (rcount) rcount[i] = rc[i];
-    }
-    return n;
-}
-
-void* dfft_alloc(long long count, int dtype, int flag) {
-    if (count < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32)) {
-        set_error("dfft_alloc: bad arguments");
-        return nullptr;
-    }
-    const size_t bytes = (size_t)count * elem_bytes(dtype);
-    void*        p = nullptr;
-    if (flag == DFFT_ALLOC_HOST) {
-        p = malloc(bytes ? bytes : 1);
-    } else if (flag == DFFT_ALLOC_DEV) {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-            return nullptr;
-        }
-    } else {
-        set_error("Fail to allocate memory!");  // fft_mpi_3d_api.cpp:226
-    }
+dfft_plan_s* plan_new(const long long shape[3], int dtype, int direction, int P, int me, dfft_comm_t comm, unsigned flags) {
+    dfft_plan_s* p = new dfft_plan_s;
+    for (int a = 0; a < 3; ++a) p->N[a] = shape[a];
+    p->dtype = dtype;
+    p->direction = direction;
+    p->P = P;
+    p->me = me;
+    p->flags = flags;
+    p->is_last = me == P - 1;
+    p->sx = make_slab(shape[0], P);
+    p->sy = make_slab(shape[1], P);
+    p->xs = p->sx.size(me);
+    p->ys = p->sy.size(me);
+    p->comm = comm;
+    p->grid_x = env_grid("DFFT_X_GRID");
+    p->grid_y = env_grid("DFFT_Y_GRID");
+    p->grid_z = env_grid("DFFT_Z_GRID");
     return p;
 }
 
-int dfft_free(void* p, int flag) {
-    if (!p) return DFFT_OK;
-    if (flag == DFFT_ALLOC_HOST) {
-        free(p);
-        return DFFT_OK;
-    }
-    DFFT_HIP_TRY(hipFree(p));
-    return DFFT_OK;
+// (dfft_plan_destroy reports a one-launch YZ stage that gave up, and a communicator may report while it unregisters: neither may
+// replace the message of the failure that ended the create function)
+void PlanDeleter::operator()(dfft_plan_s* p) const {
+    const std::string msg = last_error();
+    (void)dfft_plan_destroy(p);
+    set_error(msg);
 }
 
-// conv_half: 0 = dfft_plan_create; 1 / 2 = a half plan of dfft_plan_create_conv (2: plain rows in the exchange buffers)
-static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
-                            void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, int conv_half) {
-    if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create: null plan/in");
-    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, "dfft_plan_create: sizes must be positive");
-    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, "dfft_plan_create: dtype");
-    if (direction != DFFT_FORWARD && direction != DFFT_BACKWARD) return fail(DFFT_EINVAL, "dfft_plan_create: direction");
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices)
-        return fail(DFFT_EINVAL, "dfft_plan_create: device index");
-    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, "dfft_plan_create: a communicator is required for P > 1");
-    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, "dfft_plan_create: communicator size != P");
+void enable_peer_access(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) return;
+    for (int d = 0; d < ndev; ++d) {
+        int can = 0;
+        if (d == device || hipDeviceCanAccessPeer(&can, device, d) != hipSuccess || !can) continue;
+        if (hipDeviceEnablePeerAccess(d, 0) != hipSuccess) (void)hipGetLastError();  // already enabled / not supported: copies still work
+    }
+}
+
+long long cache_chunk_planes(long long planes, long long plane_bytes, long long default_mb, long long rule_planes) {
+    const char*     ce = getenv("DFFT_CHUNK_MB");
+    const long long mb = ce ? atoll(ce) : default_mb;
+    long long       cp = rule_planes > 0 ? rule_planes : (mb > 0 ? evened_chunk_planes(planes, plane_bytes, mb) : 0);
+    const char*     cpe = getenv("DFFT_CHUNK_PLANES");
+    if (cpe && atoll(cpe) > 0) cp = atoll(cpe);
+    return cp >= planes ? 0 : cp;
+}
+
+int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out, dfft_comm_t comm,
+                     int global_idx, int total_devices, unsigned flags, int conv_half) {
+    PlanArgRules rules;
+    rules.direction = &direction;
+    DFFT_TRY(check_plan_args("dfft_plan_create", plan, in, out, n0, n1, n2, dtype, comm, global_idx, total_devices, flags, rules));
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_plan_create: no HIP device visible (no CPU fallback)");
     bool bluestein_axis = false;
     for (long long n : {n0, n1, n2}) {
@@ -1563,73 +702,35 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
     // the four-step and Bluestein axes run in the reference's stage structure
     if (long_axis || bluestein_axis) flags = (flags | DFFT_PLAN_UNFUSED) & ~DFFT_PLAN_OVERLAP;
     trace("dfft_plan_create", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
-    dfft_plan_s* p = new dfft_plan_s;
+    // (refused while the plan owns nothing: from here on a failure destroys what has been built)
+    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
+    if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1)
+        return fail(DFFT_EINVAL, "dfft_plan_create: slab decomposition leaves the last device empty");
+    const long long max_count = dfft_max_count(n0, n1, n2, total_devices, global_idx == total_devices - 1);
+    if (max_count >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: more than 2^31 elements per device");
+    const bool inplace = (out == nullptr || out == in);  // fft_mpi_3d_api.cpp:68-75
+    if (inplace && (flags & DFFT_PLAN_INPUT_FROM_IN) && !conv_half)  // (a forward half plan never writes its result buffer)
+        return fail(DFFT_EINVAL, "dfft_plan_create: DFFT_PLAN_INPUT_FROM_IN needs an out-of-place plan");
+    if ((flags & DFFT_PLAN_NATURAL) && (flags & DFFT_PLAN_UNFUSED))
+        return fail(DFFT_EINVAL, "dfft_plan_create: DFFT_PLAN_NATURAL is a fused-pipeline option");
+    const long long shape[3] = {n0, n1, n2};
+    PlanOwner       owner(plan_new(shape, dtype, direction, total_devices, global_idx, comm, flags));
+    dfft_plan_s*    p = owner.get();
     p->long_axis = long_axis;
     p->conv_half = conv_half != 0;
     p->conv_no_rot = conv_half == 2;
-    p->N[0] = n0;
-    p->N[1] = n1;
-    p->N[2] = n2;
-    p->dtype = dtype;
-    p->direction = direction;
-    p->P = total_devices;
-    p->me = global_idx;
-    p->flags = flags;
-    p->is_last = (global_idx == total_devices - 1);
     {
         const char* fe = getenv("DFFT_FORCE_EXCHANGE");
         p->exch = total_devices > 1 || (comm && comm_kind(comm) == 1 && fe && *fe && *fe != '0');
     }
-    p->sx = make_slab(n0, total_devices);
-    p->sy = make_slab(n1, total_devices);
-    p->xs = p->sx.size(global_idx);
-    p->ys = p->sy.size(global_idx);
-    p->comm = comm;
-    p->grid_x = env_grid("DFFT_X_GRID");
-    p->grid_y = env_grid("DFFT_Y_GRID");
-    p->grid_z = env_grid("DFFT_Z_GRID");
-    p->host_timed = false;
-    for (double& t : p->host_t) t = 0;
-    if (p->sx.size(total_devices - 1) < 1 || p->sy.size(total_devices - 1) < 1) {
-        delete p;
-        return fail(DFFT_EINVAL, "dfft_plan_create: slab decomposition leaves the last device empty");
-    }
-    p->max_count = dfft_max_count(n0, n1, n2, total_devices, p->is_last);
-    if (p->max_count >= (1ll << 31)) {
-        delete p;
-        return fail(DFFT_EUNSUPPORTED, "dfft_plan_create: more than 2^31 elements per device");
-    }
+    p->max_count = max_count;
     p->in = in;
     p->out = out;
-    p->inplace = (out == nullptr || out == in);  // fft_mpi_3d_api.cpp:68-75
-    p->buf2 = p->inplace ? in : out;
-    if (p->inplace && (flags & DFFT_PLAN_INPUT_FROM_IN) && !conv_half) {  // (a forward half plan never writes its result buffer)
-        delete p;
-        return fail(DFFT_EINVAL, "dfft_plan_create: DFFT_PLAN_INPUT_FROM_IN needs an out-of-place plan");
-    }
-    if ((flags & DFFT_PLAN_NATURAL) && (flags & DFFT_PLAN_UNFUSED)) {
-        delete p;
-        return fail(DFFT_EINVAL, "dfft_plan_create: DFFT_PLAN_NATURAL is a fused-pipeline option");
-    }
-    p->chunk_planes = 0;  // decided below, once the layout of the Z -> Y intermediate is known
-    p->buf1 = nullptr;
-    p->stream = nullptr;
-    for (auto& e : p->ev) e = nullptr;
+    p->inplace = inplace;
+    p->buf2 = inplace ? in : out;
     const size_t bytes = (size_t)p->max_count * elem_bytes(dtype);
     hipError_t   e = hipGetDevice(&p->device);
-    if (e == hipSuccess && comm && comm_kind(comm) == 0 && total_devices > 1) {
-        // in-process multi-GPU (the reference's thread-per-GPU model): let this device push straight into its peers'
-        // receive buffers over xGMI instead of staging peer copies through the host
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess) {
-            for (int d = 0; d < ndev; ++d) {
-                int can = 0;
-                if (d == p->device || hipDeviceCanAccessPeer(&can, p->device, d) != hipSuccess || !can) continue;
-                hipError_t pe = hipDeviceEnablePeerAccess(d, 0);
-                if (pe != hipSuccess) (void)hipGetLastError();  // already enabled / not supported: copies still work
-            }
-        }
-    }
+    if (e == hipSuccess && comm && comm_kind(comm) == 0 && total_devices > 1) enable_peer_access(p->device);
     // buffers that are (or may be) registered as receive buffers come from the communicator (pooled per key by IPC communicators)
     const std::string rkey = std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" + std::to_string(dtype) + ":" +
                              std::to_string(total_devices);
@@ -1684,38 +785,26 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
                 if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
         }
     }
-    if (e != hipSuccess) {
-        dfft_plan_destroy(p);
-        return fail(DFFT_EHIP, std::string("dfft_plan_create: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_plan_create: ") + hipGetErrorString(e));
     const bool natural = (flags & DFFT_PLAN_NATURAL) != 0;
     fill_exchange(p, p->xd, natural ? DFFT_FORWARD : direction);
     p->xd.sendbuf = p->buf2;
     p->xd.recvbuf = p->buf1;
-    p->xd.slot = p->xd2.slot = -1;  // registration ids, set below
     if (natural && p->exch) {
         // natural-order plans re-slab twice (X->Y for the X pass, Y->X to return to the caller's layout); the second
         // exchange receives the packed [src][xs][yl_src][N2] blocks into a buffer of its own and uses the other slot
-        if (comm_recv_alloc(comm, rkey + ":nat", rbytes, &p->rbuf) != DFFT_OK) {
-            dfft_plan_destroy(p);
+        if (comm_recv_alloc(comm, rkey + ":nat", rbytes, &p->rbuf) != DFFT_OK)
             return fail(DFFT_EHIP, "dfft_plan_create: no memory for the second receive buffer");
-        }
         fill_exchange(p, p->xd2, DFFT_BACKWARD);
         p->xd2.sendbuf = p->buf2;
         p->xd2.recvbuf = p->rbuf;
-        int rc = comm_register(comm, global_idx, p->rbuf, p->device, &p->xd2.slot);
-        if (rc) {
-            dfft_plan_destroy(p);
-            return rc;
-        }
+        DFFT_TRY(comm_register(comm, global_idx, p->rbuf, p->device, &p->xd2.slot));
     }
     if (p->part_planes > 0) {
         // overlap mode: parts arrive while later planes are still being transformed in bufferDev1, so the exchange
         // needs a receive buffer of its own (one more slab in HBM; 288 GB makes that a non-issue)
-        if (comm_recv_alloc(comm, rkey + ":rb", rbytes, &p->rbuf) != DFFT_OK) {
-            dfft_plan_destroy(p);
+        if (comm_recv_alloc(comm, rkey + ":rb", rbytes, &p->rbuf) != DFFT_OK)
             return fail(DFFT_EHIP, "dfft_plan_create: no memory for the receive buffer of the overlapped exchange");
-        }
         if (direction == DFFT_FORWARD) p->xd.recvbuf = p->rbuf;  // Y pass -> out (send) -> rbuf (receive) -> X pass -> out
         else p->xd.sendbuf = p->rbuf;                            // in -> X pass -> rbuf (send) -> bufferDev1 -> Y,Z -> out
         p->xd.ycuts = p->ycuts;
@@ -1797,12 +886,8 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
     }
     if (comm) {
         // placement of the receive buffer (P > 1 twin of dfft_plan_tune), then its registration: after that the peers know the pointer
-        int rc = place_recv_buffer(p);
-        if (rc == DFFT_OK) rc = comm_register(comm, global_idx, p->xd.recvbuf, p->device, &p->xd.slot);  // nodeDataDev[loc] = bufferDev1, :80
-        if (rc) {
-            dfft_plan_destroy(p);
-            return rc;
-        }
+        DFFT_TRY(place_recv_buffer(p));
+        DFFT_TRY(comm_register(comm, global_idx, p->xd.recvbuf, p->device, &p->xd.slot));  // nodeDataDev[loc] = bufferDev1, :80
     }
     {
         // one-launch t0 (dfft_zy.hip): where the kernel exists and the plan has the unpadded-row hand-over buffer it works on
@@ -1881,9 +966,10 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
         // (228 MiB) run t0 of 512^3 fp64 in 1.213-1.216 ms, 8 x 64 (256 MiB + padding) in 1.297, 10 x 52 in 1.238, and any
         // count that leaves a short last phase loses (56 -> 9 x 56 + 8: 1.284; 62: 1.341; profiles/r03/experiments/
         // chunk_planes_one_launch.log) -- so: 230 MiB, evened out over the phases as before.
-        long long   mb = p->zy_on ? 230 : 256;
-        const char* ce = getenv("DFFT_CHUNK_MB");
-        if (ce) mb = atoll(ce);
+        const long long default_mb = p->zy_on ? 230 : 256;
+        const char*     ce = getenv("DFFT_CHUNK_MB");
+        const long long mb = ce ? atoll(ce) : default_mb;
+        long long       streamed = 0;  // the chunk of the rule for Y passes that stream their results out, where it applies
         const char* re = getenv("DFFT_CHUNK_RULE");  // 0: the rule of rounds 2-3 for every plan (A/B switch)
         const bool  y_streams_out = p->exch && !(flags & (DFFT_PLAN_UNFUSED | DFFT_PLAN_NATURAL));
         if (mb > 0 && !p->zy_on && y_streams_out && !(re && *re == '0')) {
@@ -1904,7 +990,7 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
                 const long long q = cus / std::gcd(cus, tiles_per_plane);  // planes per whole number of grid rounds
                 if (q > 1 && fit >= 2 * q) fit -= fit % q;
             }
-            p->chunk_planes = fit;
+            streamed = fit;
             // Overlapped plans on two launches per PART (no one-launch stage for the shape): a part is one Z + Y launch pair, so the same
             // rule sizes it -- when that does not change the number of parts (the overlap's granularity): config 4 per rank at P = 8,
             // 4 x 32 -> 3 x 40 + 8 planes (a 32-plane launch pair runs at the rate of a 32-plane chunk: serial t0 0.547 ms with 40-plane
@@ -1913,24 +999,13 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
             const long long blk = p->sx.blk, pp = p->part_planes;
             if (pp > 0 && !p->zy_eligible && !getenv("DFFT_OVERLAP_PARTS") && !ce && fit > pp && fit < blk && (blk + fit - 1) / fit == (blk + pp - 1) / pp)
                 p->part_planes = fit;
-        } else if (mb > 0) {
-            const long long plane_b = n1 * n2 * (long long)elem_bytes(dtype);
-            long long       fit = std::max(1ll, (mb << 20) / plane_b);
-            if (plane_b >= (8ll << 20) && fit > 1) --fit;
-            const long long nchunks = std::max(1ll, (p->xs + fit - 1) / fit);
-            p->chunk_planes = (p->xs + nchunks - 1) / nchunks;
         }
-        const char* cpe = getenv("DFFT_CHUNK_PLANES");
-        if (cpe && atoll(cpe) > 0) p->chunk_planes = atoll(cpe);
-        if (p->chunk_planes >= p->xs) p->chunk_planes = 0;
+        p->chunk_planes = cache_chunk_planes(p->xs, n1 * n2 * (long long)elem_bytes(dtype), default_mb, streamed);  // (else: evened out)
     }
     if (p->long_axis) {
         p->chunk_planes = 0;  // the four-step passes work on the whole slab
         e = hipMalloc(&p->lbuf, (size_t)p->max_count * elem_bytes(dtype));
-        if (e != hipSuccess) {
-            dfft_plan_destroy(p);
-            return fail(DFFT_EHIP, std::string("dfft_plan_create: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_plan_create: ") + hipGetErrorString(e));
     }
     if (bluestein_axis) {
         // the tables of every Bluestein axis, and the scratch of the passes that use the multi-pass form: Z rows (xs * N1 of them), Y columns
@@ -1942,20 +1017,13 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
         for (const auto& ps : passes) {
             if (length_kind(ps[0]) != 3) continue;
             BluesteinTablesPtr t;
-            const int          rc = bluestein_tables(ps[0], dtype, direction, &t);
-            if (rc) {
-                dfft_plan_destroy(p);
-                return rc;
-            }
+            DFFT_TRY(bluestein_tables(ps[0], dtype, direction, &t));
             p->bs.tables.push_back(t);
             need = std::max(need, bluestein_scratch_bytes(*t, ps[1], ps[2], p->bs.fused));
         }
         if (need) {
             e = hipMalloc(&p->bs.scratch, need);
-            if (e != hipSuccess) {
-                dfft_plan_destroy(p);
-                return fail(DFFT_EHIP, std::string("dfft_plan_create: Bluestein scratch: ") + hipGetErrorString(e));
-            }
+            if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_plan_create: Bluestein scratch: ") + hipGetErrorString(e));
             p->bs.bytes = need;
         }
     }
@@ -1963,15 +1031,17 @@ static int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long 
     for (long long n : {n0, n1, n2}) {
         if (n > 4096 || length_kind(n) == 3) continue;  // long axes: their factors' tables are built on first use; Bluestein axes: above
         const void* tw;
-        int         rc = get_twiddles((int)n, dtype, &tw);
-        if (rc) {
-            dfft_plan_destroy(p);
-            return rc;
-        }
+        DFFT_TRY(get_twiddles((int)n, dtype, &tw));
     }
-    *plan = p;
+    *plan = owner.release();
     return DFFT_OK;
 }
+
+}  // namespace dfft
+
+using namespace dfft;
+
+extern "C" {
 
 int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in,
                      void* out, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
@@ -1981,869 +1051,6 @@ int dfft_plan_create(dfft_plan_t* plan, long long n0, long long n1, long long n2
         partly_overlap(in, out, (uintptr_t)dfft_max_count(n0, n1, n2, total_devices, global_idx == total_devices - 1) * elem_bytes(dtype)))
         return fail(DFFT_EINVAL, "dfft_plan_create: in and out overlap partly (a plan runs out of place or exactly in place)");
     return plan_create_impl(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, 0);
-}
-
-int dfft_r2c_counts(long long n0, long long n1, long long n2, int total_devices, int global_idx, long long* real_count, long long* complex_count) {
-    if (n0 < 1 || n1 < 1 || n2 < 2 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices)
-        return fail(DFFT_EINVAL, "dfft_r2c_counts: bad arguments");
-    const Slab      sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
-    const long long nh = n2 / 2 + 1, xs = sx.size(global_idx), ys = sy.size(global_idx);
-    if (xs < 0 || sy.size(total_devices - 1) < 1 || sx.size(total_devices - 1) < 1)
-        return fail(DFFT_EINVAL, "dfft_r2c_counts: slab decomposition leaves the last device empty");
-    // complex side: the transposed result [ys][nh][N0], and -- forward plans with an exchange -- the packed send layout [d][xs][yl_d][nh]
-    // the Y pass writes into the same buffer (the offsets of dfft_exchange_layout at width nh)
-    const long long send = (long long)(total_devices - 1) * xs * sy.blk * nh + xs * sy.size(total_devices - 1) * nh;
-    if (real_count) *real_count = xs * n1 * n2;
-    if (complex_count) *complex_count = std::max(ys * nh * n0, total_devices > 1 ? send : 0ll);
-    return DFFT_OK;
-}
-
-}  // extern "C"
-
-// ---- spectral-filter (FFT convolution) plans ---------------------------------------------------------------------------------------
-// y = ifftn(fftn(x) . H): forward half plan (YZ stage, exchange) -> X stage in place on the slab it leaves (dfft_conv.hip: forward X
-// transform, multiply by the filter copy, inverse X transform) -> backward half plan (exchange, inverse YZ stage).
-static int conv_alloc_filter(dfft_plan_s* p, int kind) {
-    ConvState*   c = p->conv;
-    const size_t need = (size_t)c->slab_elems * elem_bytes(p->dtype) / (kind == DFFT_FILTER_REAL ? 2 : 1);
-    if (c->filt && c->filt_bytes >= need) {
-        // (real-field plans: the forward-only X stage of dfft_conv_set_kernel writes the columns below the plan's width only, and a copy
-        // that held reals before is re-read as complex elements -- whatever it does not write must read as zero)
-        if (c->real) {
-            DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
-            DFFT_HIP_TRY(hipMemsetAsync(c->filt, 0, c->filt_bytes, p->stream));
-        }
-        return DFFT_OK;
-    }
-    DFFT_HIP_TRY(hipStreamSynchronize(p->stream));  // an execute that still reads the old copy
-    if (c->filt) (void)hipFree(c->filt);
-    c->filt = nullptr;
-    c->filt_bytes = 0;
-    c->kind = -1;
-    DFFT_HIP_TRY(hipMalloc(&c->filt, need));
-    c->filt_bytes = need;
-    DFFT_HIP_TRY(hipMemsetAsync(c->filt, 0, need, p->stream));  // the padding of the layout is read (and multiplied into padding)
-    return DFFT_OK;
-}
-
-// The X stage on the plan's stream.  to_filter: the forward transform alone, times `scale`, into the filter copy (dfft_conv_set_kernel).
-static int conv_x_stage(dfft_plan_s* p, bool to_filter, double scale) {
-    ConvState* c = p->conv;
-    ConvLaunch L = c->L;
-    DFFT_TRY(get_twiddles(L.n0, p->dtype, &L.tw));
-    L.filt = c->filt;
-    L.filter_real = (!to_filter && c->kind == DFFT_FILTER_REAL) ? 1 : 0;
-    if (c->nout > 0 && !to_filter) {
-        if (c->fused) return check_launch(launch_conv_multi_fused(L, c->M, c->nout, p->stream), "X stage of the multi-output spectral-filter plan");
-        // multi route: forward columns and the multiply by the filter copy in place, ONCE; per output the factors out of place into slab k
-        // and the inverse columns there; output 0 last, in place over the product
-        FftLaunch X;
-        std::memset(&X, 0, sizeof(X));
-        X.dtype = p->dtype;
-        X.n = L.n0;
-        X.dir = DFFT_FORWARD;
-        X.cols = 1;
-        X.in = L.in;
-        X.out = const_cast<void*>(L.in);
-        X.tw = L.tw;
-        X.imap = X.omap = plain_axis(L.n0, L.plane, 1);
-        X.itile = X.otile = TileMap{L.pitch, 1};
-        X.na = L.rows;
-        X.ncols = (int)L.ncols;
-        X.scale = 1.0;
-        X.grid_limit = p->grid_x;
-        DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the multi-output spectral-filter plan (forward columns)"));
-        DFFT_TRY(check_launch(launch_conv_mul(p->dtype, L.filter_real, const_cast<void*>(L.in), c->filt, c->slab_elems, p->stream),
-                              "X stage of the multi-output spectral-filter plan (multiply)"));
-        X.dir = DFFT_BACKWARD;
-        for (int i = 0; i < c->nout; ++i) {
-            const int k = i + 1 < c->nout ? i + 1 : 0;
-            void*     slab = c->M.out[k];
-            if (k > 0 || !c->unit[k])
-                DFFT_TRY(check_launch(launch_conv_factor_mul(L, L.in, slab, c->M.ax[k], c->M.by[k], c->M.cz[k], p->stream),
-                                      "X stage of the multi-output spectral-filter plan (factors)"));
-            X.in = X.out = slab;
-            DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the multi-output spectral-filter plan (inverse columns)"));
-        }
-        return DFFT_OK;
-    }
-    if (c->fused) {
-        if (to_filter) {
-            L.forward_only = 1;
-            L.out = c->filt;
-            L.scale = scale;
-        }
-        return check_launch(launch_conv_fused(L, p->stream), "X stage of the spectral-filter plan");
-    }
-    // multi route: the C2C column kernels in place along X, the multiply, the inverse column kernels into the slab the backward half reads
-    FftLaunch X;
-    std::memset(&X, 0, sizeof(X));
-    X.dtype = p->dtype;
-    X.n = L.n0;
-    X.dir = DFFT_FORWARD;
-    X.cols = 1;
-    X.in = L.in;
-    X.out = to_filter ? c->filt : const_cast<void*>(L.in);
-    X.tw = L.tw;
-    X.imap = X.omap = plain_axis(L.n0, L.plane, 1);
-    X.itile = X.otile = TileMap{L.pitch, 1};
-    X.na = L.rows;
-    X.ncols = (int)L.ncols;
-    X.scale = to_filter ? scale : 1.0;
-    X.grid_limit = p->grid_x;
-    DFFT_TRY(check_launch(launch_fft(X, p->stream), "X stage of the spectral-filter plan (forward columns)"));
-    if (to_filter) return DFFT_OK;
-    DFFT_TRY(check_launch(launch_conv_mul(p->dtype, L.filter_real, const_cast<void*>(L.in), c->filt, c->slab_elems, p->stream),
-                          "X stage of the spectral-filter plan (multiply)"));
-    X.dir = DFFT_BACKWARD;
-    X.out = L.out;
-    return check_launch(launch_fft(X, p->stream), "X stage of the spectral-filter plan (inverse columns)");
-}
-
-static int conv_execute(dfft_plan_s* p, unsigned exec_flags) {
-    ConvState* c = p->conv;
-    if (c->kind < 0) return fail(DFFT_EINVAL, "dfft_execute: this spectral-filter plan has no filter yet (dfft_conv_set_filter / dfft_conv_set_kernel)");
-    const bool     sync = (exec_flags & DFFT_EXEC_SYNC_STAGES) != 0;
-    const unsigned half_flags = exec_flags & ~DFFT_EXEC_PRINT;
-    p->host_timed = sync;
-    p->timed = sync || !(exec_flags & DFFT_EXEC_NO_TIMING);
-    // a half that fails on this device alone must not leave the peers waiting in the other half's exchange: with a communicator the
-    // sequence is queued to its end and the first failure is the return code
-    int         rc = dfft_execute(c->f, half_flags);
-    std::string msg = rc ? g_last_error : std::string();
-    if (rc && !p->exch) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    int        rx = conv_x_stage(p, false, 1.0);
-    if (rx == DFFT_OK && sync) {
-        const hipError_t e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) rx = fail(DFFT_EHIP, std::string("X stage of the spectral-filter plan: ") + hipGetErrorString(e));
-        c->x_host = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if (rx && !rc) {
-        rc = rx;
-        msg = g_last_error;
-    }
-    if (rc && !p->exch) return rc;
-    for (int k = 0; k < c->backs(); ++k) {  // one after another on the one stream
-        const int rb = dfft_execute(c->back(k), half_flags);
-        if (rb && !rc) {
-            rc = rb;
-            msg = g_last_error;
-            if (!p->exch) return rc;
-        }
-    }
-    if (rc) return fail(rc, msg);
-    return DFFT_OK;
-}
-
-static int conv_describe(const dfft_plan_s* p, char* buf, int len) {
-    const ConvState* c = p->conv;
-    char             half[512] = "";
-    (void)dfft_plan_describe(c->f, half, (int)sizeof(half));
-    const char* yz = strstr(half, "yz_stage=");
-    char        yzs[64] = "yz_stage=?";
-    if (yz) sscanf(yz, "%63s", yzs);
-    if (c->real && c->nout > 0) {
-        snprintf(buf, (size_t)len, "pipeline=conv-real-multi outputs=%d xconv=%s filter=%s width=%lld bins=%lld pitch=%lld handover=%s chunk_planes=%lld",
-                 c->nout, c->fused ? "fused" : "multi", c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"),
-                 c->L.ncols, c->nh, c->L.pitch, p->exch ? "receive-buffer" : "intermediate", c->f->chunk_planes);
-        return DFFT_OK;
-    }
-    if (c->real) {
-        snprintf(buf, (size_t)len, "pipeline=conv-real xconv=%s filter=%s width=%lld bins=%lld pitch=%lld handover=%s chunk_planes=%lld",
-                 c->fused ? "fused" : "multi", c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"),
-                 c->L.ncols, c->nh, c->L.pitch, p->exch ? "receive-buffer" : "intermediate", c->f->chunk_planes);
-        return DFFT_OK;
-    }
-    snprintf(buf, (size_t)len, "pipeline=conv xconv=%s filter=%s %s handover=%s rotated_exchange_rows=%d", c->fused ? "fused" : "multi",
-             c->kind == DFFT_FILTER_REAL ? "real" : (c->kind == DFFT_FILTER_COMPLEX ? "complex" : "unset"), yzs,
-             (!p->exch && c->f->wbuf) ? "padded-buffer" : (p->exch ? "receive-buffer" : "bufferDev1"), c->L.rot);
-    return DFFT_OK;
-}
-
-static int conv_sync(dfft_plan_s* p) {
-    ConvState* c = p->conv;
-    DFFT_HIP_TRY(hipStreamSynchronize(p->stream));
-    DFFT_TRY(zy_check(c->f));
-    for (int k = 0; k < c->backs(); ++k) DFFT_TRY(zy_check(c->back(k)));
-    if (p->comm) return comm_check(p->comm);
-    return DFFT_OK;
-}
-
-// t = forward YZ stage (with the packing), both exchanges, the X stage, inverse YZ stage (with the unpacking)
-static int conv_stage_times(dfft_plan_s* p, double t[4]) {
-    ConvState* c = p->conv;
-    DFFT_TRY(conv_sync(p));
-    if (!p->timed) return fail(DFFT_EINVAL, "dfft_stage_times: the last execute ran with DFFT_EXEC_NO_TIMING");
-    const dfft_plan_s *f = c->f, *b = c->back(0);
-    if (p->host_timed) {
-        t[0] = f->host_t[0] + f->host_t[1];
-        t[1] = f->host_t[2];
-        t[2] = f->host_t[3] + c->x_host;
-        t[3] = 0;
-        for (int k = 0; k < c->backs(); ++k) {  // (multi-output plans: all 1 + K exchanges, the sum of the K inverse stages)
-            const dfft_plan_s* bk = c->back(k);
-            t[1] += bk->host_t[1];
-            t[2] += bk->host_t[0];
-            t[3] += bk->host_t[2] + bk->host_t[3];
-        }
-        return DFFT_OK;
-    }
-    auto ms = [](hipEvent_t a, hipEvent_t z, double* out) {
-        float v = 0;
-        DFFT_HIP_TRY(hipEventElapsedTime(&v, a, z));
-        *out = v * 1e-3;
-        return (int)DFFT_OK;
-    };
-    double x1 = 0, x2 = 0;
-    DFFT_TRY(ms(f->ev[0], f->ev[2], &t[0]));
-    DFFT_TRY(ms(f->ev[2], f->ev[3], &x1));
-    DFFT_TRY(ms(b->ev[1], b->ev[2], &x2));
-    t[1] = x1 + x2;
-    DFFT_TRY(ms(f->ev[3], b->ev[1], &t[2]));
-    DFFT_TRY(ms(b->ev[2], b->ev[4], &t[3]));
-    for (int k = 1; k < c->backs(); ++k) {
-        const dfft_plan_s* bk = c->back(k);
-        DFFT_TRY(ms(bk->ev[1], bk->ev[2], &x1));
-        DFFT_TRY(ms(bk->ev[2], bk->ev[4], &x2));
-        t[1] += x1;
-        t[3] += x2;
-    }
-    return DFFT_OK;
-}
-
-static int conv_destroy(dfft_plan_s* p) {
-    ConvState* c = p->conv;
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    int rc = DFFT_OK;
-    for (int k = CONV_MAX_OUTPUTS - 1; k >= 1; --k) {  // multi-output plans: the halves of outputs K-1 .. 1, their slabs, the factor tables
-        if (c->bk[k]) {
-            const int r = dfft_plan_destroy(c->bk[k]);
-            if (!rc) rc = r;
-        }
-        if (c->xslab[k]) (void)hipFree(c->xslab[k]);
-    }
-    if (c->fact) (void)hipFree(c->fact);
-    if (c->b) {  // (the stream and the hand-over buffer are the forward half's)
-        const int r = dfft_plan_destroy(c->b);
-        if (!rc) rc = r;
-    }
-    if (c->f) {
-        const int r = dfft_plan_destroy(c->f);
-        if (!rc) rc = r;
-    }
-    if (c->sbuf) (void)hipFree(c->sbuf);
-    if (c->filt) (void)hipFree(c->filt);
-    delete c;
-    delete p;
-    return rc;
-}
-
-extern "C" {
-
-long long dfft_conv_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx) {
-    if (n0 < 1 || n1 < 1 || n2 < 1 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return -1;
-    return make_slab(n1, total_devices).size(global_idx) * n2 * n0;
-}
-
-int dfft_conv_fused_applies(int dtype, long long n0, long long rows, long long ncols, long long plane, long long pitch, int rot, const void* in,
-                            const void* out) {
-    if ((dtype != DFFT_F64 && dtype != DFFT_F32) || n0 < 1 || n0 > 4096 || rows < 1 || ncols < 1 || plane < 1 || pitch < 1 || rot < 0) return 0;
-    ConvLaunch L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.n0 = (int)n0;
-    L.rows = rows;
-    L.ncols = ncols;
-    L.plane = plane;
-    L.pitch = pitch;
-    L.rot = rot;
-    L.in = in;
-    L.out = const_cast<void*>(out);
-    return conv_fused_applies(L) ? 1 : 0;
-}
-
-int dfft_plan_create_conv(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
-                          int global_idx, int total_devices, unsigned flags) {
-    const std::string fn = "dfft_plan_create_conv";
-    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
-    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
-    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
-    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
-    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
-    if (flags != DFFT_PLAN_DEFAULT)
-        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT is supported (no OVERLAP, NATURAL, UNFUSED, INPUT_FROM_IN -- which is "
-                                            "implied -- or ANY_LENGTH spectral-filter plans)");
-    for (long long n : {n0, n1, n2})
-        if (length_kind(n) != 1)
-            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) + " -- every axis must be a single-pass length (products of 2, 3, 5, 7 up to 4096)");
-    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
-    if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1) return fail(DFFT_EINVAL, fn + ": slab decomposition leaves the last device empty");
-    // (the X slabs the caller's buffers hold: dfft_local_count elements)
-    if (out && partly_overlap(in, out, (uintptr_t)(sx.size(global_idx) * n1 * n2) * elem_bytes(dtype)))
-        return fail(DFFT_EINVAL, fn + ": in and out overlap partly (a plan runs out of place or exactly in place)");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
-
-    const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
-    // fp32 runs the fused kernel on column PAIRS: an even N2 (every other stride of the slab is then even too)
-    const bool  want_fused = !(fe && *fe == '0') && conv_fused_length((int)n0) && (dtype == DFFT_F64 || n2 % 2 == 0);
-    trace("dfft_plan_create_conv", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices);
-    dfft_plan_s* p = new dfft_plan_s;
-    ConvState*   c = new ConvState;
-    p->conv = c;
-    p->N[0] = n0;
-    p->N[1] = n1;
-    p->N[2] = n2;
-    p->dtype = dtype;
-    p->direction = DFFT_FORWARD;
-    p->P = total_devices;
-    p->me = global_idx;
-    p->flags = flags;
-    p->is_last = global_idx == total_devices - 1;
-    p->inplace = out == nullptr || out == in;
-    p->sx = sx;
-    p->sy = sy;
-    p->xs = sx.size(global_idx);
-    p->ys = sy.size(global_idx);
-    p->max_count = dfft_max_count(n0, n1, n2, total_devices, p->is_last);
-    p->in = in;
-    p->out = p->inplace ? in : out;
-    p->buf1 = p->buf2 = nullptr;
-    p->comm = comm;
-    p->device = 0;
-    p->stream = nullptr;
-    for (auto& e : p->ev) e = nullptr;
-    for (double& t : p->host_t) t = 0;
-    p->host_timed = false;
-    p->chunk_planes = 0;
-    p->grid_x = env_grid("DFFT_X_GRID");
-    auto bail = [&](int rc) {
-        const std::string msg = g_last_error;
-        (void)conv_destroy(p);
-        return fail(rc, msg);
-    };
-    if (comm) {  // the forward half packs into a send buffer of the plan's own: `in` is left alone, and `out` may be `in`
-        const hipError_t e = hipMalloc(&c->sbuf, (size_t)p->max_count * elem_bytes(dtype));
-        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": send buffer: " + hipGetErrorString(e)));
-    }
-    const int mode = want_fused ? 1 : 2;
-    int       rc = plan_create_impl(&c->f, n0, n1, n2, dtype, DFFT_FORWARD, in, c->sbuf, comm, global_idx, total_devices, DFFT_PLAN_INPUT_FROM_IN, mode);
-    if (rc) return bail(rc);
-    rc = plan_create_impl(&c->b, n0, n1, n2, dtype, DFFT_BACKWARD, c->f->buf1, p->out, comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, mode);
-    if (rc) return bail(rc);
-    dfft_plan_s *f = c->f, *b = c->b;
-    // one stream, one hand-over buffer
-    (void)hipStreamSynchronize(b->stream);
-    (void)hipStreamDestroy(b->stream);
-    if (b->wbuf) (void)slab_free(b->wbuf);
-    b->stream = f->stream;
-    b->wbuf = f->wbuf;
-    b->wl = f->wl;
-    b->borrowed = true;
-    p->stream = f->stream;
-    p->device = f->device;
-    p->exch = f->exch;
-    if (f->exch != b->exch || f->rot_elems != b->rot_elems) return bail(fail(DFFT_EINVAL, fn + ": internal: the two halves disagree about the exchange"));
-    ConvLaunch& L = c->L;
-    L.dtype = dtype;
-    L.n0 = (int)n0;
-    L.ncols = n2;
-    L.scale = 1.0;
-    if (p->exch) {
-        // the forward exchange's receive layout [x][yl][N2] IS the backward exchange's send layout (fill_exchange, uneven splits included):
-        // the X stage works in place on the forward half's receive buffer and the backward half sends from it
-        for (int q = 0; q < p->P; ++q)
-            if (f->xd.roffset[q] != b->xd.soffset[q] || f->xd.rcount[q] != b->xd.scount[q])
-                return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
-        b->xd.sendbuf = f->buf1;
-        L.in = L.out = f->buf1;
-        L.plane = p->ys * n2;
-        L.pitch = n2;
-        L.rows = p->ys;
-        L.rot = f->rot_elems;
-        c->slab_elems = n0 * p->ys * n2;
-    } else if (f->wbuf) {
-        L.in = L.out = f->wbuf;
-        L.plane = f->wl.plane;
-        L.pitch = f->wl.pitch;
-        L.rows = n1;
-        c->slab_elems = p->xs * f->wl.plane;
-    } else {  // natural layout: out of bufferDev1 of the forward half into the result buffer, where the inverse YZ stage works in place
-        L.in = f->buf1;
-        L.out = b->buf2;
-        L.plane = n1 * n2;
-        L.pitch = n2;
-        L.rows = n1;
-        c->slab_elems = n0 * n1 * n2;
-    }
-    c->fused = want_fused && conv_fused_applies(L);
-    if (!c->fused && L.rot > 0) return bail(fail(DFFT_EINVAL, fn + ": internal: rotated rows without the fused X stage"));
-    *plan = p;
-    return DFFT_OK;
-}
-
-long long dfft_conv_real_filter_count(long long n0, long long n1, long long n2, int total_devices, int global_idx) {
-    if (n0 < 1 || n1 < 1 || n2 < 1 || total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return -1;
-    return make_slab(n1, total_devices).size(global_idx) * (n2 / 2 + 1) * n0;
-}
-
-// dfft_plan_create_conv_real (nout == 0: one output `out`, NULL or `in` for in place) and dfft_plan_create_conv_real_multi (nout >= 1
-// outputs outs[0 .. nout))
-static int conv_real_create(const std::string& fn, dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out,
-                            void* const* outs, int nout, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
-    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
-    if (outs || nout) {
-        if (!outs || nout < 1 || nout > DFFT_CONV_MAX_OUTPUTS)
-            return fail(DFFT_EINVAL, fn + ": noutputs must be 1 .. " + std::to_string(DFFT_CONV_MAX_OUTPUTS) + " and outs not NULL");
-        for (int k = 0; k < nout; ++k) {
-            if (!outs[k]) return fail(DFFT_EINVAL, fn + ": outs[" + std::to_string(k) + "] is NULL");
-            for (int q = 0; q < k; ++q)
-                if (outs[q] == outs[k]) return fail(DFFT_EINVAL, fn + ": outs[" + std::to_string(q) + "] and outs[" + std::to_string(k) + "] are the same buffer");
-        }
-        out = outs[0];
-    }
-    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
-    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
-    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
-    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
-    if (flags != DFFT_PLAN_DEFAULT)
-        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT is supported (no OVERLAP, NATURAL, UNFUSED, INPUT_FROM_IN -- which is "
-                                            "implied -- or ANY_LENGTH spectral-filter plans)");
-    for (long long n : {n0, n1})
-        if (length_kind(n) != 1)
-            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) + " -- N0 and N1 must be single-pass lengths (products of 2, 3, 5, 7 up to 4096)");
-    if (!real_length_supported(n2))
-        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) + " -- the real axis must be of dfft_real_form 1 (even, N2/2 a single-pass length)");
-    const Slab sx = make_slab(n0, total_devices), sy = make_slab(n1, total_devices);
-    if (sx.size(total_devices - 1) < 1 || sy.size(total_devices - 1) < 1) return fail(DFFT_EINVAL, fn + ": slab decomposition leaves the last device empty");
-    const long long nh = n2 / 2 + 1, nc = conv_real_width(nh, dtype);
-    const long long line = 128 / (long long)elem_bytes(dtype), pitch1 = (nc + line - 1) / line * line;
-    if (std::max(conv_real_recv_count(n0, n1, nc, total_devices), sx.blk * n1 * pitch1) >= (1ll << 31))
-        return fail(DFFT_EUNSUPPORTED, fn + ": more than 2^31 complex elements per device");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
-
-    const char* fe = getenv("DFFT_CONV_FUSED");  // A/B switch, read here once
-    const bool  want_fused = !(fe && *fe == '0') && conv_fused_length((int)n0);
-    trace("dfft_plan_create_conv_real", n0 * 1000000 + n1 * 1000 + n2 % 1000, total_devices * 100 + nout);
-    dfft_plan_s* p = new dfft_plan_s;
-    ConvState*   c = new ConvState;
-    p->conv = c;
-    c->real = true;
-    c->nh = nh;
-    c->nout = nout;
-    p->N[0] = n0;
-    p->N[1] = n1;
-    p->N[2] = n2;  // the REAL length (1 / (N0 N1 N2) in the filter copy); the halves carry the complex width
-    p->dtype = dtype;
-    p->direction = DFFT_FORWARD;
-    p->P = total_devices;
-    p->me = global_idx;
-    p->flags = flags;
-    p->is_last = global_idx == total_devices - 1;
-    p->inplace = out == nullptr || out == in;
-    p->sx = sx;
-    p->sy = sy;
-    p->xs = sx.size(global_idx);
-    p->ys = sy.size(global_idx);
-    p->max_count = p->xs * n1 * pitch1;
-    p->in = in;
-    p->out = p->inplace ? in : out;
-    p->buf1 = p->buf2 = nullptr;
-    p->comm = comm;
-    p->device = 0;
-    p->stream = nullptr;
-    for (auto& e : p->ev) e = nullptr;
-    for (double& t : p->host_t) t = 0;
-    p->host_timed = false;
-    p->chunk_planes = 0;
-    p->grid_x = env_grid("DFFT_X_GRID");
-    auto bail = [&](int rc) {
-        const std::string msg = g_last_error;
-        (void)conv_destroy(p);
-        return fail(rc, msg);
-    };
-    const size_t cs = elem_bytes(dtype);
-    if (total_devices > 1) {  // the forward half packs [d][xs][yl_d][Nc] into a send buffer of the plan's own
-        const hipError_t e = hipMalloc(&c->sbuf, (size_t)total_devices * p->xs * sy.blk * nc * cs);
-        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": send buffer: " + hipGetErrorString(e)));
-    }
-    R2cHalf hf{nc, nullptr};
-    int     rc = create_r2c(&c->f, n0, n1, n2, dtype, DFFT_FORWARD, in, c->sbuf, comm, global_idx, total_devices, DFFT_PLAN_INPUT_FROM_IN, false, &hf);
-    if (rc) return bail(rc);
-    R2cHalf hb{nc, c->f};
-    rc = create_r2c(&c->b, n0, n1, n2, dtype, DFFT_BACKWARD, in, p->out, comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, false, &hb);
-    if (rc) return bail(rc);
-    c->bk[0] = c->b;
-    // outputs 1 .. K-1: a C2R half each, on the same stream.  P = 1: its intermediate (cleared once, like the forward half's) is slab k of
-    // the X stage.  P > 1: it unpacks into the shared intermediate out of a receive buffer of its own and sends from slab k, a buffer of
-    // the plan's in the received slab's layout [N0][y_local][Nc].
-    for (int k = 1; k < nout; ++k) {
-        R2cHalf hk{nc, c->f, k, total_devices == 1};
-        rc = create_r2c(&c->bk[k], n0, n1, n2, dtype, DFFT_BACKWARD, in, outs[k], comm, global_idx, total_devices, DFFT_PLAN_DEFAULT, false, &hk);
-        if (rc) return bail(rc);
-        if (total_devices > 1) {
-            const size_t     bytes = (size_t)(n0 * p->ys * nc) * cs;
-            const hipError_t e = hipMalloc(&c->xslab[k], bytes);
-            if (e != hipSuccess || hipMemset(c->xslab[k], 0, bytes) != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": slab of output " + std::to_string(k)));
-        }
-    }
-    dfft_plan_s *f = c->f, *b = c->b;
-    p->stream = f->stream;
-    p->device = f->device;
-    p->exch = f->exch;
-    ConvLaunch& L = c->L;
-    L.dtype = dtype;
-    L.n0 = (int)n0;
-    L.ncols = nc;
-    L.scale = 1.0;
-    L.rot = 0;
-    if (p->exch) {
-        // as in dfft_plan_create_conv: the forward exchange's receive layout [x][yl][Nc] IS the backward exchange's send layout, so the X
-        // stage works in place on the forward half's receive buffer and the backward half sends from it
-        for (int q = 0; q < p->P; ++q)
-            if (f->xd.roffset[q] != b->xd.soffset[q] || f->xd.rcount[q] != b->xd.scount[q])
-                return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
-        b->xd.sendbuf = f->buf1;
-        L.in = L.out = f->buf1;
-        L.plane = p->ys * nc;
-        L.pitch = nc;
-        L.rows = p->ys;
-        c->slab_elems = n0 * p->ys * nc;
-    } else {  // the intermediate [N0][N1][pitch], rows padded to whole lines
-        L.in = L.out = f->cbuf;
-        L.plane = f->cl.plane;
-        L.pitch = f->cl.pitch;
-        L.rows = n1;
-        c->slab_elems = p->xs * f->cl.plane;
-    }
-    c->fused = want_fused && conv_fused_applies(L);
-    if (nout > 0) {
-        c->M.out[0] = const_cast<void*>(L.in);
-        for (int k = 1; k < nout; ++k) {
-            dfft_plan_s* bk = c->bk[k];
-            if (p->exch) {
-                for (int q = 0; q < p->P; ++q)
-                    if (f->xd.roffset[q] != bk->xd.soffset[q] || f->xd.rcount[q] != bk->xd.scount[q])
-                        return bail(fail(DFFT_EINVAL, fn + ": internal: forward receive pieces and backward send pieces differ"));
-                bk->xd.sendbuf = c->xslab[k];
-                c->M.out[k] = c->xslab[k];
-            } else {
-                if (bk->cl.plane != f->cl.plane || bk->cl.pitch != f->cl.pitch) return bail(fail(DFFT_EINVAL, fn + ": internal: the slabs' layouts differ"));
-                c->M.out[k] = bk->cbuf;
-            }
-        }
-        // the factor tables: ones (as long as the longest factor), then per output a | b (this device's rows) | c (Nc wide)
-        c->fa = (n0 + 1) / 2 * 2;
-        c->fb = (L.rows + 1) / 2 * 2;
-        const long long ones = std::max({c->fa, c->fb, L.ncols}), total = ones + nout * (c->fa + c->fb + L.ncols);
-        hipError_t      e = hipMalloc(&c->fact, (size_t)total * cs);
-        if (e == hipSuccess) e = hipMemset(c->fact, 0, (size_t)total * cs);
-        std::vector<char> host((size_t)ones * cs, 0);
-        for (long long i = 0; i < ones; ++i) {
-            if (dtype == DFFT_F64) reinterpret_cast<double*>(host.data())[2 * i] = 1.0;
-            else reinterpret_cast<float*>(host.data())[2 * i] = 1.f;
-        }
-        if (e == hipSuccess) e = hipMemcpy(c->fact, host.data(), host.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return bail(fail(DFFT_EHIP, fn + ": factor tables: " + hipGetErrorString(e)));
-        for (int k = 0; k < nout; ++k) {
-            c->M.ax[k] = c->M.by[k] = c->M.cz[k] = c->fact;
-            c->unit[k] = true;
-        }
-        // the fused K-output kernel stores fp32 column pairs into every slab (16-byte accesses, like conv_fused_applies asks of L.in)
-        for (int k = 0; k < nout && dtype == DFFT_F32; ++k)
-            if ((uintptr_t)c->M.out[k] & 15) c->fused = false;
-    }
-    *plan = p;
-    return DFFT_OK;
-}
-
-int dfft_plan_create_conv_real(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* out, dfft_comm_t comm,
-                               int global_idx, int total_devices, unsigned flags) {
-    return conv_real_create("dfft_plan_create_conv_real", plan, n0, n1, n2, dtype, in, out, nullptr, 0, comm, global_idx, total_devices, flags);
-}
-
-int dfft_plan_create_conv_real_multi(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, void* in, void* const* outs,
-                                     int noutputs, dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
-    if (!outs) return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: outs is NULL");
-    if (noutputs < 1 || noutputs > DFFT_CONV_MAX_OUTPUTS)
-        return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: noutputs must be 1 .. " + std::to_string(DFFT_CONV_MAX_OUTPUTS));
-    if (!plan || !in) return fail(DFFT_EINVAL, "dfft_plan_create_conv_real_multi: null plan/in");
-    return conv_real_create("dfft_plan_create_conv_real_multi", plan, n0, n1, n2, dtype, in, nullptr, outs, noutputs, comm, global_idx,
-                            total_devices, flags);
-}
-
-// The separable factors of output k (device pointers to the plan's complex type; NULL: ones): ax[N0], ay[N1] -- the whole vector, the
-// plan takes rows y0 .. y0 + y_local --, az[N2/2 + 1].  Private copies; az zero-padded to the plan's width.
-int dfft_conv_set_factors(dfft_plan_t plan, int k, const void* ax, const void* ay, const void* az) {
-    if (!plan || !plan->conv || plan->conv->nout < 1) return fail(DFFT_EINVAL, "dfft_conv_set_factors: not a multi-output spectral-filter plan");
-    ConvState* c = plan->conv;
-    if (k < 0 || k >= c->nout) return fail(DFFT_EINVAL, "dfft_conv_set_factors: output " + std::to_string(k) + " of " + std::to_string(c->nout));
-    DFFT_HIP_TRY(hipDeviceSynchronize());  // whatever stream produced the vectors, and this plan's executes that read the old tables
-    const size_t    cs = elem_bytes(plan->dtype);
-    const long long ones = std::max({c->fa, c->fb, c->L.ncols}), per = c->fa + c->fb + c->L.ncols;
-    char* const     ta = (char*)c->fact + (size_t)(ones + k * per) * cs;
-    char* const     tb = ta + (size_t)c->fa * cs;
-    char* const     tc = tb + (size_t)c->fb * cs;
-    if (ax) DFFT_HIP_TRY(hipMemcpyAsync(ta, ax, (size_t)plan->N[0] * cs, hipMemcpyDeviceToDevice, plan->stream));
-    if (ay)
-        DFFT_HIP_TRY(hipMemcpyAsync(tb, (const char*)ay + (size_t)plan->sy.start(plan->me) * cs, (size_t)plan->ys * cs, hipMemcpyDeviceToDevice,
-                                    plan->stream));
-    if (az) {
-        DFFT_HIP_TRY(hipMemsetAsync(tc, 0, (size_t)c->L.ncols * cs, plan->stream));
-        DFFT_HIP_TRY(hipMemcpyAsync(tc, az, (size_t)c->nh * cs, hipMemcpyDeviceToDevice, plan->stream));
-    }
-    DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
-    c->M.ax[k] = ax ? ta : c->fact;
-    c->M.by[k] = ay ? tb : c->fact;
-    c->M.cz[k] = az ? tc : c->fact;
-    c->unit[k] = !ax && !ay && !az;
-    return DFFT_OK;
-}
-
-static int conv_check_handle(dfft_plan_t plan, const char* fn) {
-    if (!plan || !plan->conv) return fail(DFFT_EINVAL, std::string(fn) + ": not a spectral-filter plan");
-    return DFFT_OK;
-}
-
-int dfft_conv_set_filter(dfft_plan_t plan, const void* h, int kind) {
-    DFFT_TRY(conv_check_handle(plan, "dfft_conv_set_filter"));
-    if (!h || (kind != DFFT_FILTER_COMPLEX && kind != DFFT_FILTER_REAL)) return fail(DFFT_EINVAL, "dfft_conv_set_filter: null filter or bad kind");
-    ConvState* c = plan->conv;
-    DFFT_HIP_TRY(hipDeviceSynchronize());  // whatever stream produced `h`, and this plan's executes that read the old copy
-    DFFT_TRY(conv_alloc_filter(plan, kind));
-    ConvLaunch R = c->L;
-    R.filter_real = kind == DFFT_FILTER_REAL;
-    R.scale = plan->scale / ((double)plan->N[0] * (double)plan->N[1] * (double)plan->N[2]);
-    if (c->real) DFFT_TRY(check_launch(launch_conv_real_relayout(R, c->nh, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
-    else DFFT_TRY(check_launch(launch_conv_relayout(R, h, c->filt, plan->stream), "dfft_conv_set_filter: re-layout"));
-    DFFT_HIP_TRY(hipStreamSynchronize(plan->stream));
-    c->kind = kind;
-    return DFFT_OK;
-}
-
-int dfft_conv_set_kernel(dfft_plan_t plan, const void* k) {
-    DFFT_TRY(conv_check_handle(plan, "dfft_conv_set_kernel"));
-    if (!k) return fail(DFFT_EINVAL, "dfft_conv_set_kernel: null kernel");
-    ConvState* c = plan->conv;
-    DFFT_HIP_TRY(hipDeviceSynchronize());
-    int arc = conv_alloc_filter(plan, DFFT_FILTER_COMPLEX);
-    if (arc && !plan->exch) return arc;
-    // the plan's own forward half on `k` (collective like an execute), then the forward X transform of the slab it leaves, times
-    // scale / N, straight into the filter copy: the slab's layout is the copy's
-    void* const user_in = c->f->in;
-    c->f->in = const_cast<void*>(k);
-    int rc = dfft_execute(c->f, DFFT_EXEC_NO_TIMING);
-    c->f->in = user_in;
-    if (!rc) rc = arc;
-    if (!rc) rc = conv_x_stage(plan, true, plan->scale / ((double)plan->N[0] * (double)plan->N[1] * (double)plan->N[2]));
-    if (rc) return rc;
-    DFFT_TRY(conv_sync(plan));
-    c->kind = DFFT_FILTER_COMPLEX;
-    return DFFT_OK;
-}
-
-}  // extern "C"
-
-// dfft_plan_create_r2c (any = false) and dfft_plan_create_r2c_any (any = true: the real axis of any dfft_real_form != 0); half != nullptr:
-// a half plan of dfft_plan_create_conv_real, which has checked the arguments (`in` / `out`: the real slabs the R2C half reads / the C2R
-// half writes; the forward half's `out` is the plan's send buffer, NULL without an exchange)
-static int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                      dfft_comm_t comm, int global_idx, int total_devices, unsigned flags, bool any, const R2cHalf* half) {
-    const std::string fn = any ? "dfft_plan_create_r2c_any" : "dfft_plan_create_r2c";
-    if (!plan || !in) return fail(DFFT_EINVAL, fn + ": null plan/in");
-    if (n0 < 1 || n1 < 1 || n2 < 1) return fail(DFFT_EINVAL, fn + ": sizes must be positive");
-    if (dtype != DFFT_F64 && dtype != DFFT_F32) return fail(DFFT_EINVAL, fn + ": dtype");
-    if (direction != DFFT_FORWARD && direction != DFFT_BACKWARD) return fail(DFFT_EINVAL, fn + ": direction");
-    if (total_devices < 1 || global_idx < 0 || global_idx >= total_devices) return fail(DFFT_EINVAL, fn + ": device index");
-    if (total_devices > 1 && !comm) return fail(DFFT_EINVAL, fn + ": a communicator is required for P > 1");
-    if (comm && comm_size(comm) != total_devices) return fail(DFFT_EINVAL, fn + ": communicator size != P");
-    if (!half && (out == nullptr || out == in)) return fail(DFFT_EINVAL, fn + ": real-to-complex plans are out of place (out != NULL, out != in)");
-    if (flags & ~DFFT_PLAN_INPUT_FROM_IN)
-        return fail(DFFT_EUNSUPPORTED, fn + ": only DFFT_PLAN_DEFAULT and DFFT_PLAN_INPUT_FROM_IN are supported "
-                                       "(no OVERLAP, NATURAL or UNFUSED real-to-complex plans)");
-    const int form = any ? real_form(n2) : 1;
-    if (any && form == 0)
-        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) + " -- no real form (at most 2^23, or a four-step length)");
-    if (!any && !real_length_supported(n2))
-        return fail(DFFT_EUNSUPPORTED, fn + ": N2 = " + std::to_string(n2) +
-                                           " -- the real axis must be even with N2/2 a supported length of at most 4096");
-    for (long long n : {n0, n1})
-        if (n > 4096 || !dfft_length_supported(n))
-            return fail(DFFT_EUNSUPPORTED, fn + ": FFT length " + std::to_string(n) +
-                                               " -- N0 and N1 must be single-pass lengths (products of 2, 3, 5, 7 up to 4096)");
-    long long rc_n = 0, cc_n = 0, rc_last = 0, cc_last = 0;
-    if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, global_idx, &rc_n, &cc_n)) return rc;
-    if (int rc = dfft_r2c_counts(n0, n1, n2, total_devices, total_devices - 1, &rc_last, &cc_last)) return rc;
-    long long rc0 = 0, cc0 = 0;
-    (void)dfft_r2c_counts(n0, n1, n2, total_devices, 0, &rc0, &cc0);
-    if (std::max(cc0, cc_last) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, fn + ": more than 2^31 complex elements per device");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, fn + ": no HIP device visible (no CPU fallback)");
-
-    const long long nh = half ? half->nc : n2 / 2 + 1;  // the complex width: what the Y pass, the exchange and the X stage see
-    trace("dfft_plan_create_r2c", n0 * 1000000 + n1 * 1000 + n2 % 1000, (long long)flags * 100 + total_devices);
-    dfft_plan_s* p = new dfft_plan_s;
-    p->r2c = true;
-    p->conv_half = half != nullptr;
-    p->borrowed = half && half->share;
-    p->own_cbuf = p->borrowed && half->own_cbuf;
-    p->n2r = n2;
-    p->real_any = any;
-    p->real_form = form;
-    p->N[0] = n0;
-    p->N[1] = n1;
-    p->N[2] = nh;
-    p->dtype = dtype;
-    p->direction = direction;
-    p->P = total_devices;
-    p->me = global_idx;
-    p->flags = flags;
-    p->is_last = (global_idx == total_devices - 1);
-    p->exch = total_devices > 1;
-    p->sx = make_slab(n0, total_devices);
-    p->sy = make_slab(n1, total_devices);
-    p->xs = p->sx.size(global_idx);
-    p->ys = p->sy.size(global_idx);
-    p->comm = comm;
-    p->grid_x = env_grid("DFFT_X_GRID");
-    p->grid_y = env_grid("DFFT_Y_GRID");
-    p->grid_z = env_grid("DFFT_Z_GRID");
-    p->host_timed = false;
-    for (double& t : p->host_t) t = 0;
-    p->max_count = cc_n;
-    p->in = in;
-    p->out = out;
-    p->inplace = false;
-    p->buf2 = out;
-    p->buf1 = nullptr;
-    p->stream = nullptr;
-    p->chunk_planes = 0;
-    for (auto& e : p->ev) e = nullptr;
-    const size_t cs = elem_bytes(dtype), rs = cs / 2;
-    // the intermediate: rows of nh bins padded to whole 128-byte lines (a pitch of nh alone puts the rows off line alignment)
-    const long long line = 128 / (long long)cs;
-    p->cl.pitch = (nh + line - 1) / line * line;
-    p->cl.plane = n1 * p->cl.pitch;
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess && comm && comm_kind(comm) == 0 && total_devices > 1) {  // as dfft_plan_create: direct pushes to the peers
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess) {
-            for (int d = 0; d < ndev; ++d) {
-                int can = 0;
-                if (d == p->device || hipDeviceCanAccessPeer(&can, p->device, d) != hipSuccess || !can) continue;
-                if (hipDeviceEnablePeerAccess(d, 0) != hipSuccess) (void)hipGetLastError();
-            }
-        }
-    }
-    // bufferDev1: the real slab (R2C) or the complex input (C2R), and the receive buffer of the exchange -- the same size on every rank
-    // (pooled receive buffers of IPC communicators are matched by key and size)
-    // (half plans: a receive buffer alone, and only with a communicator)
-    const size_t b1 = half ? (size_t)conv_real_recv_count(n0, n1, nh, total_devices) * cs : (size_t)std::max({rc0 * rs, cc0 * cs, rc_last * rs, cc_last * cs});
-    const std::string rkey = std::string(half ? "convr:" : "r2c:") + std::to_string(n0) + "x" + std::to_string(n1) + "x" + std::to_string(n2) + ":" +
-                             std::to_string(dtype) + ":" + std::to_string(total_devices) +
-                             (half && half->output > 0 ? ":o" + std::to_string(half->output) : std::string());
-    if (e == hipSuccess && (!half || comm) && comm_recv_alloc(comm, rkey + ":b1", b1, &p->buf1) != DFFT_OK) e = hipErrorOutOfMemory;
-    // the intermediate, also the send buffer of the backward exchange ([N0][ys][nh])
-    const size_t cbytes = (size_t)(half ? p->xs * p->cl.plane : std::max(p->xs * p->cl.plane, n0 * p->ys * nh)) * cs;
-    if (p->borrowed) {
-        p->cbuf = half->share->cbuf;
-        p->stream = half->share->stream;
-        if (p->own_cbuf) {
-            p->cbuf = nullptr;
-            if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
-        }
-    } else {
-        if (e == hipSuccess) e = hipMalloc(&p->cbuf, cbytes);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    }
-    // input captured at plan time, on the plan's stream (see dfft_plan_create); exactly the caller's elements, nothing beyond them
-    const size_t ibytes = direction == DFFT_FORWARD ? (size_t)rc_n * rs : (size_t)(p->ys * nh * n0) * cs;
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && !half) e = hipMemcpyAsync(p->buf1, in, ibytes, hipMemcpyDeviceToDevice, p->stream);
-    // (half plans capture nothing.  Their intermediate is cleared ONCE: its columns n2/2 + 1 .. nc - 1 and its row padding are never
-    // written with anything but zeros afterwards -- the argument is at the top of dfft_conv_real.hip)
-    if (e == hipSuccess && half && (!p->borrowed || p->own_cbuf)) e = hipMemsetAsync(p->cbuf, 0, cbytes, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    for (auto& ev : p->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) {
-        dfft_plan_destroy(p);
-        return fail(DFFT_EHIP, fn + ": " + hipGetErrorString(e));
-    }
-    fill_exchange(p, p->xd, direction);  // at width nh
-    p->xd.sendbuf = direction == DFFT_FORWARD ? p->buf2 : p->cbuf;
-    p->xd.recvbuf = p->buf1;
-    p->xd.slot = p->xd2.slot = -1;
-    if (comm) {
-        const int rc = comm_register(comm, global_idx, p->xd.recvbuf, p->device, &p->xd.slot);
-        if (rc) {
-            dfft_plan_destroy(p);
-            return rc;
-        }
-    }
-    {
-        // Z+Y blocking for the 256 MiB Infinity Cache, sized on the intermediate's planes (the rule of two-launch C2C plans); DFFT_CHUNK_MB /
-        // DFFT_CHUNK_PLANES as there
-        long long   mb = 256;
-        const char* ce = getenv("DFFT_CHUNK_MB");
-        if (ce) mb = atoll(ce);
-        if (mb > 0) {
-            const long long plane_b = p->cl.plane * (long long)cs;
-            long long       fit = std::max(1ll, (mb << 20) / plane_b);
-            if (plane_b >= (8ll << 20) && fit > 1) --fit;
-            const long long nchunks = std::max(1ll, (p->xs + fit - 1) / fit);
-            p->chunk_planes = (p->xs + nchunks - 1) / nchunks;
-        }
-        const char* cpe = getenv("DFFT_CHUNK_PLANES");
-        if (cpe && atoll(cpe) > 0) p->chunk_planes = atoll(cpe);
-        if (p->chunk_planes >= p->xs) p->chunk_planes = 0;
-    }
-    if (form != 1) {
-        // the two-for-one rows: Bluestein tables (n2 of kind 3) and the scratch of one cache chunk of rows
-        p->rfused = bluestein_fused_env();
-        if (length_kind(n2) == 3) {
-            const int rc = bluestein_tables(n2, dtype, direction, &p->rtab);
-            if (rc) {
-                dfft_plan_destroy(p);
-                return rc;
-            }
-        }
-        const long long rows = (p->chunk_planes > 0 ? p->chunk_planes : p->xs) * n1;
-        p->rscratch_bytes = real_pair_scratch_bytes(n2, dtype, rows, p->rtab.get(), p->rfused);
-        if (p->rscratch_bytes && (e = hipMalloc(&p->rscratch, p->rscratch_bytes)) != hipSuccess) {
-            dfft_plan_destroy(p);
-            return fail(DFFT_EHIP, fn + ": scratch of the real rows: " + hipGetErrorString(e));
-        }
-    }
-    // warm the twiddle caches so execute never allocates (form 3: the Bluestein tables above; four-step factors on first use)
-    std::vector<long long> warm{n0, n1};
-    if (form == 1) warm.insert(warm.end(), {n2 / 2, n2});
-    if (form == 2) warm.push_back(n2);
-    for (long long n : warm) {
-        const void* tw;
-        const int   rc = get_twiddles((int)n, dtype, &tw);
-        if (rc) {
-            dfft_plan_destroy(p);
-            return rc;
-        }
-    }
-    *plan = p;
-    return DFFT_OK;
-}
-
-extern "C" {
-
-int dfft_real_form(long long n) { return real_form(n); }
-
-int dfft_plan_create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                         dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
-    return create_r2c(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, false);
-}
-
-int dfft_plan_create_r2c_any(dfft_plan_t* plan, long long n0, long long n1, long long n2, int dtype, int direction, void* in, void* out,
-                             dfft_comm_t comm, int global_idx, int total_devices, unsigned flags) {
-    return create_r2c(plan, n0, n1, n2, dtype, direction, in, out, comm, global_idx, total_devices, flags, true);
 }
 
 int dfft_plan_set_scale(dfft_plan_t plan, double s) {
@@ -2873,20 +1080,14 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
     // exchange queues this execute all the same (on the two-launch stage) and reports afterwards: returning early on ONE rank would
     // leave its peers waiting in the exchange for a partner that never comes.
     const int   zrc0 = zy_check(plan);
-    std::string zmsg0 = zrc0 ? g_last_error : std::string();
+    std::string zmsg0 = zrc0 ? last_error() : std::string();
     if (zrc0 && !plan->exch) return zrc0;
     auto run = [&]() {
-        t_plan_scratch = plan->lbuf;
-        t_plan_zgrid = plan->grid_z;
-        t_plan_bs = plan->bs.tables.empty() ? nullptr : &plan->bs;
-        const int r = plan->r2c ? execute_r2c(plan, sync)
-                      : (plan->flags & DFFT_PLAN_NATURAL) ? execute_natural(plan, sync)
-                      : plan->direction == DFFT_FORWARD ? execute_forward(plan, sync)
-                                                        : execute_backward(plan, sync);
-        t_plan_scratch = nullptr;
-        t_plan_zgrid = 0;
-        t_plan_bs = nullptr;
-        return r;
+        const ExecutingPlan scope(plan);  // the passes run with this plan's scratch, grid cap and Bluestein tables
+        return plan->r2c ? execute_r2c(plan, sync)
+               : (plan->flags & DFFT_PLAN_NATURAL) ? execute_natural(plan, sync)
+               : plan->direction == DFFT_FORWARD ? execute_forward(plan, sync)
+                                                 : execute_backward(plan, sync);
     };
     const bool zy_used = plan->zy_on;
     if (plan->P > 1) trace("dfft_execute", plan->direction, exec_flags);
@@ -2907,11 +1108,11 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
         // Every device of the communicator learns of it here, returns an error and continues on the two-launch stage, so no rank
         // ever returns DFFT_OK for an execute that any rank knows to be invalid.
         const int   run_rc = rc;
-        std::string run_msg = run_rc ? g_last_error : std::string();
+        std::string run_msg = run_rc ? last_error() : std::string();
         int         mine = (zrc0 || run_rc) ? 1 : 0;
         if (!mine && zy_used) {
             mine = zy_check(plan) ? 1 : 0;
-            if (mine) zmsg0 = g_last_error;
+            if (mine) zmsg0 = last_error();
         }
         int any = 0;
         rc = comm_agree_max(plan->comm, plan->me, mine, plan->stream, &any);
@@ -2951,178 +1152,6 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
         printf("t0: %lf, t1: %lf, t2: %lf, t3: %lf, total: %lf\n", t[0], t[1], t[2], t[3], t[0] + t[1] + t[2] + t[3]);
     }
     return DFFT_OK;
-}
-
-// X-pass kernel of the plan alone on hand-over buffer `w` (forward: w -> result buffer, backward: source -> w): median of
-// five timed launches after two warm-up launches, in ms.  Results are garbage (w is not initialised); only the addresses matter.
-static int probe_x_pass(dfft_plan_s* p, void* w, float* ms_out) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    DFFT_HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(DFFT_EHIP, "dfft_plan_tune: cannot create events");
-    }
-    float t[5];
-    int   rc = DFFT_OK;
-    for (int i = 0; i < 7 && rc == DFFT_OK; ++i) {
-        hipError_t e = hipEventRecord(e0, p->stream);
-        if (e == hipSuccess) {
-            if (p->direction == DFFT_FORWARD) rc = launch_x(p, w, p->buf2, false, 0, &p->wl);
-            else rc = launch_x(p, (p->flags & DFFT_PLAN_INPUT_FROM_IN) ? p->in : p->buf1, w, false, 0, &p->wl);
-        }
-        if (e == hipSuccess && rc == DFFT_OK) e = hipEventRecord(e1, p->stream);
-        if (e == hipSuccess && rc == DFFT_OK) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess && rc == DFFT_OK) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess && rc == DFFT_OK) rc = fail(DFFT_EHIP, std::string("dfft_plan_tune: ") + hipGetErrorString(e));
-        if (i >= 2) t[i - 2] = ms;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    std::sort(t, t + 5);
-    *ms_out = t[2];
-    return DFFT_OK;
-}
-
-int dfft_plan_tune(dfft_plan_t plan) {
-    if (!plan) return fail(DFFT_EINVAL, "dfft_plan_tune: null plan");
-    if (plan->conv) return DFFT_OK;  // the X stage works in place: no read / write placement to choose
-    const char* te = getenv("DFFT_TUNE");
-    if (te && *te == '0') return DFFT_OK;
-    // only fused single-GPU plans with a hand-over buffer have anything to place
-    if (plan->exch || !plan->wbuf || (plan->flags & (DFFT_PLAN_NATURAL | DFFT_PLAN_UNFUSED))) return DFFT_OK;
-    dfft_plan_s* p = plan;
-    // plan-time call: wait for the whole device, not only for the plan's stream -- the caller may have filled `out` on a stream of
-    // its own (the contents are set aside below and put back at the end; seen as a lost update in the GPU suite of round 4)
-    DFFT_HIP_TRY(hipDeviceSynchronize());
-    const size_t wbytes = (size_t)p->xs * p->wl.plane * elem_bytes(p->dtype);
-    // Candidates: the current buffer, then fresh allocations of the same size, ALL kept until the end.  The driver hands out
-    // device memory block by block (runs of 2 ... 36 consecutive 2 GiB allocations behave alike, then the behaviour flips:
-    // tools/xprobe.hip census, profiles/r03/experiments/xprobe_census_*.log, placement_state.log), so every allocation that stays
-    // alive moves the next one on, and walking densely cannot step over a short run the way a few large strides can (an
-    // earlier version placed seven candidates behind spacers of 8 ... 64 GiB; on some boxes all of them behaved like the first
-    // one: experiments/tune_check_final.log).  The walk ends at the first candidate that is 3 % away from another one (the two
-    // behaviours are 5-8 % apart), after DFFT_TUNE_TRIES candidates (default 128), or when the transient footprint would exceed
-    // 70 % of the free device memory; one probe costs about 7 X passes.  DFFT_TUNE_SPACER_MB puts a spacer in front of every
-    // candidate (coarser, further-reaching walk).
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        free_b = total_b = 0;
-    }
-    // a process that finds at least 90 % of the device's memory free has the GPU to itself: the long walk (what bench.py asks for
-    // explicitly) -- the drop-in CLI then lands in the fast mode as reliably as the benchmark does; otherwise the short, polite one
-    const bool  alone = total_b > 0 && free_b >= total_b / 10 * 9;
-    int         max_tries = alone ? 128 : 32;
-    const char* mt = getenv("DFFT_TUNE_TRIES");
-    if (mt && atoi(mt) > 0) max_tries = atoi(mt);
-    size_t      spacer_bytes = 0;
-    const char* sm = getenv("DFFT_TUNE_SPACER_MB");
-    if (sm && atoll(sm) > 0) spacer_bytes = (size_t)atoll(sm) << 20;
-    // transient footprint: at most a quarter of the free device memory by default (DFFT_TUNE_MEM_PCT, 1 ... 90) -- other plans and
-    // processes share the GPU -- and 70 % when this process has the GPU to itself (above)
-    int         pct = alone ? 70 : 25;
-    const char* pe = getenv("DFFT_TUNE_MEM_PCT");
-    if (pe && atoi(pe) >= 1 && atoi(pe) <= 90) pct = atoi(pe);
-    const size_t budget = free_b / 100 * (size_t)pct;
-    // The probe launches of a forward plan write (garbage) into the plan's result buffer -- the caller's `out`, which the
-    // reference's plan creation never touches (fft_mpi_3d_api.cpp:41-141): its contents are set aside and put back.  Without
-    // room for that copy nothing is tuned.
-    void*        saved_out = nullptr;
-    const size_t out_bytes = (size_t)p->max_count * elem_bytes(p->dtype);
-    if (p->direction == DFFT_FORWARD) {
-        if (out_bytes + wbytes > budget || hipMalloc(&saved_out, out_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return DFFT_OK;
-        }
-        if (hipMemcpyAsync(saved_out, p->buf2, out_bytes, hipMemcpyDeviceToDevice, p->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(saved_out);
-            return DFFT_OK;
-        }
-    }
-    auto restore_out = [&]() {
-        if (!saved_out) return;
-        (void)hipMemcpyAsync(p->buf2, saved_out, out_bytes, hipMemcpyDeviceToDevice, p->stream);
-        (void)hipStreamSynchronize(p->stream);
-        (void)hipFree(saved_out);
-        saved_out = nullptr;
-    };
-    std::vector<void*> cand(1, p->wbuf), spacers;
-    p->w_ms.clear();
-    float ms = 0.f;
-    int   rc = probe_x_pass(p, p->wbuf, &ms);
-    if (rc) {
-        restore_out();
-        return rc;
-    }
-    p->w_ms.push_back(ms);
-    float  lo = ms, hi = ms;
-    size_t used = saved_out ? out_bytes : 0;
-    while ((int)cand.size() < max_tries && used + spacer_bytes + wbytes <= budget) {
-        if (lo < 0.97f * hi) {
-            // Both behaviours seen?  The two classes are 5-8 % apart, but single probes of ONE class have been seen 3.5 % apart (round 4,
-            // profiles/r04/experiments/tune_check_false_stop.log: 0.7841 / 0.8027 / 0.7749 ms, all slow -- the walk stopped there and the
-            // bench process ran at 1.94 instead of 1.87 ms).  So the fastest and the slowest candidate are timed once more, each keeps its
-            // lower figure (a probe reads high more often than low), and only a confirmed gap ends the walk.
-            int ilo = 0, ihi = 0;
-            for (int i = 1; i < (int)p->w_ms.size(); ++i) {
-                if (p->w_ms[i] < p->w_ms[ilo]) ilo = i;
-                if (p->w_ms[i] > p->w_ms[ihi]) ihi = i;
-            }
-            for (int idx : {ilo, ihi}) {
-                float again = 0.f;
-                if (probe_x_pass(p, cand[idx], &again) == DFFT_OK && again > 0.f) p->w_ms[idx] = std::min(p->w_ms[idx], again);
-            }
-            lo = *std::min_element(p->w_ms.begin(), p->w_ms.end());
-            hi = *std::max_element(p->w_ms.begin(), p->w_ms.end());
-            if (lo < 0.965f * hi) break;  // confirmed: keep the fast one
-        }
-        void *sp = nullptr, *nw = nullptr;
-        if (spacer_bytes > 0) {
-            if (hipMalloc(&sp, spacer_bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                break;
-            }
-            spacers.push_back(sp);
-        }
-        if (slab_alloc(&nw, wbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            break;
-        }
-        used += spacer_bytes + wbytes;
-        cand.push_back(nw);
-        rc = probe_x_pass(p, nw, &ms);
-        if (rc) break;
-        p->w_ms.push_back(ms);
-        lo = std::min(lo, ms);
-        hi = std::max(hi, ms);
-    }
-    (void)hipStreamSynchronize(p->stream);
-    for (void* sp : spacers) (void)hipFree(sp);
-    // w_ms[i] belongs to candidate i (a failed probe leaves one candidate without an entry)
-    int best = 0;
-    for (int i = 1; i < (int)p->w_ms.size(); ++i)
-        if (p->w_ms[i] < 0.985f * p->w_ms[best]) best = i;  // a later candidate must be clearly faster
-    (void)hipStreamSynchronize(p->stream);
-    for (int i = 0; i < (int)cand.size(); ++i)
-        if (i != best) (void)slab_free(cand[i]);
-    p->wbuf = cand[best];
-    p->w_kept = best;
-    if (rc) {
-        restore_out();
-        return rc;
-    }
-    // the kept buffer once more, now that its neighbours are gone (reported, not acted upon)
-    rc = probe_x_pass(p, p->wbuf, &p->w_final_ms);
-    restore_out();
-    if (getenv("DFFT_DEBUG")) {
-        fprintf(stderr, "[dfft] hand-over buffer placement: X pass");
-        for (float v : p->w_ms) fprintf(stderr, " %.4f", v);
-        fprintf(stderr, " ms, kept candidate %d (%.4f ms when re-timed)\n", p->w_kept, p->w_final_ms);
-    }
-    return rc;
 }
 
 int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
@@ -3165,16 +1194,6 @@ int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
                  fused ? "fused" : "multi-pass");
     }
     return DFFT_OK;
-}
-
-int dfft_plan_tune_report(dfft_plan_t plan, int max_n, double* ms, int* kept, double* final_ms) {
-    if (!plan || max_n < 0) return fail(DFFT_EINVAL, "dfft_plan_tune_report: bad arguments");
-    const int n = (int)plan->w_ms.size();
-    for (int i = 0; i < n && i < max_n; ++i)
-        if (ms) ms[i] = plan->w_ms[i];
-    if (kept) *kept = plan->w_kept;
-    if (final_ms) *final_ms = plan->w_final_ms;
-    return n;
 }
 
 int dfft_plan_sync(dfft_plan_t plan) {
@@ -3277,589 +1296,6 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     if (plan->zy_err) hipHostFree(plan->zy_err);
     delete plan;
     return zy_rc;
-}
-
-int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_fft1d_rows: bad arguments");
-    if (!dfft_length_supported(n)) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_rows: unsupported length");
-    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * elem_bytes(dtype)))
-        return fail(DFFT_EINVAL, "dfft_fft1d_rows: in and out overlap partly (the transform runs out of place or exactly in place)");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_rows: no HIP device visible (no CPU fallback)");
-    return fft_rows(in, out, (int)n, batch, dtype, direction, (hipStream_t)stream);
-}
-
-// ---- batched 2D transform: the plan's t0 stage as an entry point of its own ------------------------------------
-// Planes per group of `batch` planes of plane_b bytes that fit the 256 MiB Infinity Cache (dfft_plan_create's rule for single-GPU plans:
-// one plane less per group from 8 MiB planes on, groups of equal size): the column pass then reads what the row pass wrote from the cache.
-static long long cache_plane_group(long long batch, long long plane_b) {
-    if (batch * plane_b <= (256ll << 20)) return batch;
-    long long fit = std::max(1ll, (256ll << 20) / plane_b);
-    if (plane_b >= (8ll << 20) && fit > 1) --fit;
-    const long long nchunks = std::max(1ll, (batch + fit - 1) / fit);
-    return (batch + nchunks - 1) / nchunks;
-}
-
-// State of the one-launch stage for one (device, stream, plane shape, structure): the kernel's control block, its pinned error word and
-// the host's running ticket / execute counters (dfft_zy.hip) -- what a plan keeps in dfft_plan_s, cached here because the call is
-// plan-less.  Freed by dfft_trim().
-namespace {
-struct Zy2dCtx {
-    ZyCtl*    ctl = nullptr;
-    unsigned* err = nullptr;
-    unsigned  ticket = 0, execs = 0;
-    long long batch = 0;    // planes of the last launch on this context (0: none since the control block was zeroed)
-    bool      off = false;  // a launch gave up: this context stays on two launches per chunk
-};
-struct Zy2dKey {
-    int         dev;
-    hipStream_t stream;
-    int         n1, n2, sign;
-    bool        operator<(const Zy2dKey& o) const { return std::tie(dev, stream, n1, n2, sign) < std::tie(o.dev, o.stream, o.n1, o.n2, o.sign); }
-};
-std::mutex                 g_zy2d_mutex;
-std::map<Zy2dKey, Zy2dCtx> g_zy2d;
-
-void zy2d_trim() {
-    std::lock_guard<std::mutex> lk(g_zy2d_mutex);
-    int                         cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto& kv : g_zy2d) {
-        (void)hipSetDevice(kv.first.dev);
-        (void)hipDeviceSynchronize();
-        if (kv.second.ctl) (void)hipFree(kv.second.ctl);
-        if (kv.second.err) (void)hipHostFree(kv.second.err);
-    }
-    g_zy2d.clear();
-    (void)hipSetDevice(cur);
-}
-}  // namespace
-
-// `batch` planes of [n1][n2] (n2 contiguous), each transformed along both axes; in place (out == in) or out of place (`in` is left
-// untouched).  What a 3D plan runs as t0 (reference fftZY, fft_mpi_3d_api.cpp:466-522; templateFFT's FFTDim = 2 application,
-// templateFFT.cpp:5767): planes are taken in groups that fit the 256 MiB Infinity Cache, so the column pass reads what the row pass
-// wrote from the cache, and plane shapes the one-launch stage is built for (dfft_zy.hip: fp64, n1 in {256, 512, 768 (n2 = 512)}, n2 in
-// {256, 512}) run as ONE persistent launch.  Forward: rows n2 then columns n1; backward: the same order with conjugated twiddles
-// (the two 1-D transforms of a plane commute).  Un-normalised.
-int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || n1 < 1 || n2 < 1 || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_fft2d_batch: bad arguments");
-    if (!dfft_length_supported(n1) || !dfft_length_supported(n2)) return fail(DFFT_EUNSUPPORTED, "dfft_fft2d_batch: unsupported length");
-    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n1 * (uintptr_t)n2 * elem_bytes(dtype)))
-        return fail(DFFT_EINVAL, "dfft_fft2d_batch: in and out overlap partly (the transform runs out of place or exactly in place)");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft2d_batch: no HIP device visible (no CPU fallback)");
-    if (batch == 0) return DFFT_OK;
-    hipStream_t     s = (hipStream_t)stream;
-    const long long plane = n1 * n2, plane_b = plane * (long long)elem_bytes(dtype);
-    if (n1 > 4096 || n2 > 4096 || plane >= (1ll << 31)) {  // four-step axes: whole-buffer passes on the 1-D entry points
-        int rc = dfft_fft1d_rows(in, out, n2, n1 * batch, dtype, direction, stream);
-        if (rc == DFFT_OK) rc = dfft_fft1d_cols(out, out, n1, n2, batch, dtype, direction, stream);
-        return rc;
-    }
-    static const bool one_launch_off = [] {
-        const char* e = getenv("DFFT_T0_ONE_LAUNCH");
-        return e && *e == '0';
-    }();
-    // ---- one persistent launch
-    if (!one_launch_off && zy_supported(dtype, (int)n1, (int)n2) && batch <= ZY_MAX_PLANES) {
-        int dev = 0;
-        DFFT_HIP_TRY(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(g_zy2d_mutex);
-        Zy2dCtx&                    c = g_zy2d[Zy2dKey{dev, s, (int)n1, (int)n2, direction}];
-        if (!c.off && !c.ctl) {
-            // (zeroed on the caller's stream and waited for, like a plan's: dfft_plan_create)
-            if (hipMalloc((void**)&c.ctl, sizeof(ZyCtl)) != hipSuccess || hipMemsetAsync(c.ctl, 0, sizeof(ZyCtl), s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess || hipHostMalloc((void**)&c.err, 128, hipHostMallocMapped) != hipSuccess) {
-                (void)hipGetLastError();
-                if (c.ctl) (void)hipFree(c.ctl);
-                c.ctl = nullptr;
-                c.off = true;
-            } else {
-                *c.err = 0u;
-            }
-        }
-        if (!c.off && *(volatile unsigned*)c.err != 0u) {
-            c.off = true;  // sticky on the device side too: every later launch on this block would return at once
-            return fail(DFFT_EHIP, "dfft_fft2d_batch: an earlier one-launch YZ stage on this stream gave up; the results of that call and of every call queued "
-                                   "behind it are invalid, later calls use two launches per chunk");
-        }
-        if (!c.off) {
-            const void *twz = nullptr, *twy = nullptr;
-            DFFT_TRY(get_twiddles((int)n2, dtype, &twz));
-            DFFT_TRY(get_twiddles((int)n1, dtype, &twy));
-            ZyLaunch L;
-            std::memset(&L, 0, sizeof(L));
-            L.dtype = dtype;
-            L.n1 = (int)n1;
-            L.n2 = (int)n2;
-            L.dir = +1;  // rows first in both directions (the inverse: SIGN = -1, dfft_zy.hip)
-            L.sign = direction;
-            L.src = in;
-            L.w = out;
-            L.dst = nullptr;
-            L.src_plane = L.w_plane = L.dst_plane = plane;
-            DFFT_ZY_SET_PITCH(L, n2);
-            L.plane0 = 0;
-            L.nplanes = batch;
-            const long long fit = std::max(1ll, (230ll << 20) / plane_b), nch = (batch + fit - 1) / fit;
-            L.chunk = batch * plane_b <= (256ll << 20) ? batch : (batch + nch - 1) / nch;  // zy_phase_planes
-            L.ctl = c.ctl;
-            L.twz = twz;
-            L.twy = twy;
-            L.lazy = 1;
-            static const unsigned polls = [] {
-                const char* sp = getenv("DFFT_ZY_SPIN_POLLS");
-                return sp && atoll(sp) > 0 ? (unsigned)std::min(atoll(sp), 0xffffffffll) : (4u << 20);
-            }();
-            L.spin_polls = polls;
-            if (hipHostGetDevicePointer((void**)&L.err_host, c.err, 0) != hipSuccess) return fail(DFFT_EHIP, "dfft_fft2d_batch: no device pointer for the error word");
-            // done_base = execs x producers holds only while every earlier launch on this block covered planes [0, batch): each one
-            // added `producers` to done[p] of exactly those planes.  A plan always launches all of its planes, so its counters never
-            // drift; this entry point takes any batch, so when the batch changes the control block is zeroed on the caller's stream
-            // (stream order puts that behind every earlier launch of this context) and the host counters restart from 0.
-            if (c.batch != batch) {
-                if (c.batch != 0 && hipMemsetAsync(c.ctl, 0, sizeof(ZyCtl), s) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(DFFT_EHIP, "dfft_fft2d_batch: cannot reset the control block of the one-launch YZ stage");
-                }
-                c.ticket = 0;
-                c.execs = 0;
-                c.batch = batch;
-            }
-            unsigned producers = 0;
-            (void)zy_units_per_plane(L.n1, L.n2, L.dir, 0, &producers);
-            L.ticket_base = c.ticket;
-            L.done_base = c.execs * producers;
-            ++c.execs;
-            c.ticket += zy_tickets(L.n1, L.n2, L.dir, 0, L.nplanes, L.chunk);
-            return check_launch(launch_zy(L, s), "dfft_fft2d_batch (one-launch YZ stage)");
-        }
-    }
-    // ---- two launches per Infinity-Cache chunk (dfft_plan_create's rule for single-GPU plans)
-    const long long cp = cache_plane_group(batch, plane_b);
-    const void* twy = nullptr;
-    DFFT_TRY(get_twiddles((int)n1, dtype, &twy));
-    const bool chunked = cp < batch;
-    for (long long x0 = 0; x0 < batch; x0 += cp) {
-        const long long nx = std::min(cp, batch - x0);
-        DFFT_TRY(fft_rows(in, out, (int)n2, nx * n1, dtype, direction, s, x0 * n1, (chunked && in != out) ? FFT_HINT_STREAM_IN : 0));
-        FftLaunch L;
-        std::memset(&L, 0, sizeof(L));
-        L.dtype = dtype;
-        L.n = (int)n1;
-        L.dir = direction;
-        L.cols = 1;
-        L.in = out;
-        L.out = out;
-        L.tw = twy;
-        L.imap = L.omap = plain_axis(n1, n2, 1);
-        L.itile = L.otile = TileMap{plane, 1};
-        L.na = nx;
-        L.a_first = x0;
-        L.ncols = (int)n2;
-        DFFT_TRY(check_launch(launch_fft(L, s), "dfft_fft2d_batch (columns)"));
-    }
-    return DFFT_OK;
-}
-
-// Did a one-launch stage of dfft_fft2d_batch on (current device, stream) give up?  Meant for after the caller has waited for the stream:
-// it reads the pinned error words the kernels write.  A failure reported here is reported once -- the context then stays on two
-// launches per chunk, and the next call on it does not report it again.
-int dfft_fft2d_batch_status(void* stream) {
-    int dev = 0;
-    DFFT_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_zy2d_mutex);
-    for (auto& kv : g_zy2d) {
-        Zy2dCtx& c = kv.second;
-        if (kv.first.dev != dev || kv.first.stream != (hipStream_t)stream || c.off || !c.err || *(volatile unsigned*)c.err == 0u) continue;
-        c.off = true;
-        return fail(DFFT_EHIP, "dfft_fft2d_batch: a one-launch YZ stage on this stream gave up (" + std::string(*c.err == ZY_ERR_DESYNC ? "control block out of step" : "timed out") +
-                                   ", " + std::to_string(kv.first.n1) + "x" + std::to_string(kv.first.n2) + "); the results of that call and of every call queued "
-                                   "behind it are invalid, later calls use two launches per chunk");
-    }
-    return DFFT_OK;
-}
-
-int dfft_trim(void) {
-    long_scratch_trim();
-    bluestein_trim();
-    r2r_trim();
-    zy2d_trim();
-    return DFFT_OK;
-}
-
-int dfft_scale(void* data, long long count, int dtype, double s, void* stream) {
-    if (!data || count < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32)) return fail(DFFT_EINVAL, "dfft_scale: bad arguments");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_scale: no HIP device visible (no CPU fallback)");
-    hipError_t e = launch_scale(dtype, data, count, s, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_scale: ") + hipGetErrorString(e));
-    return DFFT_OK;
-}
-
-int dfft_fft1d_any(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || batch < 0 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_fft1d_any: bad arguments");
-    const int kind = length_kind(n);
-    if (kind == 0) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_any: length " + std::to_string(n) + " is outside every form (at most 2^23, or a four-step length)");
-    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * (uintptr_t)s * elem_bytes(dtype)))
-        return fail(DFFT_EINVAL, "dfft_fft1d_any: in and out overlap partly (the transform runs out of place or exactly in place)");
-    if (kind != 3)  // single-pass and four-step lengths: exactly the existing entry points
-        return s == 1 ? dfft_fft1d_rows(in, out, n, batch, dtype, direction, stream) : dfft_fft1d_cols(in, out, n, s, batch, dtype, direction, stream);
-    if (!any_extent_ok(n, s, dtype, aligned16(in), aligned16(out))) return fail(DFFT_EUNSUPPORTED, extent_message("dfft_fft1d_any", n, s));
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_any: no HIP device visible (no CPU fallback)");
-    if (batch == 0) return DFFT_OK;
-    return bluestein_pass(in, out, n, s, batch, dtype, direction, 1.0, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- shared by dfft_rfft1d, dfft_rfft1d_strided and dfft_rfft2d_batch ------------------------------------------------------------------
-// A caller that needs the per-(device, stream) scratch for more than one step at a time (dfft_rfft2d_batch's inverse: the bins of a plane
-// group and the scratch of the transforms on them) takes ONE lease for all of it -- the lease is not re-entrant -- so these helpers size
-// their scratch first (*_prepare) and then run on whatever scratch they are given (*_run).
-
-// Real rows of dfft_rfft1d: `rows` rows of n reals <-> n/2 + 1 bins.  in_is_scratch: the C2R input is the caller's own scratch, which
-// the two-launch C2R form of real form 1 may merge in place on (no copy into scratch first).
-struct RealRowsPass {
-    long long          n, chunk;  // rows per launch
-    int                dtype, dir, form;
-    bool               copy;      // form 1 C2R with n/2 untuned: the bins go through scratch first
-    BluesteinTablesPtr t;         // forms 2 / 3 with a Bluestein n
-    bool               bs_fused;
-    size_t             need;      // scratch bytes
-};
-static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, RealRowsPass* R) {
-    const size_t    cs = elem_bytes(dtype);
-    const long long nh = n / 2 + 1;
-    // rows as one plane: real pitch n, complex pitch nh; at most 2^30 rows per launch (an even count: pairs never straddle two calls)
-    const long long max_rows = 1ll << 30;
-    R->n = n;
-    R->dtype = dtype;
-    R->dir = dir;
-    R->form = real_form(n);
-    R->t.reset();
-    R->bs_fused = true;
-    R->copy = false;
-    R->chunk = max_rows;
-    R->need = 0;
-    if (R->form == 1) {
-        // the half-length kernels; their two-launch C2R form (n/2 without a tuned plan) merges in place on its input, so the bins go
-        // through the per-(device, stream) scratch first, in chunks of at most 256 MiB
-        R->copy = dir != DFFT_FORWARD && !fft_length_tuned((int)(n / 2)) && !in_is_scratch;
-        if (R->copy) {
-            R->chunk = std::max(1ll, std::min(max_rows, (long long)((256ll << 20) / (nh * (long long)cs))));
-            R->need = (size_t)std::min(R->chunk, rows) * nh * cs;
-        }
-        return DFFT_OK;
-    }
-    // two-for-one pairs: the cached Bluestein tables of (n, dtype, direction) for Bluestein lengths
-    if (length_kind(n) == 3)
-        if (int rc = bluestein_tables(n, dtype, dir, &R->t)) return rc;
-    R->bs_fused = bluestein_fused_env();
-    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), R->t.get(), R->bs_fused);
-    return DFFT_OK;
-}
-static int real_rows_run(const RealRowsPass& R, const void* in, void* out, long long rows, void* scr, hipStream_t st) {
-    const bool      fwd = R.dir == DFFT_FORWARD;
-    const long long n = R.n, nh = n / 2 + 1;
-    const size_t    cs = elem_bytes(R.dtype), rs = cs / 2;
-    int             rc = DFFT_OK;
-    for (long long b0 = 0; b0 < rows && rc == DFFT_OK; b0 += R.chunk) {
-        const long long m = std::min(R.chunk, rows - b0);
-        const void*     ip = (const char*)in + (size_t)b0 * (fwd ? n * rs : nh * cs);
-        void*           op = (char*)out + (size_t)b0 * (fwd ? nh * cs : n * rs);
-        if (R.form == 1) {
-            RealLaunch L;
-            std::memset(&L, 0, sizeof(L));
-            L.dtype = R.dtype;
-            L.n2 = (int)n;
-            L.dir = R.dir;
-            L.in = ip;
-            L.out = op;
-            L.rows = m;
-            L.rows_per_plane = m;
-            L.rpitch = n;
-            L.rplane = m * n;
-            L.cpitch = nh;
-            L.cplane = m * nh;
-            L.scale = 1.0;
-            if (R.copy) {
-                const hipError_t e = hipMemcpyAsync(scr, L.in, (size_t)m * nh * cs, hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) rc = fail(DFFT_EHIP, std::string("dfft_rfft1d: ") + hipGetErrorString(e));
-                L.in = scr;
-            }
-            if (rc == DFFT_OK) rc = check_launch(launch_real_rows(L, st), fwd ? "dfft_rfft1d (R2C rows)" : "dfft_rfft1d (C2R rows)");
-        } else {
-            RealPairLaunch P;
-            std::memset(&P, 0, sizeof(P));
-            P.dtype = R.dtype;
-            P.n = n;
-            P.dir = R.dir;
-            P.in = ip;
-            P.out = op;
-            P.rows = m;
-            P.rows_per_plane = m;
-            P.rpitch = n;
-            P.rplane = m * n;
-            P.cpitch = nh;
-            P.cplane = m * nh;
-            rc = real_pair_rows(P, R.t.get(), R.bs_fused, scr, R.need, st);
-        }
-    }
-    return rc;
-}
-
-// dfft_fft1d_any's transforms of [batch][n][s] on caller-provided scratch (the four-step and Bluestein forms need some; dfft_fft1d_any
-// itself leases it inside dfft_fft1d_rows / dfft_fft1d_cols / bluestein_pass)
-struct AnyPass {
-    long long          n, s;
-    int                dtype, dir, kind;
-    BluesteinTablesPtr t;
-    bool               bs_fused;
-    size_t             need;
-};
-static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, AnyPass* A) {
-    A->n = n;
-    A->s = s;
-    A->dtype = dtype;
-    A->dir = dir;
-    A->kind = length_kind(n);
-    A->t.reset();
-    A->bs_fused = bluestein_fused_env();
-    A->need = A->kind == 2 ? (size_t)batch * n * s * elem_bytes(dtype) : 0;
-    if (A->kind == 3) {
-        if (int rc = bluestein_tables(n, dtype, dir, &A->t)) return rc;
-        A->need = bluestein_scratch_bytes(*A->t, s, batch, A->bs_fused);
-    }
-    return DFFT_OK;
-}
-static int any_run(const AnyPass& A, const void* in, void* out, long long batch, void* scr, hipStream_t st) {
-    if (A.kind == 3) return bluestein_fft(*A.t, in, out, A.s, batch, 1.0, A.bs_fused, scr, A.need, st);
-    if (A.kind == 2) return long_fft(in, out, A.n, A.s, batch, A.dtype, A.dir, 1.0, scr, st);
-    return A.s == 1 ? dfft_fft1d_rows((void*)in, out, A.n, batch, A.dtype, A.dir, st) : dfft_fft1d_cols((void*)in, out, A.n, A.s, batch, A.dtype, A.dir, st);
-}
-
-extern "C" {
-
-int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_rfft1d: bad arguments");
-    const int form = real_form(n);
-    if (form == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft1d: length " + std::to_string(n) + " has no real form (at most 2^23, or a four-step length)");
-    const bool      fwd = direction == DFFT_FORWARD;
-    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
-    const long long nh = n / 2 + 1;
-    // out of place: the byte ranges of in and out must not overlap
-    if (ranges_overlap(in, (uintptr_t)batch * (fwd ? n * rs : nh * cs), out, (uintptr_t)batch * (fwd ? nh * cs : n * rs)))
-        return fail(DFFT_EINVAL, "dfft_rfft1d: in and out overlap (the transform is out of place)");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d: no HIP device visible (no CPU fallback)");
-    if (batch == 0) return DFFT_OK;
-    const hipStream_t st = (hipStream_t)stream;
-    RealRowsPass      R;
-    if (int rc = real_rows_prepare(n, batch, dtype, direction, false, &R)) return rc;
-    LongScratchLease lease = nullptr;
-    void*            scr = nullptr;
-    if (R.need) {
-        scr = long_scratch(R.need, st, &lease);
-        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
-    }
-    const int rc = real_rows_run(R, in, out, batch, scr, st);
-    long_scratch_release(lease);
-    return rc;
-}
-
-// Real transforms along the middle axis of [batch][n][s] (dfft_real_cols.hip); s = 1 is dfft_rfft1d.
-int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || batch < 0 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_rfft1d_strided: bad arguments");
-    if (length_kind(n) == 0)
-        return fail(DFFT_EUNSUPPORTED, "dfft_rfft1d_strided: length " + std::to_string(n) + " has no real form (at most 2^23, or a four-step length)");
-    const bool      fwd = direction == DFFT_FORWARD;
-    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
-    const uintptr_t rb = (uintptr_t)batch * n * s * rs, cb = (uintptr_t)batch * (n / 2 + 1) * s * cs;
-    if (ranges_overlap(in, fwd ? rb : cb, out, fwd ? cb : rb))
-        return fail(DFFT_EINVAL, "dfft_rfft1d_strided: in and out overlap (the transform is out of place)");
-    if (s == 1) return dfft_rfft1d(in, out, n, batch, dtype, direction, stream);
-    if (!real_cols_fused(n, s, dtype)) {  // multi-pass: n-point columns of the (s + 1) / 2 packed pairs, straight from `in` / into `out` where
-                                          // s is even and that pointer is aligned to a complex element, else on the scratch
-        const bool direct = s % 2 == 0 && (uintptr_t)(fwd ? in : out) % cs == 0;
-        const bool p16 = direct ? aligned16(fwd ? in : out) : scratch16();
-        if (!any_extent_ok(n, (s + 1) / 2, dtype, fwd ? p16 : scratch16(), fwd ? scratch16() : p16))
-            return fail(DFFT_EUNSUPPORTED, extent_message("dfft_rfft1d_strided (packed pairs)", n, (s + 1) / 2));
-    }
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft1d_strided: no HIP device visible (no CPU fallback)");
-    if (batch == 0) return DFFT_OK;
-    const hipStream_t  st = (hipStream_t)stream;
-    BluesteinTablesPtr t;
-    if (length_kind(n) == 3)
-        if (int rc = bluestein_tables(n, dtype, direction, &t)) return rc;
-    const bool       bs_fused = bluestein_fused_env();
-    const size_t     need = real_cols_scratch_bytes(n, s, batch, dtype, t.get(), bs_fused);
-    LongScratchLease lease = nullptr;
-    void*            scr = nullptr;
-    if (need) {
-        scr = long_scratch(need, st, &lease);
-        if (!scr) return fail(DFFT_EHIP, "dfft_rfft1d_strided: cannot allocate the scratch buffer");
-    }
-    RealColsLaunch L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.n = n;
-    L.s = s;
-    L.batch = batch;
-    L.dir = direction;
-    L.in = in;
-    L.out = out;
-    const int rc = real_cols(L, t.get(), bs_fused, scr, need, st);
-    long_scratch_release(lease);
-    return rc;
-}
-
-// Real-to-real transforms (DCT / DST, types II and III) along the middle axis of [batch][n][s] (dfft_r2r.hip)
-int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int kind, void* stream) {
-    if (!in || !out || n < 1 || s < 1 || batch < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3)
-        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: bad arguments");
-    if (length_kind(n) == 0)
-        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: length " + std::to_string(n) + " is outside every form (at most 2^23, or a four-step length)");
-    const uintptr_t bytes = (uintptr_t)batch * n * s * (elem_bytes(dtype) / 2);
-    if (in != out && ranges_overlap(in, bytes, out, bytes))
-        return fail(DFFT_EINVAL, "dfft_r2r1d_strided: in and out overlap partly (the transform runs out of place or exactly in place)");
-    if (s > 1 && !(r2r_fused_env() && r2r_fused(n, s, dtype, kind, r2r_vec(in, out, s, dtype))) &&
-        !any_extent_ok(n, (s + 1) / 2, dtype, scratch16(), scratch16()))  // composed route: n-point columns in place on the scratch
-        return fail(DFFT_EUNSUPPORTED, extent_message("dfft_r2r1d_strided (packed pairs)", n, (s + 1) / 2));
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_r2r1d_strided: no HIP device visible (no CPU fallback)");
-    const hipStream_t  st = (hipStream_t)stream;
-    const bool         three = kind == DFFT_R2R_DCT3 || kind == DFFT_R2R_DST3;
-    const bool         fused_on = r2r_fused_env();
-    R2rTablePtr        w;
-    BluesteinTablesPtr t;
-    if (int rc = r2r_table(n, dtype, &w)) return rc;
-    if (length_kind(n) == 3)
-        if (int rc = bluestein_tables(n, dtype, three ? DFFT_BACKWARD : DFFT_FORWARD, &t)) return rc;
-    const bool bs_fused = bluestein_fused_env();
-    R2rLaunch  L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.kind = kind;
-    L.n = n;
-    L.s = s;
-    L.batch = batch;
-    L.in = in;
-    L.out = out;
-    const size_t     need = r2r_scratch_bytes(L, fused_on, t.get(), bs_fused);
-    LongScratchLease lease = nullptr;
-    void*            scr = nullptr;
-    if (need) {
-        scr = long_scratch(need, st, &lease);
-        if (!scr) return fail(DFFT_EHIP, "dfft_r2r1d_strided: cannot allocate the scratch buffer");
-    }
-    const int rc = r2r(L, *w, fused_on, t.get(), bs_fused, scr, need, st);
-    long_scratch_release(lease);
-    return rc;
-}
-
-// `batch` planes of [n1][n2] reals <-> [n1][n2/2 + 1] bins, in groups of planes sized for the 256 MiB Infinity Cache (dfft_fft2d_batch's
-// rule, on the complex side): forward R2C rows into `out`, then the n1-point columns in place on `out` (dfft_fft1d_any); backward the
-// inverse columns from `in` into a scratch group, then C2R rows from there into `out`.
-int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream) {
-    if (!in || !out || n1 < 1 || n2 < 1 || batch < 0 || (dtype != DFFT_F64 && dtype != DFFT_F32) || (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_rfft2d_batch: bad arguments");
-    if (real_form(n2) == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft2d_batch: n2 = " + std::to_string(n2) + " has no real form");
-    if (length_kind(n1) == 0) return fail(DFFT_EUNSUPPORTED, "dfft_rfft2d_batch: n1 = " + std::to_string(n1) + " is outside every form");
-    const bool      fwd = direction == DFFT_FORWARD;
-    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
-    const long long nh = n2 / 2 + 1;
-    const uintptr_t rplane_b = (uintptr_t)n1 * n2 * rs, cplane_b = (uintptr_t)n1 * nh * cs;
-    if (ranges_overlap(in, (uintptr_t)batch * (fwd ? rplane_b : cplane_b), out, (uintptr_t)batch * (fwd ? cplane_b : rplane_b)))
-        return fail(DFFT_EINVAL, "dfft_rfft2d_batch: in and out overlap (the transform is out of place)");
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rfft2d_batch: no HIP device visible (no CPU fallback)");
-    if (batch == 0) return DFFT_OK;
-    const hipStream_t st = (hipStream_t)stream;
-    const long long   cp = cache_plane_group(batch, (long long)cplane_b);  // planes per group
-    RealRowsPass R;
-    if (int rc = real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, &R)) return rc;
-    if (fwd) {
-        for (long long p0 = 0; p0 < batch; p0 += cp) {
-            const long long  np = std::min(cp, batch - p0);
-            void*            op = (char*)out + p0 * cplane_b;
-            LongScratchLease lease = nullptr;
-            void*            scr = nullptr;
-            if (R.need) {
-                scr = long_scratch(R.need, st, &lease);
-                if (!scr) return fail(DFFT_EHIP, "dfft_rfft2d_batch: cannot allocate the scratch buffer");
-            }
-            const int rc = real_rows_run(R, (const char*)in + p0 * rplane_b, op, np * n1, scr, st);
-            long_scratch_release(lease);
-            if (rc) return rc;
-            if (int rc2 = dfft_fft1d_any(op, op, n1, nh, np, dtype, direction, stream)) return rc2;
-        }
-        return DFFT_OK;
-    }
-    AnyPass A;
-    if (int rc = any_prepare(n1, nh, cp, dtype, direction, &A)) return rc;
-    const size_t     gb = (size_t)cp * cplane_b;  // the bins of one plane group
-    const size_t     inner = std::max(R.need, A.need);
-    LongScratchLease lease = nullptr;
-    void*            scr = long_scratch(gb + inner, st, &lease);
-    if (!scr) return fail(DFFT_EHIP, "dfft_rfft2d_batch: cannot allocate the scratch buffer");
-    void* iscr = inner ? (char*)scr + gb : nullptr;
-    int   rc = DFFT_OK;
-    for (long long p0 = 0; p0 < batch && rc == DFFT_OK; p0 += cp) {
-        const long long np = std::min(cp, batch - p0);
-        rc = any_run(A, (const char*)in + p0 * cplane_b, scr, np, iscr, st);
-        if (rc == DFFT_OK) rc = real_rows_run(R, scr, (char*)out + p0 * rplane_b, np * n1, iscr, st);
-    }
-    long_scratch_release(lease);
-    return rc;
-}
-
-// The extent rule of dfft_fft1d_cols (include/dfft.h; any_extent_ok above).  `pairs`: both pointers are 16-byte aligned.
-int dfft_cols_extent_supported(long long n, long long width, int dtype, int pairs) {
-    if (n < 1 || width < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || length_kind(n) == 0 || length_kind(n) == 3) return 0;
-    return cols_extent_ok(n, width, dtype, pairs != 0, pairs != 0) ? 1 : 0;
-}
-// The same for dfft_fft1d_any along the middle axis of [batch][n][s], every kind of length; in16 / out16: that pointer is 16-byte aligned.
-int dfft_fft1d_any_extent_supported(long long n, long long s, int dtype, int in16, int out16) {
-    if (n < 1 || s < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) || length_kind(n) == 0) return 0;
-    return any_extent_ok(n, s, dtype, in16 != 0, out16 != 0) ? 1 : 0;
-}
-
-int dfft_fft1d_cols(void* in, void* out, long long n, long long width, long long batch, int dtype, int direction,
-                    void* stream) {
-    if (!in || !out || batch < 0 || width < 1 || (dtype != DFFT_F64 && dtype != DFFT_F32) ||
-        (direction != DFFT_FORWARD && direction != DFFT_BACKWARD))
-        return fail(DFFT_EINVAL, "dfft_fft1d_cols: bad arguments");
-    if (!dfft_length_supported(n)) return fail(DFFT_EUNSUPPORTED, "dfft_fft1d_cols: unsupported length");
-    if (partly_overlap(in, out, (uintptr_t)batch * (uintptr_t)n * (uintptr_t)width * elem_bytes(dtype)))
-        return fail(DFFT_EINVAL, "dfft_fft1d_cols: in and out overlap partly (the transform runs out of place or exactly in place)");
-    if (!cols_extent_ok(n, width, dtype, aligned16(in), aligned16(out))) return fail(DFFT_EUNSUPPORTED, extent_message("dfft_fft1d_cols", n, width));
-    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_fft1d_cols: no HIP device visible (no CPU fallback)");
-    if (n > 4096) {
-        if (batch == 0) return DFFT_OK;
-        LongScratchLease lease = nullptr;
-        void*            scr = long_scratch((size_t)batch * n * width * elem_bytes(dtype), (hipStream_t)stream, &lease);
-        if (!scr) return fail(DFFT_EHIP, "dfft_fft1d_cols: cannot allocate the scratch buffer of the four-step transform");
-        const int rc = long_fft(in, out, n, width, batch, dtype, direction, 1.0, scr, (hipStream_t)stream);
-        long_scratch_release(lease);
-        return rc;
-    }
-    const void* tw = nullptr;
-    int         rc = get_twiddles((int)n, dtype, &tw);
-    if (rc) return rc;
-    FftLaunch L;
-    std::memset(&L, 0, sizeof(L));
-    L.dtype = dtype;
-    L.n = (int)n;
-    L.dir = direction;
-    L.cols = 1;
-    L.in = in;
-    L.out = out;
-    L.tw = tw;
-    L.imap = L.omap = plain_axis(n, width, 1);
-    L.itile = L.otile = TileMap{n * width, 1};
-    L.na = batch;
-    L.ncols = (int)width;
-    return check_launch(launch_fft(L, (hipStream_t)stream), "dfft_fft1d_cols");
 }
 
 }  // extern "C"

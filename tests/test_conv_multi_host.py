@@ -219,7 +219,7 @@ def test_factor_tables_slice_ay_at_y0_and_pad_az_to_the_width(N, P, prec):
 
 
 def test_the_library_source_addresses_the_tables_as_the_model_does():
-    src = (CSRC / "dfft_plan.cpp").read_text()
+    src = (CSRC / "dfft_plan_conv.cpp").read_text()
     body = src[src.index("int dfft_conv_set_factors("):]
     body = body[:body.index("\n}\n")]
     assert "plan->sy.start(plan->me)" in body and "plan->ys" in body          # ay from y0, y_local elements

@@ -334,6 +334,22 @@ def test_conv_inplace_and_repeats_are_bit_identical(gpu, N, P):
     assert np.array_equal(oop[0], inp[0]) and np.array_equal(oop[0], inp[1]), "in place differs from out of place"
 
 
+def test_conv_plan_created_and_destroyed_without_an_execute(gpu):
+    """Both half plans, the shared stream and the send-less P = 1 handle go away cleanly when nothing has run; the input is untouched."""
+    import torch
+    from distributedfft_amd import api
+    N = (16, 6, 8)
+    x = _input(N, "f64")
+    a = torch.from_numpy(x.reshape(-1)).to(gpu)
+    b = torch.zeros(int(np.prod(N)), dtype=torch.complex128, device=gpu)
+    torch.cuda.synchronize()
+    p = api.PlanConv(*N, a, b, None, 0, 1)
+    assert "pipeline=conv " in p.describe() and "filter=unset" in p.describe()
+    p.destroy()  # raises on any return code but DFFT_OK
+    torch.cuda.synchronize()
+    assert np.array_equal(a.cpu().numpy(), x.reshape(-1)) and not bool(b.any())
+
+
 def test_conv_contract(gpu):
     """Replacing the filter, set_scale's documented rule, execute without a filter, stage_times, tune / kernel_times / buffer accessors."""
     import torch

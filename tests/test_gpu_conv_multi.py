@@ -290,6 +290,23 @@ def test_multi_set_kernel_agrees_with_set_filter(gpu, N, P, prec):
 
 
 # 10
+def test_multi_plan_created_and_destroyed_without_an_execute(gpu):
+    """The forward half, one C2R half per output and the factor tables go away cleanly when nothing has run; the buffers are untouched."""
+    import torch
+    from distributedfft_amd import api
+    N = (16, 6, 8)
+    cnt = int(np.prod(N))
+    x = _input(N, "f64")
+    a = torch.from_numpy(x.reshape(-1)).to(gpu)
+    outs = [torch.zeros(cnt, dtype=torch.float64, device=gpu) for _ in range(3)]
+    torch.cuda.synchronize()
+    p = api.PlanConvRealMulti(*N, a, outs, None, 0, 1)
+    assert "pipeline=conv-real-multi outputs=3 " in p.describe() and "filter=unset" in p.describe()
+    p.destroy()  # raises on any return code but DFFT_OK
+    torch.cuda.synchronize()
+    assert np.array_equal(a.cpu().numpy(), x.reshape(-1)) and not any(bool(o.any()) for o in outs)
+
+
 def test_multi_contract_on_a_live_device(gpu):
     import torch
     from distributedfft_amd import _lib as L

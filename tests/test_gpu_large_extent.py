@@ -71,7 +71,9 @@ FFT2D = [
     ("m-f64", 256, 256, (1 << 15) + 1, "f64"),
 ]
 # dfft_rfft2d_batch, forward and backward: (id, n1, n2, batch, prec)
-RFFT2D = [("n", 512, 512, (1 << 14) + 1, "f32")]
+# "odd": an odd n2 (real form 2: the rows lease scratch) over two plane groups of 8192 planes -- forward takes and returns the lease once
+# per group around the rows (the columns lease their own), backward holds one lease across both groups
+RFFT2D = [("n", 512, 512, (1 << 14) + 1, "f32"), ("odd", 64, 63, 8192 + 61, "f64")]
 
 
 def all_shapes():

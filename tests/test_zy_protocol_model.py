@@ -9,7 +9,7 @@ than the resident set does) drives them.  Checked under many interleavings:
   * the ticket counter ends at exactly items + 2 * workgroups -- zy_tickets(), what the host adds to its running ticket base.
 Negative controls: the lazy loop WITHOUT the flush in front of its blocking wait deadlocks; a loop that prefetches without the
 dependency poll loads a consumer unit too early.
-Across launches, the host bookkeeping of dfft_fft2d_batch (distributedfft_amd/csrc/dfft_plan.cpp): calls on one cached control block
+Across launches, the host bookkeeping of dfft_fft2d_batch (distributedfft_amd/csrc/dfft_batch.cpp): calls on one cached control block
 with changing batch sizes must start every launch with done[p] == done_base on each of its planes; the rule before the fix
 (done_base = execs x producers, no reset) breaks that at batch 1 -> 2, and the kernel's range check then raises ZY_ERR_DESYNC.
 (Test infrastructure: a model of the protocol, not the kernel's arithmetic --
