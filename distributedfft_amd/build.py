@@ -22,7 +22,7 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 HIPCC = str(ROCM / "bin" / "hipcc")
 ARCH = "gfx950"
 NUM_INST_GROUPS = 12  # keep in sync with csrc/dfft_plans.h
-# host-side units (csrc/<name>.cpp).  All of them are compiled as HIP: the plan units take DFFT_ZY_ROW_PITCH and friends from dfft_zy.h
+# host-side units (csrc/<name>.cpp).  All of them are compiled as HIP: the plan units take the launch structs from the kernel headers (dfft_zy.h and friends)
 HOST_UNITS = ["dfft_core", "dfft_passes", "dfft_plan", "dfft_plan_tune", "dfft_plan_r2c", "dfft_plan_conv", "dfft_batch",
               "dfft_exchange", "dfft_bootstrap", "dfft_alloc", "dfft_trace"]
 

@@ -257,7 +257,6 @@ int dfft_fft2d_batch(void* in, void* out, long long n1, long long n2, long long 
             L.w = out;
             L.dst = nullptr;
             L.src_plane = L.w_plane = L.dst_plane = plane;
-            DFFT_ZY_SET_PITCH(L, n2);
             L.plane0 = 0;
             L.nplanes = batch;
             const long long fit = std::max(1ll, (230ll << 20) / plane_b), nch = (batch + fit - 1) / fit;

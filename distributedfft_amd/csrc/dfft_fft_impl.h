@@ -176,12 +176,9 @@ constexpr int tw_slots(int R, bool pow2only) { return !pow2only ? R - 1 : (R >= 
 // table to registers; measured (round 1, profiles/r01/experiments) that costs 3-6 % on the 1024/2048-point column kernels (register
 // pressure), so the sharing is switched on only for 4096 points, where 16 points x 256 threads then keep 12 twiddles in
 // registers instead of a 64 KiB LDS table that, next to the 72 KiB row tile, would leave one workgroup per CU.
-#ifndef DFFT_TW_EFFECTIVE
-#define DFFT_TW_EFFECTIVE 0
-#endif
-template <class P> constexpr bool tw_sharing() { return DFFT_TW_EFFECTIVE || P::N >= 4096; }
+template <class P> constexpr bool tw_sharing() { return P::N >= 4096; }
 
-// Stage-major LDS twiddle table (the default since round 4; -DDFFT_TW_STAGE_MAJOR=0 builds the natural-order table for A/B runs): the
+// Stage-major LDS twiddle table (since round 4): the
 // LDS copy of the twiddle table (TW_LDS kernels: 16 / 24 points per thread -- 768, 1024, 2048 points) is laid out [stage][m][r - 1]
 // like the reference's LUT (templateFFT.cpp:5120-5141) instead of as the natural N-entry table read at r * m * N / (Ns R).  In the
 // early stages (small Ns) the lanes of a ds_read_b128 group read a handful of distinct entries a power-of-two number of bytes apart
@@ -193,9 +190,6 @@ template <class P> constexpr bool tw_sharing() { return DFFT_TW_EFFECTIVE || P::
 // 3.17 -> 3.06, 2048 x 1024 x 512 fp64 7.11 -> 6.96, fp32 4.61 -> 4.54, 1024 x 768 x 512 fp64 2.729 -> 2.710, fp32 1.116 -> 1.098; t0 with
 // a 768- / 1024-point Y axis -1 ... -2.5 %; nothing slower.  Entries: sum over stages s >= 1 of Ns (R - 1) = N - R_0 <= N: the
 // same LDS area.
-#ifndef DFFT_TW_STAGE_MAJOR
-#define DFFT_TW_STAGE_MAJOR 1
-#endif
 template <class P, int S, bool TWPOW> struct StageInfo {
     using Prev = StageInfo<P, S - 1, TWPOW>;
     static constexpr int R = P::R[S];
@@ -270,10 +264,7 @@ __device__ __forceinline__ void load_twiddles(W* twr, const W* __restrict__ tw, 
 // wavefront; here wavefront w takes the ids congruent to w modulo NW instead: j = w + NW * (lane / CB).  The 8 (16 in fp32) lanes of a
 // column group still cover one full 128-byte line / all 32 LDS banks per access, and which rows of the tile a wavefront touches never
 // mattered to HBM (every row is a line of its own), so nothing changes on the memory side -- but every exchange after the first then
-// stays inside a wavefront.  -DDFFT_WAVE_OWNED=0 builds the tid / CB numbering (A/B).
-#ifndef DFFT_WAVE_OWNED
-#define DFFT_WAVE_OWNED 1
-#endif
+// stays inside a wavefront.
 // Where it is used: tiles whose column groups are whole 128-byte lines of 16-byte elements (fp64, fp32 column pairs), one-phase
 // exchanges, and not the staged transposing store of column pairs.  Measured before that rule (profiles/r06/experiments/
 // lib_ab_wave_owned.log): the labelling puts the lanes of a ds_read_b128 group (lanes {0-3, 12-15, 20-27}, ...: four different column
@@ -283,7 +274,7 @@ __device__ __forceinline__ void load_twiddles(W* twr, const W* __restrict__ tw, 
 // the 2048-point X pass) have two column groups per 128 bytes and lose either way (1.87 -> 2.21 ms).
 template <class V, int CB, int T, int PH = 1, bool PAIR_IMAGE = false> constexpr int owned_waves() {
     constexpr int GT = CB * T;
-    return (DFFT_WAVE_OWNED && sizeof(V) == 16 && (CB * sizeof(V)) % 128 == 0 && !PAIR_IMAGE && PH == 1 && GT % 64 == 0 && GT / 64 > 1 && 64 % CB == 0) ? GT / 64 : 0;
+    return (sizeof(V) == 16 && (CB * sizeof(V)) % 128 == 0 && !PAIR_IMAGE && PH == 1 && GT % 64 == 0 && GT / 64 > 1 && 64 % CB == 0) ? GT / 64 : 0;
 }
 // Position p of the exchange tile under the labelling: the two 128-byte halves of every 256-byte bank row are swapped in every second
 // group of 8 positions, so that the column groups of a ds_read_b128 lane group -- positions 8 apart -- alternate between the halves.
@@ -330,60 +321,6 @@ __device__ __forceinline__ void fill_stage_major(W* dst, const W* __restrict__ t
 //   TW_GLOBAL N-entry table read through L1/L2 (only when the LDS is needed for the exchange tile, e.g. N = 2048)
 enum { TW_REG = 0, TW_LDS = 1, TW_GLOBAL = 2 };
 
-// Cross-lane form of a wave-owned exchange (round 6, experiment: -DDFFT_XLANE=1; VERDICT r05 Next-1c).  Under the wave-interleaved labelling
-// with NW = 8 waves, 8-column tiles and T = 64 butterfly threads a wavefront holds the ids w + 8 g (g = lane / 8, column = lane % 8).
-// For a stage with NS R = 64 = T (NS = 8 n) the scatter / gather sends the result (g, q, r) to lane group (r, g mod n) as point
-// g / n + R q: for each of the thread's B butterflies a TRANSPOSE between the upper lane-group bits and the register index r of 16-byte
-// elements, followed by a renaming of registers.  gfx950 does a round of such a transpose on a register pair without selects:
-// v_permlane32_swap (upper half of a <-> lower half of b), v_permlane16_swap (odd rows of a <-> even rows of b); lane bit 3 takes two
-// v_mov_b32_dpp row_ror:8 with bank masks.  Cases: the exchange between the radix-8 stages of 512 / 1024 / 2048 = 8 8 ... (three rounds),
-// the one behind the third radix-4 stage of 768 = 4 4 4 4 3 (NS = 16: two rounds, no DPP).  Pure data movement: bit-identical results.
-// tools/xlane_probe.hip measures the exchange alone (profiles/r06/README.md section 1i).
-#ifndef DFFT_XLANE
-#define DFFT_XLANE 0
-#endif
-typedef unsigned xl_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned xl_u32x4 __attribute__((ext_vector_type(4)));
-template <int NW, int CB, int T, int NS, int R, int S, class V> constexpr bool xlane_exchange() {
-    return DFFT_XLANE && NW == 8 && CB == 8 && T == 64 && S > 0 && sizeof(V) == 16 && NS % 8 == 0 && NS * R == 64 && (R == 8 || R == 4 || R == 2);
-}
-// one round on a register pair: lanes whose bit BIT is clear keep a and receive the partner's a into b, the others keep b and receive the
-// partner's b into a
-template <int BIT, class V> __device__ __forceinline__ void xlane_round(V& a, V& b) {
-    xl_u32x4 x, y;
-    __builtin_memcpy(&x, &a, 16);
-    __builtin_memcpy(&y, &b, 16);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        if constexpr (BIT == 5) {
-            const xl_u32x2 r = __builtin_amdgcn_permlane32_swap(x[d], y[d], false, false);
-            x[d] = r.x;
-            y[d] = r.y;
-        } else if constexpr (BIT == 4) {
-            const xl_u32x2 r = __builtin_amdgcn_permlane16_swap(x[d], y[d], false, false);
-            x[d] = r.x;
-            y[d] = r.y;
-        } else {
-            static_assert(BIT == 3, "lane bits 3..5");
-            const unsigned nx = __builtin_amdgcn_update_dpp(x[d], y[d], 0x128 /* row_ror:8 */, 0xf, 0xc, false);
-            const unsigned ny = __builtin_amdgcn_update_dpp(y[d], x[d], 0x128, 0xf, 0x3, false);
-            x[d] = nx;
-            y[d] = ny;
-        }
-    }
-    __builtin_memcpy(&a, &x, 16);
-    __builtin_memcpy(&b, &y, 16);
-}
-template <int BIT0, int RB, int R, int B, class V> __device__ __forceinline__ void xlane_transpose(V* v, int q) {
-    // register bit RB of r <-> lane bit BIT0 + RB
-    if constexpr (RB >= 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (!(r & (1 << RB))) xlane_round<BIT0 + RB>(v[q + r * B], v[q + (r | (1 << RB)) * B]);
-        xlane_transpose<BIT0, RB - 1, R, B>(v, q);
-    }
-}
-
 // PH = 2: the tile (N x CB elements) is twice what the LDS holds, so every exchange runs in two phases -- first the threads
 // of columns [0, CB/2), then those of [CB/2, CB) -- through one half-size buffer.  HBM accesses keep full 128-byte lines
 // (all CB columns of a row segment are loaded/stored together); only the LDS issue slots double.
@@ -401,14 +338,11 @@ __device__ __forceinline__ void run_stages(V* v, const typename VecTraits<V>::W*
 #pragma unroll
         for (int r = 0; r < R; ++r) u[r] = v[q + r * B];
         if constexpr (S > 0) {
-#if DFFT_TW_STAGE_MAJOR
             if constexpr (TWMODE == TW_LDS && TWS == 1) {
                 const W* ts = twr + SI::SM_OFF + tw_row<NW, NS>((j + q * T) % NS) * (R - 1);
 #pragma unroll
                 for (int r = 1; r < R; ++r) u[r] = cmul(u[r], ts[r - 1]);
-            } else
-#endif
-            if constexpr (TWMODE == TW_LDS) {
+            } else if constexpr (TWMODE == TW_LDS) {
                 const int m = ((j + q * T) % NS) * (TWS * P::N / (NS * R));
 #pragma unroll
                 for (int r = 1; r < R; ++r) u[r] = cmul(u[r], twr[r * m]);
@@ -442,11 +376,6 @@ __device__ __forceinline__ void run_stages(V* v, const typename VecTraits<V>::W*
         for (int r = 0; r < R; ++r) v[q + r * B] = u[r];
     }
     if constexpr (S + 1 < P::S) {
-#ifdef DFFT_DBG_NOEXCH
-        // measurement builds only (-DDFFT_DBG_NOEXCH): skip the LDS exchange to see the HBM + VALU time alone (wrong results)
-        run_stages<V, P, S + 1, DIR, CB, PAD, WAVE_LOCAL, TWMODE, TWPOW, PH, TWS, NW, LOCALX>(v, twr, lds, j, c);
-        return;
-#endif
         // Thread-local exchange (round 6).  The scatter after stage S sends the result (jq, r) to position
         //     p = (jq / NS) NS R + jq mod NS + r NS,         jq = j + q T,
         // and position p is read back by thread p mod T as its point p / T.  When T divides NS every term but j is a multiple of
@@ -456,27 +385,13 @@ __device__ __forceinline__ void run_stages(V* v, const typename VecTraits<V>::W*
         // stages whose remaining radix product fits the E points of a thread: the exchange in front of the last stage of 1024 = 8 8 8 2
         // on 16 x 64 threads (config 4's X axis, the halves of config 5's DIF-split 2048-point Y axis), of 768 = 4 4 4 4 3 on 12 x 64
         // (config 4's Y axis), 1536 = 8 8 8 3, the one-wavefront rows of 2048 points (32 x 64).  Same values in the same order of
-        // operations: bit-identical results.  -DDFFT_LOCAL_EXCHANGE=0 builds the LDS form (A/B).
-#ifndef DFFT_LOCAL_EXCHANGE
-#define DFFT_LOCAL_EXCHANGE 1
-#endif
-        if constexpr (DFFT_LOCAL_EXCHANGE && LOCALX && NS % T == 0) {
+        // operations: bit-identical results.
+        if constexpr (LOCALX && NS % T == 0) {
             V t[E];
 #pragma unroll
             for (int q = 0; q < B; ++q)
 #pragma unroll
                 for (int r = 0; r < R; ++r) t[((q * T) / NS) * (NS / T) * R + ((q * T) % NS) / T + r * (NS / T)] = v[q + r * B];
-#pragma unroll
-            for (int k = 0; k < E; ++k) v[k] = t[k];
-        } else if constexpr (PH == 1 && xlane_exchange<NW, CB, T, NS, R, S, V>()) {
-            constexpr int LR = R == 8 ? 3 : (R == 4 ? 2 : 1);  // bits of r; the lane bits are the top LR bits of the lane group: 6 - LR .. 5
-            V t[E];
-#pragma unroll
-            for (int q = 0; q < B; ++q) {
-                xlane_transpose<6 - LR, LR - 1, R, B>(v, q);
-#pragma unroll
-                for (int i = 0; i < R; ++i) t[i + R * q] = v[q + i * B];
-            }
 #pragma unroll
             for (int k = 0; k < E; ++k) v[k] = t[k];
         } else if constexpr (PH == 1) {
@@ -488,6 +403,8 @@ __device__ __forceinline__ void run_stages(V* v, const typename VecTraits<V>::W*
             // compiler fences.  With radix-8 first stages and 8 waves per tile that is every exchange but the first: 512 = 8 8 8 keeps 2
             // of 4 barriers per tile, 1024 = 8 8 [8 2] 2 of 4, 2048 = 8 8 8 4 2 of 6 (plus the two of a staged store).  The labelling
             // changes which lane computes a butterfly, not what is computed: bit-identical results.
+            // (A cross-lane form of this exchange -- permlane swaps instead of the LDS round trip -- was measured in round 6 and not
+            // adopted: profiles/r06/README.md section 1i.)
             constexpr bool OWNED = NW > 1 && S > 0 && NS % NW == 0 && T % NW == 0;
             constexpr bool WL = WAVE_LOCAL || OWNED;
             if constexpr (S > 0 || !WAVE_LOCAL) group_sync<WL>();  // WAR: previous readers are done
@@ -594,11 +511,8 @@ template <class V, class P, int CB, int G, class Tune> struct KernelGeom {
     // 0.42 -> 0.455 ms per GiB with the exchange in registers, profiles/r06/experiments/long_axis_kernels_ab.txt)
     // (and 729 points -- 648-thread workgroups, 168 registers -- with per-point rotated offsets: 20-44 bytes over with three of the
     // six radix-3 stages back to back; see also LOCALX_GENERAL in the kernel)
-#ifndef DFFT_729_LOCALX
-#define DFFT_729_LOCALX 0
-#endif
     static constexpr bool LOCALX = !(ROT2_PLAIN && P::E * (int)sizeof(V) / 4 >= 64) && !(CB == 1 && P::E * (int)sizeof(V) / 4 >= 128) &&
-                                   (DFFT_729_LOCALX || !(ROT2_PLAIN && (P::N == 729 || (P::N == 768 && VecTraits<V>::LANES == 2 && Tune::ROT_IN == 2))));
+                                   !(ROT2_PLAIN && (P::N == 729 || (P::N == 768 && VecTraits<V>::LANES == 2 && Tune::ROT_IN == 2)));
     // (768-point column pairs loading rotated points without a staged store -- an un-fused or natural-order forward X pass: 12 bytes over)
     static constexpr int EX_ELEMS = (P::S > 1) ? (PAD ? P::N + P::N / 8 : P::N) * CB / PH : 0;
     // staged image: one scalar column per row of N + OPAD twiddle-typed elements (OPAD = 2 keeps cpair rows 16-B aligned)
@@ -664,9 +578,7 @@ __device__ __forceinline__ void pin_loaded(const cpair& x) { asm volatile("" : :
 
 // register prefetch only where the second register set is cheap (64 VGPRs, i.e. E = 16 fp64: 1024-point columns
 // 4.6 -> 3.7 TB/s, round 1)
-#ifndef DFFT_PREFETCH_MAX_REGS
-#define DFFT_PREFETCH_MAX_REGS 32
-#endif
+constexpr int kPrefetchMaxRegs = 32;
 // offset of block ib of an axis map (single- or two-level, see AxisMap)
 __device__ __forceinline__ long long block_term(const AxisMap& m, int ib) {
     if (m.sub > 1) return (long long)(ib / m.sub) * m.blk_stride + (long long)(ib % m.sub) * m.sub_stride;
@@ -721,15 +633,7 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
     if constexpr (KG::TWMODE == TW_GLOBAL) {
         twr = tw;
     } else if constexpr (KG::TWMODE == TW_LDS) {
-#if DFFT_TW_STAGE_MAJOR
         fill_stage_major<W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-#else
-        for (int i = threadIdx.x; i < N; i += KG::THREADS) {
-            W w = tw[i];
-            if (DIR < 0) w.y = -w.y;
-            ldstw[i] = w;
-        }
-#endif
         __syncthreads();
         twr = ldstw;
     } else {
@@ -842,36 +746,20 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
     };
     auto load_tile = [&](unsigned t, V* dst) { load_part(t, dst, std::integral_constant<int, 0>{}, std::integral_constant<int, E>{}); };
     // only where the second register set is cheap: <= 32 VGPRs and blocks that do not need the 128-VGPR budget
-    // (round 4) ... and where the second set is free: a workgroup of at most 256 threads is one wave per SIMD, which may use all 512
-    // registers of its lanes (the compiler parks what does not fit the 256 architectural ones in AGPRs; loads can target them), and
-    // a tile beyond 80 KiB means one workgroup per CU anyway -- the 768-point column kernels (24 points per thread, 96 KiB tiles:
-    // config 4's Y axis) have nothing in flight underneath their exchanges.  -DDFFT_WIDE_PREFETCH=1 builds it, =2 adds the early wait
-    // (the prefetched tile is waited for before this tile's stores are issued, so that they drain underneath the next tile: what the
-    // lazy one-launch YZ stage does).  Measured and NOT adopted (round 4, 362-392 registers, no scratch, bit-identical):
-    // profiles/r04/experiments/lib_ab_wide_prefetch.log.
-#ifndef DFFT_WIDE_PREFETCH
-#define DFFT_WIDE_PREFETCH 0
-#endif
-    constexpr bool WIDE = DFFT_WIDE_PREFETCH && KG::THREADS <= 256 && KG::LDS_BYTES > 80 * 1024 && !GENERAL;
-    constexpr bool EARLY = Tune::EARLY_WAIT || (WIDE && DFFT_WIDE_PREFETCH >= 2);
+    // (A wide prefetch for workgroups of at most 256 threads with tiles beyond 80 KiB, the second set parked in AGPRs, was measured in
+    // round 4 and not adopted: profiles/r04/experiments/lib_ab_wide_prefetch.log.)
+    constexpr bool EARLY = Tune::EARLY_WAIT;
     // 768 points on 12 points x 64 threads (the library's column plan since round 5): its second register set is 48 VGPRs of 16-byte
-    // points -- over the general bound, but these kernels have the room.  -DDFFT_768_PREFETCH=0 compiles it out (A/B builds).
-#ifndef DFFT_768_PREFETCH
-#define DFFT_768_PREFETCH 1
-#endif
-    constexpr bool P768 = DFFT_768_PREFETCH && P::N == 768 && E == 12 && sizeof(V) == 16;
-    constexpr bool PREFETCH = Tune::PREFETCH && (E * (int)sizeof(V) / 4 <= DFFT_PREFETCH_MAX_REGS || Tune::FULL_PREFETCH || WIDE || P768) && KG::THREADS <= 512;
+    // points -- over the general bound, but these kernels have the room.
+    constexpr bool P768 = P::N == 768 && E == 12 && sizeof(V) == 16;
+    constexpr bool PREFETCH = Tune::PREFETCH && (E * (int)sizeof(V) / 4 <= kPrefetchMaxRegs || Tune::FULL_PREFETCH || P768) && KG::THREADS <= 512;
     // 16 points per thread (1024- and 2048-point columns) without Tune::FULL_PREFETCH: a whole second register set does not fit next
     // to per-point offsets (64 VGPRs: 4.6 -> 3.7 TB/s, round 1), but the kernels leave room for HALF of one -- the first 8 points of
     // the next tile are fetched underneath the current tile's exchanges and stores, the other 8 at the top of the next iteration.
-    // DFFT_HALF_PREFETCH=0 compiles it out.
-#ifndef DFFT_HALF_PREFETCH
-#define DFFT_HALF_PREFETCH 1
-#endif
     // (only the staged-store variant -- the X pass -- has the registers: 192 -> 228; the plain column variants sit at 216 and would
     // spill 28-68 B with it.  Measured: 1024-point X pass on fp32 column pairs 4.5 -> 4.9 TB/s, fp64 unchanged at 4.6-4.7;
     // profiles/r03/experiments/half_prefetch_ab.log)
-    constexpr int PF = PREFETCH ? E : (DFFT_HALF_PREFETCH && Tune::PREFETCH && KG::OSTAGE && E == 16 && sizeof(V) == 16 && KG::THREADS <= 512 && KG::PH == 1 ? E / 2 : 0);
+    constexpr int PF = PREFETCH ? E : (Tune::PREFETCH && KG::OSTAGE && E == 16 && sizeof(V) == 16 && KG::THREADS <= 512 && KG::PH == 1 ? E / 2 : 0);
     constexpr bool PARTIAL = PF > 0 && PF < E;
     using K0 = std::integral_constant<int, 0>;
     using KP = std::integral_constant<int, PF>;
@@ -905,7 +793,7 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
         }
 
         // (729-point column tiles with the ragged / uneven-slab address terms compiled in: 12 bytes over with the thread-local exchange)
-        constexpr bool LOCALX = KG::LOCALX && (DFFT_729_LOCALX || !(GENERAL && P::N == 729 && CB > 1));
+        constexpr bool LOCALX = KG::LOCALX && !(GENERAL && P::N == 729 && CB > 1);
         run_stages<V, P, 0, DIR, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, LOCALX>(v, twr, lds, j, c);
 
         // normalisation folded into this pass: every result is multiplied on its way out (x * 1.0 is exact, so the default
@@ -990,19 +878,18 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
 // (a wave touches whole lines), and the two 4-column transforms go through the one LDS tile one after the other while the
 // other half waits in registers.  Fast path of the transposing store only (forward X pass; no ragged tile, no uneven slab),
 // staged per half through the same LDS; everything else stays on fft_tiles_kernel.
-// WPC: workgroups meant to be resident per CU (each gets 160 KiB / WPC of LDS and 512 / WPC registers per lane)
-template <class V, class P, int CB, int WPC = 1> struct DualGeom {
+template <class V, class P, int CB> struct DualGeom {
     using W = typename VecTraits<V>::W;
     static constexpr int    LANES = VecTraits<V>::LANES, OPAD = LANES == 2 ? 2 : 1;
-    static constexpr size_t BUDGET = 160 * 1024 / WPC;
+    static constexpr size_t BUDGET = 160 * 1024;
     static constexpr size_t TW_BYTES = ((size_t)P::N * sizeof(W) + 15) / 16 * 16;
     static constexpr bool   PADROW = (size_t)(P::N + OPAD) * CB * sizeof(V) + TW_BYTES <= BUDGET;
     static constexpr int    ROW = PADROW ? P::N + OPAD : P::N;  // in units of W; CB * LANES rows
     static constexpr size_t LDS_BYTES = TW_BYTES + (size_t)ROW * CB * sizeof(V);
     static_assert(LDS_BYTES <= BUDGET, "dual tiles: tile + twiddle table must fit the workgroup's share of the CU's LDS");
 };
-template <class V, class P, int CB, int DIR, bool NT, bool ROT = false, int WPC = 1>
-__global__ void __attribute__((amdgpu_flat_work_group_size(1, CB * P::T), amdgpu_waves_per_eu(WPC)))
+template <class V, class P, int CB, int DIR, bool NT, bool ROT = false>
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, CB * P::T), amdgpu_waves_per_eu(1)))
 fft_dual_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* out, const typename VecTraits<V>::W* __restrict__ tw,
                       AxisMap imap, AxisMap omap, TileMap itile, TileMap otile, unsigned ntiles, unsigned tiles_per_a, unsigned a_first,
                       double scale, RotMap rm) {
@@ -1016,7 +903,7 @@ fft_dual_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
     // 160 KiB, so the rows stay N long and row s is rotated by ROT * s elements instead.  Measured
     // (profiles/r02/experiments/dual_tiles.log): any rotation that is not a multiple of 8 memory elements gives 4.8-4.9 TB/s,
     // multiples of 8 (8, 16) 4.5.
-    using DG = DualGeom<V, P, CB, WPC>;
+    using DG = DualGeom<V, P, CB>;
     constexpr bool PADROW = DG::PADROW;
     constexpr int  ROW = DG::ROW, IMGROT = LANES;
     auto img_at = [](int col, int e) -> int {  // element e of scalar column col, in units of W
@@ -1029,15 +916,7 @@ fft_dual_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
     V* lds = reinterpret_cast<V*>(dfft_smem + TW_BYTES);
     constexpr int NWV = owned_waves<V, CB, T, 1, LANES == 2>();  // (half-line tiles: 0 -- see owned_waves)
     const int tid = threadIdx.x, c = tid % CB, j = tile_j<CB, NWV>(tid);
-#if DFFT_TW_STAGE_MAJOR
     fill_stage_major<W, P, 0, DIR, NWV>(ldstw, tw, tid, GT);
-#else
-    for (int i = tid; i < N; i += GT) {
-        W w = tw[i];
-        if (DIR < 0) w.y = -w.y;
-        ldstw[i] = w;
-    }
-#endif
     __syncthreads();
     // The launcher guarantees imap.blk % T == 0: the block a point j + T*k falls into depends on k alone, so its
     // offset splits into a wave-uniform term per k and ONE per-thread term -- no per-point address registers next to the two
@@ -1061,110 +940,8 @@ fft_dual_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
     const long long ithr = (long long)j * imap.stride + (long long)c * imap.cstride;
     // rotated rows of the receive buffer (RotMap mode 2): the pair of tiles of plane j + T k starts rot * plane further on in its row
     const int rot_j = ROT ? (rm.rot * j) & rm.mask : 0, rot_t = ROT ? (rm.rot * T) & rm.mask : 0;
-    // -DDFFT_DUAL_PIPELINE=1 (build-time experiment of round 4, measured and NOT adopted): a software pipeline over tile pairs.
-    // The two register sets hold the whole pair (2 E points of 16 bytes per thread: nothing is left for a third set), so the
-    // shipped form loads a pair, transforms and stores its halves, and only then loads the next pair -- with nothing in flight
-    // underneath the arithmetic.  The pipelined form refills the registers of a half as soon as its stores have been issued (below).
-    // Bit-identical, no scratch in fp64 (242 VGPRs), 8-16 B on fp32 pairs -- and slower in 6 of 8 plans, two processes each,
-    // interleaved with the shipped build (profiles/r04/experiments/lib_ab_pipelined_2048.log): X pass of 2048 x 1024 x 512 fp64 7.55 ->
-    // 8.11 ms, config 5's per rank (fp32, rotated rows, P = 8) 1.86 -> 2.07, P = 4 3.71 -> 4.1; only the un-rotated fp32 form gained
-    // (4.58 -> 4.16).  Every iteration still ends in a full drain (the second refill group is needed at the top of the next one),
-    // the refills are half as deep as the whole-pair burst, and the body is written out twice (19 -> 38 KiB of code).
-#ifndef DFFT_DUAL_PIPELINE
-#define DFFT_DUAL_PIPELINE 0
-#endif
-#if DFFT_DUAL_PIPELINE
-    auto in_ptr = [&](unsigned t) -> const GV* {
-        const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-        return in + (long long)a * itile.a_stride + (long long)b * (2 * CB) * itile.b_stride + ithr;
-    };
-    auto out_ptr = [&](unsigned t, int h) -> GV* {
-        const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-        return out + (long long)a * otile.a_stride + (long long)b * (2 * CB) * otile.b_stride + (long long)h * CB * LANES * omap.cstride;  // omap.cstride: distance between SCALAR columns
-    };
-    // One half of a tile pair: the 4-column transform through the LDS tile, the staged image, the transposing store.
-    auto process_half = [&](V* v, GV* oh) {
-        run_stages<V, P, 0, DIR, CB, false, false, TW_LDS, false, 1, 1, NWV>(v, ldstw, lds, j, c);
-        W* img = reinterpret_cast<W*>(lds);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < E; ++k)
-#pragma unroll
-            for (int l = 0; l < LANES; ++l) {
-                const int col = c * LANES + l;
-                img[img_at(col, j + T * k)] = VT::lane(cscale(v[k], sc), l);
-            }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            const int lin = tid + GT * k;
-            const int col = lin / ON;
-            const GV  r = *reinterpret_cast<const GV*>(img + img_at(col, (lin % ON) * LANES));
-            gstore<NT>(oh + (long long)col * omap.cstride + (lin % ON), r);
-        }
-        __syncthreads();  // the image is read before the next half's exchange overwrites the tile
-    };
-    // point k of both halves of tile pair t (the two loads of a lane group are the two halves of the same 128-byte lines)
-    auto load_point = [&](unsigned t, int k, V& a0, V& a1) {
-        const GV* ip = in_ptr(t);
-        long long off = iuni[k];
-        if constexpr (ROT) {
-            const int cb0 = (int)((t % tiles_per_a) * (2 * CB));
-            off += (long long)(((cb0 + rot_j + k * rot_t) & rm.mask) - cb0);
-        }
-        a0 = VT::from_g(gload<NT>(ip + off));
-        a1 = VT::from_g(gload<NT>(ip + off + (long long)CB * imap.cstride));
-    };
-    // The registers of a half are refilled as soon as that half's stores have been issued: after half 0
-    // the points k < E/2 of BOTH halves of the next pair (a lane group still fetches whole 128-byte lines -- loading one half's
-    // columns first would fetch every line twice, profiles/r02/experiments/dual_tiles.log), after half 1 the points k >= E/2.
-    // The loads of the first group complete underneath the second half's exchanges, those of the second group underneath
-    // the drain of its stores.  Loaded registers must not be moved (a move waits for its load), so the assignment of points to
-    // registers alternates between two layouts and the loop body is written out for both:
-    //   layout 0: A = half 0 (all k), B = half 1;   layout 1: half 0 = {A[k], B[k]}, half 1 = {A[E/2 + k], B[E/2 + k]}, k < E/2
-    constexpr int EH = E / 2;
-    static_assert(E % 2 == 0, "dual tiles: even number of points per thread");
-    V A[E], B[E];
-    unsigned t = blockIdx.x;
-    if (t < ntiles) {
-#pragma unroll
-        for (int k = 0; k < E; ++k) load_point(t, k, A[k], B[k]);
-    }
-    // (the prefetch is unconditional: past the workgroup's last pair it re-reads that pair -- two branches less in a loop body
-    // that sits at the register limit)
-    const unsigned step = gridDim.x;
-    while (t < ntiles) {
-        {  // layout 0 -> 1
-            const unsigned tn = t + step, tl = tn < ntiles ? tn : t;
-            process_half(A, out_ptr(t, 0));
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_point(tl, k, A[k], A[EH + k]);
-            process_half(B, out_ptr(t, 1));
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_point(tl, EH + k, B[k], B[EH + k]);
-            t = tn;
-            if (t >= ntiles) break;
-        }
-        {  // layout 1 -> 0
-            const unsigned tn = t + step, tl = tn < ntiles ? tn : t;
-            V              w0[E], w1[E];
-#pragma unroll
-            for (int k = 0; k < EH; ++k) {
-                w0[k] = A[k];
-                w0[EH + k] = B[k];
-                w1[k] = A[EH + k];
-                w1[EH + k] = B[EH + k];
-            }
-            process_half(w0, out_ptr(t, 0));
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_point(tl, k, A[k], B[k]);
-            process_half(w1, out_ptr(t, 1));
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_point(tl, EH + k, A[EH + k], B[EH + k]);
-            t = tn;
-        }
-    }
-#else
+    // A software pipeline over tile pairs (the registers of a half refilled as soon as its stores have been issued) was measured in
+    // round 4 and not adopted -- slower in 6 of 8 plans: profiles/r04/experiments/lib_ab_pipelined_2048.log.
     for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
         const GV*      ip = in + (long long)a * itile.a_stride + (long long)b * (2 * CB) * itile.b_stride + ithr;
@@ -1205,7 +982,6 @@ fft_dual_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
             __syncthreads();  // the image is read before the next half's exchange overwrites the tile
         }
     }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1237,8 +1013,6 @@ template <class V, class PH, int CB, bool TOUT = false> struct Dif2Geom {
     static constexpr size_t IMG_PLAIN = (size_t)(CB / 2) * LANES * N * sizeof(W);
     static constexpr bool   TWO_PER_CU = TOUT && TW_BYTES + (TILE_BYTES > IMG_PLAIN ? TILE_BYTES : IMG_PLAIN) <= 80 * 1024;
     static constexpr size_t BUDGET = TWO_PER_CU ? 80 * 1024 : 160 * 1024;
-    // (-DDFFT_DIF2_HALF experiment) half-line tiles of the non-transposing passes: two workgroups per CU where half tile + table allow it
-    static constexpr bool   HALF2 = !TOUT && (size_t)CB * sizeof(V) < 128 && TW_BYTES + TILE_BYTES <= 80 * 1024;
     static constexpr bool   PADROW = TW_BYTES + (size_t)(CB / 2) * LANES * (N + OPAD) * sizeof(W) <= BUDGET;
     static constexpr int    ROW = PADROW ? N + OPAD : N;
     static constexpr size_t IMG_BYTES = TOUT ? (size_t)(CB / 2) * LANES * ROW * sizeof(W) : 0;
@@ -1248,7 +1022,7 @@ template <class V, class PH, int CB, bool TOUT = false> struct Dif2Geom {
 // BIN / BOUT: the side's wave-uniform offsets come from a table computed once (any map); false = k * step for single-block maps,
 // which measured 150 B of scratch against none with the tables, so the launcher always asks for both.
 template <class V, class PH, int CB, int DIR, bool NTL, bool NTS, bool BIN, bool BOUT, int ROT = 0, bool TOUT = false>
-__global__ void __attribute__((amdgpu_flat_work_group_size(1, CB * PH::T), amdgpu_waves_per_eu((Dif2Geom<V, PH, CB, TOUT>::TWO_PER_CU || Dif2Geom<V, PH, CB, TOUT>::HALF2) ? (CB * PH::T) / 128 : 1)))
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, CB * PH::T), amdgpu_waves_per_eu(Dif2Geom<V, PH, CB, TOUT>::TWO_PER_CU ? (CB * PH::T) / 128 : 1)))
 fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* out, const typename VecTraits<V>::W* __restrict__ tw,
                       AxisMap imap, AxisMap omap, TileMap itile, TileMap otile, unsigned ntiles, unsigned tiles_per_a, unsigned a_first,
                       double scale, RotMap rm) {
@@ -1265,7 +1039,6 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
     V* lds = reinterpret_cast<V*>(dfft_smem + DG::TW_BYTES);
     constexpr int NWV = owned_waves<V, CB, T>();
     const int tid = threadIdx.x, c = tid % CB, j = tile_j<CB, NWV>(tid);
-#if DFFT_TW_STAGE_MAJOR
     // (round 6) the same N entries of LDS, laid out for the lanes that read them: [0, NH) the stage-major table of the NH-point stages
     // (every second entry of the N-point table, rows in lane order: tw_row), [NH, N) the first-stage factors W_N^n, n = j + T k, as
     // [k][ids in lane order] -- under the wave-interleaved labelling the lanes of a wavefront hold ids NW apart, and read from the
@@ -1283,15 +1056,6 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
         ldsf[(i / T) * T + fperm(i % T)] = w;
     }
     const W* fst = ldsf + fperm(j);  // factor of point k: fst[T k]
-#else
-    constexpr int TWS_RUN = 2;
-    for (int i = tid; i < N; i += GT) {
-        W w = tw[i];
-        if (DIR < 0) w.y = -w.y;
-        ldstw[i] = w;
-    }
-    const W* fst = ldstw + j;
-#endif
     __syncthreads();
     // Multi-block sides: the launcher guarantees imap.blk % T == 0 and omap.blk % (2 T) == 0, so the block a point falls into
     // depends on k alone -- a wave-uniform 32-bit term per k (computed once) plus ONE per-thread term.  Plain sides: k * step.
@@ -1322,102 +1086,11 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
     const long long ithr = (long long)j * imap.stride + (long long)c * imap.cstride;
     const long long othr = (long long)(2 * j) * omap.stride + (long long)c * omap.cstride;
     const typename real_of<W>::type sc = (typename real_of<W>::type)scale;
-    // -DDFFT_DIF2_PIPELINE=1 (build-time experiment of round 4, measured and NOT adopted; see fft_dual_tiles_kernel): t0 of
-    // 512 x 2048 x 512 fp64 6.19 -> 5.97 ms, but fp32 3.16 -> 3.66, config 5's per-rank t0 3.27 -> 3.37 (12 B of scratch on fp32 pairs).
-#ifndef DFFT_DIF2_PIPELINE
-#define DFFT_DIF2_PIPELINE 0
-#endif
-#if DFFT_DIF2_PIPELINE
-    auto in_ptr = [&](unsigned t) -> const GV* {
-        const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-        // rotated rows of an exchange buffer (RotMap mode 1): the whole tile moves inside its row by the plane's rotation
-        int cbi = (int)(b * CB);
-        if constexpr (ROT == 1) {
-            if (rm.in_mode == 1) cbi = (cbi + rm.rot * (int)(a + (unsigned)rm.a0)) & rm.mask;
-        }
-        return in + (long long)a * itile.a_stride + (long long)cbi * itile.b_stride + ithr;
-    };
-    auto out_ptr = [&](unsigned t) -> GV* {
-        const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-        int cbo = (int)(b * CB);
-        if constexpr (ROT == 1) {
-            if (rm.out_mode == 1) cbo = (cbo + rm.rot * (int)(a + (unsigned)rm.a0)) & rm.mask;
-        }
-        return out + (long long)a * otile.a_stride + (long long)cbo * otile.b_stride + othr;
-    };
-    // the two inputs n = j + T k and n + NH of first-stage butterfly k
-    auto load_pair = [&](unsigned t, int k, V& x0, V& x1) {
-        const GV* ip = in_ptr(t);
-        x0 = VT::from_g(gload<NTL>(ip + in_off(k)));
-        x1 = VT::from_g(gload<NTL>(ip + in_off(k + E)));
-    };
-    auto split = [&](V& x0, V& x1, int k) {  // (x[n], x[n + NH]) -> (a[n], b[n])
-        const V sum = cadd(x0, x1);
-        const V dif = csub(x0, x1);
-        x0 = sum;
-        x1 = cmul(dif, fst[T * k]);  // W_N^{j + T k}
-    };
-    auto process_half = [&](V* v, unsigned t, int h) {
-        run_stages<V, PH, 0, DIR, CB, false, false, TW_LDS, false, 1, TWS_RUN, NWV>(v, ldstw, lds, j, c);
-        GV* op = out_ptr(t);
-#pragma unroll
-        for (int k = 0; k < E; ++k) gstore<NTS>(op + out_off(k) + (long long)h * omap.stride, VT::to_g(cscale(v[k], sc)));
-    };
-    // Software pipeline over tiles, as in fft_dual_tiles_kernel: the registers of a half transform are refilled as soon as
-    // its stores have been issued -- after the even half the input pairs k < E/2 of the next tile, after the odd half the pairs
-    // k >= E/2 -- so that half of the next tile's loads complete underneath the odd half's exchanges.  Loaded registers are not
-    // moved; the register layout alternates between
-    //   layout 0: pair k = (A[k], B[k]);   layout 1: pair k = (A[k], A[E/2 + k]) for k < E/2, (B[k - E/2], B[k]) for k >= E/2
-    // and the first-stage butterfly leaves a[k] in the pair's first register, b[k] in its second.
-    constexpr int EH = E / 2;
-    static_assert(E % 2 == 0, "DIF-split tiles: even number of points per thread");
-    V A[E], B[E];
-    unsigned t = blockIdx.x;
-    if (t < ntiles) {
-#pragma unroll
-        for (int k = 0; k < E; ++k) load_pair(t, k, A[k], B[k]);
-    }
-    const unsigned step = gridDim.x;
-    while (t < ntiles) {
-        {  // layout 0 -> 1
-            const unsigned tn = t + step, tl = tn < ntiles ? tn : t;  // (past the last tile: re-read it, see fft_dual_tiles_kernel)
-#pragma unroll
-            for (int k = 0; k < E; ++k) split(A[k], B[k], k);
-            process_half(A, t, 0);
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_pair(tl, k, A[k], A[EH + k]);
-            process_half(B, t, 1);
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_pair(tl, EH + k, B[k], B[EH + k]);
-            t = tn;
-            if (t >= ntiles) break;
-        }
-        {  // layout 1 -> 0
-            const unsigned tn = t + step, tl = tn < ntiles ? tn : t;
-            V              w0[E], w1[E];
-#pragma unroll
-            for (int k = 0; k < EH; ++k) {
-                split(A[k], A[EH + k], k);
-                split(B[k], B[EH + k], EH + k);
-                w0[k] = A[k];
-                w0[EH + k] = B[k];
-                w1[k] = A[EH + k];
-                w1[EH + k] = B[EH + k];
-            }
-            process_half(w0, t, 0);
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_pair(tl, k, A[k], B[k]);
-            process_half(w1, t, 1);
-#pragma unroll
-            for (int k = 0; k < EH; ++k) load_pair(tl, EH + k, A[EH + k], B[EH + k]);
-            t = tn;
-        }
-    }
-#else
+    // (The software pipeline over tiles of fft_dual_tiles_kernel's experiment was measured here too in round 4 and not adopted:
+    // profiles/r04/experiments/lib_ab_pipelined_2048.log.)
     if constexpr (TOUT) {
-        // Software pipeline over tiles: the next tile's loads are issued as soon as the second image phase has taken the last results out
-        // of the registers -- in front of that phase's stores, so the wait for the loaded points (one vmcnt for loads and stores) lets
-        // those stores drain underneath the next tile's first stage instead of in front of it.
+        // (A software pipeline over tiles -- the next tile's loads issued as soon as the second image phase has taken the last results out
+        // of the registers -- was measured in round 6 and not adopted: 270-300 bytes of scratch, 11-14 % slower, profiles/r06/README.md.)
         constexpr int CH = CB / 2, ON = N / LANES, ROW = DG::ROW;
         auto img_at = [](int col, int e) -> int {  // element e (units of W) of scalar column col of the phase
             if constexpr (DG::PADROW) return col * ROW + e;
@@ -1454,16 +1127,10 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
                 v1[k] = VT::from_g(__builtin_bit_cast(GV, __builtin_amdgcn_raw_buffer_load_b128(rs1, (int)o1, so, NTL ? 2 : 0)));
             }
         };
-        // -DDFFT_DIF2_TOUT_PIPE=1 builds the software pipeline described above: measured and NOT adopted (round 6) -- with the next tile's 2 E
-        // points in flight next to the second phase's image reads the kernel needs 270-300 bytes of scratch (flat or buffer loads alike)
-#ifndef DFFT_DIF2_TOUT_PIPE
-#define DFFT_DIF2_TOUT_PIPE 0
-#endif
         unsigned t = blockIdx.x;
-        if (DFFT_DIF2_TOUT_PIPE && t < ntiles) load_tile(t);
         for (; t < ntiles; t += gridDim.x) {
             const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-            if (!DFFT_DIF2_TOUT_PIPE) load_tile(t);
+            load_tile(t);
 #pragma unroll
             for (int k = 0; k < E; ++k) {
                 const V sum = cadd(v0[k], v1[k]);
@@ -1495,7 +1162,6 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
                         }
                     }
                 }
-                if (DFFT_DIF2_TOUT_PIPE && ph == 1 && t + gridDim.x < ntiles) load_tile(t + gridDim.x);  // every result has left the registers
                 __syncthreads();
 #pragma unroll
                 for (int k = 0; k < E; ++k) {
@@ -1509,18 +1175,7 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
             }
         }
     } else {
-    // half-line tiles (CB columns narrower than a cache line; -DDFFT_DIF2_HALF experiment): the XCD-aware tile order of fft_tiles_kernel --
-    // the Q tiles that share the lines of a row segment go to workgroups on the same XCD
-    constexpr int  Q = (CB * sizeof(V) < 128) ? (int)(128 / (CB * sizeof(V))) : 1;
-    const unsigned remap_full = (Q > 1 && tiles_per_a % Q == 0) ? (ntiles / (8u * Q)) * (8u * Q) : 0u;
-    for (unsigned tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
-        unsigned t = tl;
-        if constexpr (Q > 1) {
-            if (tl < remap_full) {
-                const unsigned xcd = tl & 7u, s = tl >> 3;
-                t = ((s / Q) * 8u + xcd) * Q + (s % Q);
-            }
-        }
+    for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
         // rotated rows of an exchange buffer (RotMap mode 1): the whole tile moves inside its row by the plane's rotation
         int cbi = (int)(b * CB), cbo = (int)(b * CB);
@@ -1552,109 +1207,6 @@ fft_dif2_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>:
             for (int k = 0; k < E; ++k) gstore<NTS>(op + out_off(k) + (long long)h * omap.stride, VT::to_g(cscale(v[k], sc)));
         }
     }
-    }
-#endif
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Radix-3 split at load time (round 6, last session; -DDFFT_DIF3=1, DFFT_DIF3=1): full-line column tiles for N = 3 * NT whose own tile
-// leaves room for ONE workgroup per CU only (768 points: 96 KiB + table).  Thread j of a column holds the points n = j + T k, n + NT and
-// n + 2 NT (k < E; PT = the NT-point plan, E T = NT) -- the three inputs of every first-stage butterfly of a decimation-in-frequency
-// radix-3 step --
-//     u_r[n] = (sum_q x[n + q NT] w3^(q r)) * W_N^(n r)   ->   X[3 m + r] = DFT_NT(u_r)[m],   r = 0, 1, 2
-// and the three NT-point transforms go through one (NT x CB) LDS tile one after the other: 768 fp64 points need 32 KiB + 12 KiB of
-// tables, so THREE workgroups share a CU (fft_dif2_tiles_kernel's argument for 1024 points, profiles/r06/README.md section 1g), with two
-// exchanges per sub-transform instead of three over the whole 96 KiB tile.  W_N^n and W_N^(2 n) (n < NT) come from the N-point table;
-// the NT-point stages read every third entry of it, stage-major, from the LDS copy.  Fast path only: whole tiles, both sides keep the
-// columns of a line together, input blocks multiples of T points, output blocks multiples of 3 T.
-template <class V, class PT, int CB> struct Dif3Geom {
-    using W = typename VecTraits<V>::W;
-    static constexpr size_t TW_BYTES = ((size_t)3 * PT::N * sizeof(W) + 15) / 16 * 16;  // stage-major table + W^n + W^(2n)
-    static constexpr size_t TILE_BYTES = (size_t)PT::N * CB * sizeof(V);
-    static constexpr size_t LDS_BYTES = TW_BYTES + TILE_BYTES;
-    static constexpr int    PER_CU = (int)(160 * 1024 / LDS_BYTES) < 1 ? 1 : (int)(160 * 1024 / LDS_BYTES);
-    static constexpr int    WAVES_PER_EU = (PER_CU * CB * PT::T + 255) / 256;  // waves per SIMD when PER_CU workgroups are resident
-};
-template <class V, class PT, int CB, int DIR, bool NTL, bool NTS, int ROT = 0>
-__global__ void __attribute__((amdgpu_flat_work_group_size(1, CB * PT::T), amdgpu_waves_per_eu(Dif3Geom<V, PT, CB>::WAVES_PER_EU)))
-fft_dif3_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* out, const typename VecTraits<V>::W* __restrict__ tw,
-                      AxisMap imap, AxisMap omap, TileMap itile, TileMap otile, unsigned ntiles, unsigned tiles_per_a, unsigned a_first,
-                      double scale, RotMap rm) {
-    using VT = VecTraits<V>;
-    using W = typename VT::W;
-    using GV = typename VT::G;
-    constexpr int E = PT::E, T = PT::T, GT = CB * T, NT = PT::N;
-    static_assert(PT::S > 1 && E * T == NT && GT <= 1024, "radix-3 split tiles: multi-stage third plan, one workgroup per tile");
-    using DG = Dif3Geom<V, PT, CB>;
-    extern __shared__ __attribute__((aligned(16))) char dfft_smem[];
-    W* ldstw = reinterpret_cast<W*>(dfft_smem);  // [0, NT) stage-major table of the NT-point stages, [NT, 2 NT) W_N^n, [2 NT, 3 NT) W_N^(2 n)
-    V* lds = reinterpret_cast<V*>(dfft_smem + DG::TW_BYTES);
-    constexpr int NWV = owned_waves<V, CB, T>();
-    const int     tid = threadIdx.x, c = tid % CB, j = tile_j<CB, NWV>(tid);
-    fill_stage_major<W, PT, 0, DIR, NWV, 3>(ldstw, tw, tid, GT);
-    auto fperm = [](int jj) -> int {  // (as in fft_dif2_tiles_kernel: the factors in the order the lanes of a wavefront read them)
-        if constexpr (NWV > 1) return (jj % NWV) * (T / NWV) + jj / NWV;
-        else return jj;
-    };
-    for (int i = tid; i < NT; i += GT) {
-        W w1 = tw[i], w2 = tw[2 * i];
-        if (DIR < 0) {
-            w1.y = -w1.y;
-            w2.y = -w2.y;
-        }
-        const int at = (i / T) * T + fperm(i % T);
-        ldstw[NT + at] = w1;
-        ldstw[2 * NT + at] = w2;
-    }
-    const W* f1 = ldstw + NT + fperm(j);  // factors of point k: f1[T k], f2[T k]
-    const W* f2 = ldstw + 2 * NT + fperm(j);
-    __syncthreads();
-    unsigned iuni[3 * E], ouni[E];
-#pragma unroll
-    for (int kk = 0; kk < 3 * E; ++kk) {
-        const int ib = (T * kk) / imap.blk;
-        iuni[kk] = (unsigned)(block_term(imap, ib) + (long long)(T * kk - ib * imap.blk) * imap.stride);
-    }
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-        const int ob = (3 * T * k) / omap.blk;
-        ouni[k] = (unsigned)(block_term(omap, ob) + (long long)(3 * T * k - ob * omap.blk) * omap.stride);
-    }
-    const long long ithr = (long long)j * imap.stride + (long long)c * imap.cstride;
-    const long long othr = (long long)(3 * j) * omap.stride + (long long)c * omap.cstride;
-    const typename real_of<W>::type sc = (typename real_of<W>::type)scale;
-    for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const unsigned al = t / tiles_per_a, b = t - al * tiles_per_a, a = al + a_first;
-        int cbi = (int)(b * CB), cbo = (int)(b * CB);
-        if constexpr (ROT == 1) {  // rotated rows of an exchange buffer (RotMap mode 1): the whole tile moves inside its row
-            const int r = rm.rot * (int)(a + (unsigned)rm.a0);
-            if (rm.in_mode == 1) cbi = (cbi + r) & rm.mask;
-            if (rm.out_mode == 1) cbo = (cbo + r) & rm.mask;
-        }
-        const GV* ip = in + (long long)a * itile.a_stride + (long long)cbi * itile.b_stride + ithr;
-        GV*       op = out + (long long)a * otile.a_stride + (long long)cbo * otile.b_stride + othr;
-        V         v0[E], v1[E], v2[E];
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            v0[k] = VT::from_g(gload<NTL>(ip + (long long)iuni[k]));
-            v1[k] = VT::from_g(gload<NTL>(ip + (long long)iuni[k + E]));
-            v2[k] = VT::from_g(gload<NTL>(ip + (long long)iuni[k + 2 * E]));
-        }
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            V u[3] = {v0[k], v1[k], v2[k]};
-            Butterfly<3, DIR, V>::run(u);
-            v0[k] = u[0];
-            v1[k] = cmul(u[1], f1[T * k]);  // W_N^(j + T k)
-            v2[k] = cmul(u[2], f2[T * k]);  // W_N^(2 (j + T k))
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            V* v = r == 0 ? v0 : (r == 1 ? v1 : v2);
-            run_stages<V, PT, 0, DIR, CB, false, false, TW_LDS, false, 1, 1, NWV>(v, ldstw, lds, j, c);
-#pragma unroll
-            for (int k = 0; k < E; ++k) gstore<NTS>(op + (long long)ouni[k] + (long long)r * omap.stride, VT::to_g(cscale(v[k], sc)));
-        }
     }
 }
 
@@ -1694,15 +1246,7 @@ fft_tload_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>
     if constexpr (KG::TWMODE == TW_GLOBAL) {
         twr = tw;
     } else if constexpr (KG::TWMODE == TW_LDS) {
-#if DFFT_TW_STAGE_MAJOR
         fill_stage_major<W, P, 0, DIR, KG::NW>(ldstw, tw, tid, GT);
-#else
-        for (int i = tid; i < N; i += GT) {
-            W w = tw[i];
-            if (DIR < 0) w.y = -w.y;
-            ldstw[i] = w;
-        }
-#endif
         __syncthreads();
         twr = ldstw;
     } else {
@@ -1850,12 +1394,12 @@ hipError_t launch_variant(const FftLaunch& L, hipStream_t stream, int* blocks_pe
     return hipSuccess;
 }
 
-template <class V, class P, int CB, int DIR, bool NT, bool ROT = false, int WPC = 1> hipError_t launch_dual(const FftLaunch& L, hipStream_t stream) {
+template <class V, class P, int CB, int DIR, bool NT, bool ROT = false> hipError_t launch_dual(const FftLaunch& L, hipStream_t stream) {
     using VT = VecTraits<V>;
     using W = typename VT::W;
     using GV = typename VT::G;
-    constexpr size_t LDS_BYTES = DualGeom<V, P, CB, WPC>::LDS_BYTES;
-    auto kern = fft_dual_tiles_kernel<V, P, CB, DIR, NT, ROT, WPC>;
+    constexpr size_t LDS_BYTES = DualGeom<V, P, CB>::LDS_BYTES;
+    auto kern = fft_dual_tiles_kernel<V, P, CB, DIR, NT, ROT>;
     static std::atomic<bool> attr_set[64];
     static std::mutex        setup_mutex;
     int         dev = 0;
@@ -1871,7 +1415,7 @@ template <class V, class P, int CB, int DIR, bool NT, bool ROT = false, int WPC 
     const long long tiles_per_a = L.ncols / (2 * CB), ntiles = L.na * tiles_per_a;
     if (ntiles <= 0) return hipSuccess;
     if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    long long grid = (long long)device_info().cus * WPC;
+    long long grid = (long long)device_info().cus;
     if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
     if (grid > ntiles) grid = ntiles;
     (void)hipGetLastError();
@@ -1916,43 +1460,6 @@ template <class V, class PH, int CB, int DIR, bool NTL, bool NTS, bool BIN, bool
                        L.omap, L.itile, L.otile, (unsigned)ntiles, (unsigned)tiles_per_a, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);
     e = hipGetLastError();
     if (e != hipSuccess) return launch_debug(e, "kernel launch", (int)LDS_BYTES, CB * PH::T);
-    return hipSuccess;
-}
-
-template <class V, class PT, int CB, int DIR, bool NTL, bool NTS, int ROT = 0> hipError_t launch_dif3(const FftLaunch& L, hipStream_t stream) {
-    using VT = VecTraits<V>;
-    using W = typename VT::W;
-    using GV = typename VT::G;
-    constexpr size_t LDS_BYTES = Dif3Geom<V, PT, CB>::LDS_BYTES;
-    auto kern = fft_dif3_tiles_kernel<V, PT, CB, DIR, NTL, NTS, ROT>;
-    static std::atomic<int> blocks_per_cu[64];  // 0 = not set up on that device yet
-    static std::mutex       setup_mutex;
-    int         dev = 0;
-    hipError_t  e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return launch_debug(e, "hipFuncSetAttribute", (int)LDS_BYTES, CB * PT::T);
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, CB * PT::T, LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks_per_cu[dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-    }
-    const long long tiles_per_a = L.ncols / CB, ntiles = L.na * tiles_per_a;
-    if (ntiles <= 0) return hipSuccess;
-    if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    long long grid = (long long)device_info().cus * blocks_per_cu[dev].load(std::memory_order_relaxed);
-    if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
-    if (grid > ntiles) grid = ntiles;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CB * PT::T), LDS_BYTES, stream, (const GV*)L.in, (GV*)L.out, (const W*)L.tw, L.imap,
-                       L.omap, L.itile, L.otile, (unsigned)ntiles, (unsigned)tiles_per_a, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);
-    e = hipGetLastError();
-    if (e != hipSuccess) return launch_debug(e, "kernel launch", (int)LDS_BYTES, CB * PT::T);
     return hipSuccess;
 }
 
@@ -2027,10 +1534,7 @@ template <class V, class P, int CBO = 0> constexpr bool can_stage_store() {
 }
 
 // the staged transposed LOAD (fft_tload_tiles_kernel) exists where the staged store's image fits, on one-phase tiles of at least 256
-// threads whose linear element order splits evenly over the workgroup.  -DDFFT_TLOAD=0 compiles the path out (A/B builds).
-#ifndef DFFT_TLOAD
-#define DFFT_TLOAD 1
-#endif
+// threads whose linear element order splits evenly over the workgroup.
 template <class V, class P> constexpr bool can_tload() {
     constexpr int CBC = cols_per_tile<V, P>();
     constexpr int GT = CBC * P::T, ON = P::N / VecTraits<V>::LANES;
@@ -2039,7 +1543,7 @@ template <class V, class P> constexpr bool can_tload() {
     // at P = 8 3.65 -> 2.62, 512^3 fp32 0.52 -> 0.455; fp64 256^3 0.1045 -> 0.0893 but 512^3 0.84 -> 0.99 and 1024 x 768 x 512 2.49 ->
     // 2.76 (fp64 already reads whole lines through fft_tiles_kernel and pays here for the extra LDS round trip).
     constexpr bool type_ok = VecTraits<V>::LANES == 2 || P::N <= 256;
-    return DFFT_TLOAD && type_ok && sizeof(V) == 16 && P::S > 1 && can_stage_store<V, P>() && GT >= 256 && GT <= 1024 && (ON % GT == 0 || GT % ON == 0) &&
+    return type_ok && sizeof(V) == 16 && P::S > 1 && can_stage_store<V, P>() && GT >= 256 && GT <= 1024 && (ON % GT == 0 || GT % ON == 0) &&
            (size_t)P::N * CBC * sizeof(V) <= 128 * 1024;
 }
 // run-time side of the same rule (fast path only: single-block maps, whole tiles, rotation -- if any -- per point on the output side)
@@ -2079,9 +1583,6 @@ template <class V, class P> hipError_t launch_rows(const FftLaunch& L, hipStream
 
 // PH: plan of the half length (N / 2 points) for lengths whose non-transposing column passes run DIF-split (void: none)
 // CBO: columns per tile when not cols_per_tile() -- the half-line tiles of the "lean" lengths, see below.
-#ifndef DFFT_LEAN_COLS
-#define DFFT_LEAN_COLS 1
-#endif
 template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan(const FftLaunch& Lin, hipStream_t stream) {
     constexpr int CBC = CBO > 0 ? CBO : cols_per_tile<V, P>();
     constexpr int GC = ConstMax1<256 / (CBC * P::T)>::value;  // column kernel
@@ -2107,21 +1608,11 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
     // kept 52-320 bytes in scratch (profiles/r06/kernel_resources.txt of library b1622e22).  Full-line tiles stay where they are
     // clean -- the Plain twins on single-block maps, the staged store of 1536 fp64 points -- and everything else runs on HALF-line
     // tiles (4 columns: 256-400 threads, twice the register budget, no scratch; the XCD-aware tile order of fft_tiles_kernel gives
-    // the two tiles of a line to one L2).  -DDFFT_LEAN_COLS=0 restores the full-line variants (A/B builds).
-    // -DDFFT_LEAN_EXTRA=1 (experiment, round 6): the same half-line tiles for the packed / rotated variants of 768 and 1024 points, which
-    // do NOT spill -- does a 256-thread workgroup with two or three of its kind resident per CU beat the 512-thread full-line tile?
-    // Measured and NOT adopted (profiles/r06/experiments/lib_ab_lean_extra_768_1024.log, bit-identical): config 4's rank at P = 8
-    // t0 0.56 -> 0.60 ms, t3 0.35 -> 0.46; 1024^3 fp32 at P = 4 1.45 / 0.82 -> 1.58 / 1.16.  What the lean lengths gain is the scratch
-    // they lose, not the geometry.
-#ifndef DFFT_LEAN_EXTRA
-#define DFFT_LEAN_EXTRA 0
-#endif
-    constexpr bool lean_extra = DFFT_LEAN_EXTRA && CBO == 0 && sizeof(V) == 16 && (P::N == 768 || P::N == 1024) && CBC >= 2;
-    if constexpr (lean_extra) {
-        const bool single = L.imap.nblk == 1 && L.imap.sub <= 1 && L.omap.nblk == 1 && L.omap.sub <= 1;
-        if (!general && (rot || !single)) return launch_plan<V, P, void, CBC / 2>(Lin, stream);
-    }
-    constexpr bool lean_len = DFFT_LEAN_COLS && CBO == 0 && sizeof(V) == 16 && (P::N == 1000 || P::N == 1280 || P::N == 1536) && CBC >= 2;
+    // the two tiles of a line to one L2).
+    // (The same half-line tiles for the packed / rotated variants of 768 and 1024 points, which do NOT spill, were measured in round 6
+    // and not adopted: profiles/r06/experiments/lib_ab_lean_extra_768_1024.log.  What the lean lengths gain is the scratch they lose,
+    // not the geometry.)
+    constexpr bool lean_len = CBO == 0 && sizeof(V) == 16 && (P::N == 1000 || P::N == 1280 || P::N == 1536) && CBC >= 2;
     if constexpr (lean_len) {
         const bool single = L.imap.nblk == 1 && L.imap.sub <= 1 && L.omap.nblk == 1 && L.omap.sub <= 1;
         const bool staged = can_stage_store<V, P>() && !general && L.omap.nblk == 1 && L.omap.stride == 1 && L.omap.cstride != 1;
@@ -2173,25 +1664,8 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
         // when columns are adjacent in memory on the input side (forward X pass)
         constexpr bool can_dual = P::S > 1 && sizeof(V) == 16 && 2 * CBC * sizeof(V) == 128 && (P::N & (P::N - 1)) == 0 && (P::N / VecTraits<V>::LANES) % (CBC * P::T) == 0 &&
                                   (size_t)P::N * CBC * sizeof(V) + (size_t)P::N * sizeof(typename VecTraits<V>::W) <= 160 * 1024;
-        // 1024 points (round 4, -DDFFT_DUAL_1024=1): the full-line tile (128 KiB + table) leaves one 512-thread workgroup per CU; paired
-        // half-line tiles of 4 columns need 64 KiB + table = 80 KiB and 256 threads, so TWO workgroups are resident per CU and one
-        // transforms while the other one's loads and stores are in flight (each still fetches whole 128-byte lines: it owns both
-        // tiles of a line).  Measured and NOT adopted (900 parity cases green; profiles/r04/experiments/lib_ab_dual_1024_two_per_cu.log):
-        // slower everywhere -- config 4's shape X pass 2.72 -> 3.27 ms, fp32 1.19 -> 1.60, its rank at P = 8 0.373 -> 0.392: two resident
-        // workgroups that each have nothing in flight underneath their transforms lose to one workgroup with a whole-tile prefetch.
-#ifndef DFFT_DUAL_1024
-#define DFFT_DUAL_1024 0
-#endif
-        constexpr bool can_dual2 = DFFT_DUAL_1024 && P::N == 1024 && P::E == 16 && sizeof(V) == 16 && (P::N / VecTraits<V>::LANES) % (4 * P::T) == 0;
-        if constexpr (can_dual2) {
-            constexpr int CBH = 4;
-            const bool    transposed = L.omap.nblk == 1 && L.omap.stride == 1 && L.omap.cstride != 1;
-            if (!general && transposed && L.imap.blk % P::T == 0 && L.ncols % (2 * CBH) == 0 && L.imap.cstride == 1 && L.itile.b_stride == 1 &&
-                (!rot || (L.rot.in_mode == 2 && L.rot.out_mode == 0))) {
-                if (rot) return L.dir > 0 ? launch_dual<V, P, CBH, +1, true, true, 2>(L, stream) : launch_dual<V, P, CBH, -1, true, true, 2>(L, stream);
-                return L.dir > 0 ? launch_dual<V, P, CBH, +1, true, false, 2>(L, stream) : launch_dual<V, P, CBH, -1, true, false, 2>(L, stream);
-            }
-        }
+        // (1024 points on paired half-line tiles with two workgroups per CU were measured in round 4 and not adopted -- slower everywhere:
+        // profiles/r04/experiments/lib_ab_dual_1024_two_per_cu.log.)
         // The same kernel for the 1024-point forward X pass (round 6, config 4's t3): two 512-point half transforms through a 64 KiB tile
         // + 16 KiB table = 80 KiB, so TWO workgroups share a CU and one transforms while the other's loads and stores are in flight (at most
         // 128 registers each: Dif2Geom::TWO_PER_CU) -- instead of TuneTransposedStoreFull's one 128 KiB tile with a whole-tile prefetch.
@@ -2200,14 +1674,7 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
         // fp32 pairs with rotated rows (P > 1) 0.175 -> 0.162 and 0.828 -> 0.795, but on the padded hand-over buffer of a single-GPU plan
         // 1.08 -> 1.19 and 2.81 -> 3.13 -- and a rule "pairs only with rotated rows" would give up the bit-identity of rotated and
         // un-rotated pipelines (test_rotated_exchange_rows_vs_oracle), so 1024-point pairs stay on TuneTransposedStoreFull.
-        // -DDFFT_X_DIF2_1024=0 compiles it out.
-#ifndef DFFT_X_DIF2_1024
-#define DFFT_X_DIF2_1024 1
-#endif
-#ifndef DFFT_DIF2_HALF
-#define DFFT_DIF2_HALF 0
-#endif
-        if constexpr (!std::is_void<PH>::value && ((VecTraits<V>::LANES == 2 && P::N >= 2048) || (DFFT_X_DIF2_1024 && P::N == 1024 && VecTraits<V>::LANES == 1))) {  // (fp64 2048: 108-116 bytes of scratch next to the rotated-row image -- stays on the paired tiles)
+        if constexpr (!std::is_void<PH>::value && ((VecTraits<V>::LANES == 2 && P::N >= 2048) || (P::N == 1024 && VecTraits<V>::LANES == 1))) {  // (fp64 2048: 108-116 bytes of scratch next to the rotated-row image -- stays on the paired tiles)
             // forward X pass of lengths whose full-line tile does not fit the LDS (2048 points): DIF-split full-line tiles with the
             // staged transposed store (round 6; fft_dif2_tiles_kernel, TOUT).  DFFT_X_DIF2=0: the paired half-line tiles of rounds 2-5.
             static const bool x_dif2 = [] {
@@ -2237,33 +1704,8 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
                 return L.dir > 0 ? launch_dual<V, P, CBC, +1, true>(L, stream) : launch_dual<V, P, CBC, -1, true>(L, stream);
             }
         }
-#ifndef DFFT_DIF3
-#define DFFT_DIF3 0
-#endif
-#if DFFT_DIF3
-        if constexpr (P::N == 768 && VecTraits<V>::LANES == 1) {
-            // radix-3 split tiles (fft_dif3_tiles_kernel): three 256-point sub-transforms through a 32 KiB tile, three workgroups per CU
-            using PT3 = Plan<256, 8, 8, 8, 4>;
-            constexpr int CB3 = 128 / (int)sizeof(V);
-            static const bool dif3 = [] {
-                const char* e = getenv("DFFT_DIF3");
-                return e && *e == '1';
-            }();
-            const bool lines = L.imap.cstride == 1 && L.itile.b_stride == 1 && L.omap.cstride == 1 && L.otile.b_stride == 1;
-            const bool even3 = L.ncols % CB3 == 0 && L.imap.last_delta == 0 && L.omap.last_delta == 0;
-            const bool fit3 = axis_max_offset(L.imap, P::N) < (1ll << 32) && axis_max_offset(L.omap, P::N) < (1ll << 32);
-            const bool rot3 = !rot || (L.rot.in_mode != 2 && L.rot.out_mode != 2);
-            if (dif3 && !general && lines && even3 && fit3 && rot3 && L.imap.blk % PT3::T == 0 && L.omap.blk % (3 * PT3::T) == 0) {
-                const bool s_in = (L.hints & FFT_HINT_STREAM_IN) != 0, s_out = (L.hints & FFT_HINT_STREAM_OUT) != 0;
-                if (rot) {
-                    if (L.dir > 0) return s_out ? launch_dif3<V, PT3, CB3, +1, false, true, 1>(L, stream) : launch_dif3<V, PT3, CB3, +1, false, false, 1>(L, stream);
-                    return s_in ? launch_dif3<V, PT3, CB3, -1, true, false, 1>(L, stream) : launch_dif3<V, PT3, CB3, -1, false, false, 1>(L, stream);
-                }
-                if (L.dir > 0) return s_out ? launch_dif3<V, PT3, CB3, +1, false, true>(L, stream) : launch_dif3<V, PT3, CB3, +1, false, false>(L, stream);
-                return s_in ? launch_dif3<V, PT3, CB3, -1, true, false>(L, stream) : launch_dif3<V, PT3, CB3, -1, false, false>(L, stream);
-            }
-        }
-#endif
+        // (Radix-3 split tiles for 768 points -- three 256-point sub-transforms through a 32 KiB tile, three workgroups per CU -- were
+        // measured in round 6 and not adopted: profiles/r06/experiments/lib_ab_768_dif3.log.)
         if constexpr (!std::is_void<PH>::value) {
             // full-line tiles through the DIF split whenever both sides keep the 8 (16 fp32) columns of a line together
             constexpr int CBF = 128 / (int)sizeof(V);
@@ -2296,17 +1738,8 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
                 L.omap.blk % (2 * PH::T) == 0 && (!rot || rot_tile)) {
                 if (rot) {
                     if (L.dir > 0) {
-#if DFFT_DIF2_HALF
-                        // experiment (round 6): the packing Y pass of 2048-point column pairs on HALF-line tiles (4 pairs: 64 KiB half tile +
-                        // 16 KiB table, two workgroups per CU) -- DFFT_Y_DIF2_HALF=1 selects it
-                        if constexpr (VecTraits<V>::LANES == 2 && P::N == 2048) {
-                            static const bool half = [] {
-                                const char* e = getenv("DFFT_Y_DIF2_HALF");
-                                return e && *e == '1';
-                            }();
-                            if (half && sout && L.ncols % (CBF / 2) == 0) return launch_dif2<V, PH, CBF / 2, +1, false, true, true, true, 1>(L, stream);
-                        }
-#endif
+                        // (half-line tiles with two workgroups per CU for the packing Y pass of 2048-point column pairs were measured in
+                        // round 6 and not adopted: profiles/r06/experiments/lib_ab_y_pass_2048_half_line.log)
                         if (sout) return launch_dif2<V, PH, CBF, +1, false, true, true, true, 1>(L, stream);
                         return launch_dif2<V, PH, CBF, +1, false, false, true, true, 1>(L, stream);
                     }

@@ -251,7 +251,7 @@ static int launch_zy_stage(dfft_plan_s* p, const void* src, void* w, long long w
     L.dst = dst;
     L.src_plane = L.dst_plane = p->N[1] * p->N[2];
     if (structure > 0 && p->direction < 0) L.src_plane = p->wl.plane;  // rows read the (plane-padded) hand-over buffer
-    L.w_plane = w_plane; DFFT_ZY_SET_PITCH(L, (p->wbuf && w == p->wbuf) ? p->wl.pitch : p->N[2]);
+    L.w_plane = w_plane;
     L.plane0 = x0;
     L.nplanes = nx;
     L.chunk = zy_phase_planes(p, nx, packed && p->direction == DFFT_FORWARD);
@@ -579,8 +579,7 @@ static int execute_backward(dfft_plan_s* p, bool sync) {
     // Y columns (in place on the intermediate, or unpacking the receive buffer into it), then Z rows into the result: one launch
     // single-GPU plans with a hand-over buffer: rows first (dfft_zy.hip, SIGN) -- Z rows hand-over buffer -> result buffer, Y columns in place
     // on the result buffer; the transform is the same, its strided side moves from HBM reads to the cache-resident chunk
-    // (the kernel's row-producing source path reads rows n2 apart: a hand-over buffer with padded ROWS -- the -DDFFT_ZY_ROW_PITCH=1 build
-    // only -- keeps columns first)
+    // (the kernel's row-producing source path reads rows n2 apart: a hand-over buffer with padded ROWS keeps columns first)
     if (one_launch && p->zy_inv_rows_first && xw && p->zy_lazy && p->wl.pitch == n2) DFFT_TRY(launch_zy_stage(p, p->wbuf, ybuf, n1 * n2, nullptr, nullptr, false, 0, p->xs, +1));
     else if (one_launch) DFFT_TRY(launch_zy_stage(p, nullptr, fused ? ydst : ybuf, yl.plane, ybuf, y_unpacks ? p->buf1 : nullptr, y_unpacks, 0, p->xs));
     for (long long x0 = 0; !one_launch && x0 < p->xs; x0 += cp) {  // Y then Z per cache-sized chunk of planes (see execute_forward)
@@ -893,7 +892,7 @@ int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2
         // one-launch t0 (dfft_zy.hip): where the kernel exists and the plan has the unpadded-row hand-over buffer it works on
         const char* oe = getenv("DFFT_T0_ONE_LAUNCH");
         const long long ysub = p->sy.blk / std::max(1, p->ycuts);
-        const bool      single_ok = !p->exch && (!p->wbuf || p->wl.pitch == n2 || DFFT_ZY_ROW_PITCH);
+        const bool      single_ok = !p->exch && (!p->wbuf || p->wl.pitch == n2);
         const bool      multi_ok = p->exch && n0 % total_devices == 0 && n1 % total_devices == 0 && n1 >= 8 && ysub % zy_col_threads((int)n1, p->zy_lazy ? 1 : 0) == 0;  // even splits; a
                                    // destination block is a whole number of the column unit's strides (the threads of one column FFT)
         // Where the stage is used by itself (DFFT_T0_ONE_LAUNCH=0: never; =1: wherever the kernel exists on single-GPU plans; =all:

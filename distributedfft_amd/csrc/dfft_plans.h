@@ -14,15 +14,7 @@
 // geometry of every other plane shape of the one-launch YZ stage (dfft_zy.hip), which is what this plan is chosen for: as a two-launch
 // column kernel it measures equal to 24 points x 32 threads (radix 8 8 4 3, 256-thread workgroups; profiles/r04/experiments/
 // lib_ab_768_e12.log, profiles/r05/experiments/variant_ab_768_e12.log), inside the one-launch stage 24 x 32 leaves four waves per CU for
-// the row units and loses 20 % (profiles/r05/README.md section 3).  -DDFFT_768_E12=0 builds the 24-point plan.
-#ifndef DFFT_768_E12
-#define DFFT_768_E12 1
-#endif
-#if DFFT_768_E12
-#define DFFT_PLAN_768(X) X(768, 4, 12, 4, 4, 4, 4, 3)
-#else
-#define DFFT_PLAN_768(X) X(768, 4, 24, 8, 8, 4, 3)
-#endif
+// the row units and loses 20 % (profiles/r05/README.md section 3).
 
 #define DFFT_PLAN_TABLE(X)        \
     X(2, 0, 2, 2)                 \
@@ -52,7 +44,7 @@
     X(343, 2, 7, 7, 7, 7)         \
     X(384, 3, 24, 8, 8, 3, 2)     \
     X(512, 3, 8, 8, 8, 8)         \
-    DFFT_PLAN_768(X)              \
+    X(768, 4, 12, 4, 4, 4, 4, 3)  \
     X(1024, 5, 16, 8, 8, 8, 2)    \
     X(2048, 6, 16, 8, 8, 8, 4)    \
     X(40, 7, 20, 5, 4, 2)         \

@@ -40,10 +40,8 @@ namespace {
 
 typedef unsigned zy_u32x4 __attribute__((ext_vector_type(4)));
 // cache policy of the send-buffer stores of SIG launches: sc1 (16, write-through) | nt (2, streaming: the send buffer is not read again by
-// this device and must not push the Z -> Y intermediate out of the Infinity Cache).  -DDFFT_ZY_SIG_AUX=16: sc1 alone (A/B)
-#ifndef DFFT_ZY_SIG_AUX
-#define DFFT_ZY_SIG_AUX 18
-#endif
+// this device and must not push the Z -> Y intermediate out of the Infinity Cache).  (16 would be sc1 alone.)
+constexpr int kZySigAux = 18;
 #define DFFT_ZY_AGENT __HIP_MEMORY_SCOPE_AGENT
 
 // DIR = +1: producers = Z rows (src -> w), consumers = Y columns (w in place)
@@ -81,11 +79,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(ZyTile<PY, PACK>::THR
 zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const double2* __restrict__ twz, const double2* __restrict__ twy,
                 long long src_plane, long long w_plane, long long dst_plane, unsigned plane0, unsigned nplanes, unsigned chunk,
                 unsigned ticket_base, unsigned done_base, AxisMap pk, long long pk_plane, RotMap rm, unsigned* err_host, unsigned spin_polls, unsigned need,
-                unsigned* part_done, unsigned part_planes
-#if DFFT_ZY_ROW_PITCH
-                , unsigned wpitch
-#endif
-                ) {
+                unsigned* part_done, unsigned part_planes) {
     using V = double2;
     constexpr int CB = ZyTile<PY, PACK>::CB;  // columns per tile: one cache line, or two for 256-point Y axes (ZyTile)
     constexpr int THREADS = ZyTile<PY, PACK>::THREADS;
@@ -105,12 +99,6 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
     constexpr bool     TWPZ = TWMZ == TW_REG, TWPY = TWMY == TW_REG;
     constexpr size_t   TWZ_BYTES = TWMZ == TW_LDS ? (size_t)N2 * sizeof(V) : 0, TWY_BYTES = TWMY == TW_LDS ? (size_t)N1 * sizeof(V) : 0;
     constexpr int      ROW_LDS = N2 + N2 / 8;  // padded row (lds_index<1, true>)
-// row pitch of w: the compile-time N2, or the launch parameter of the -DDFFT_ZY_ROW_PITCH=1 build (dfft_zy.h)
-#if DFFT_ZY_ROW_PITCH
-#define DFFT_ZY_WP ((int)wpitch)
-#else
-#define DFFT_ZY_WP N2
-#endif
 
     extern __shared__ __attribute__((aligned(16))) char dfft_smem[];
     unsigned* shw = reinterpret_cast<unsigned*>(dfft_smem);  // [0] ticket broadcast, [1] dependency state
@@ -222,7 +210,7 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
         return ok;
     };
     auto wrsrc = [&](unsigned plane) {  // buffer descriptor of one plane of w (offsets inside a plane fit 32 bits)
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(w + (long long)plane * w_plane), 0, (int)((size_t)N1 * DFFT_ZY_WP * sizeof(V)), 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(w + (long long)plane * w_plane), 0, (int)((size_t)N1 * N2 * sizeof(V)), 0x00020000);
     };
     // packed side (PACK): point jy + TY k of a column lies in block (TY k) / pk.blk of the map -- the launcher guarantees
     // pk.blk % TY == 0, so the block term is wave-uniform per k (computed once) -- plus one per-thread term and the tile's base
@@ -265,7 +253,7 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
             const __amdgpu_buffer_rsrc_t rs = wrsrc(plane);
 #pragma unroll
             for (int k = 0; k < EZ; ++k) {
-                const unsigned elem = (unsigned)((un * GR + gz) * DFFT_ZY_WP + jz + TZ * k);
+                const unsigned elem = (unsigned)((un * GR + gz) * N2 + jz + TZ * k);
                 d[k] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(elem * 16u), 0, 16 /* sc1 */));
             }
         }
@@ -275,7 +263,7 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
             const __amdgpu_buffer_rsrc_t rs = wrsrc(plane);
 #pragma unroll
             for (int k = 0; k < EZ; ++k) {
-                const unsigned elem = (unsigned)((un * GR + gz) * DFFT_ZY_WP + jz + TZ * k);
+                const unsigned elem = (unsigned)((un * GR + gz) * N2 + jz + TZ * k);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(zy_u32x4, v[k]), rs, (int)(elem * 16u), 0, 16 /* sc1 */);
             }
         } else {
@@ -290,7 +278,7 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
             const __amdgpu_buffer_rsrc_t rs = wrsrc(plane);
 #pragma unroll
             for (int k = 0; k < EY; ++k) {
-                const unsigned elem = (unsigned)((jy + TY * k) * DFFT_ZY_WP + un * CB + cy);
+                const unsigned elem = (unsigned)((jy + TY * k) * N2 + un * CB + cy);
                 d[k] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(elem * 16u), 0, 16 /* sc1 */));
             }
         } else if constexpr (PACK) {
@@ -298,9 +286,9 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
 #pragma unroll
             for (int k = 0; k < EY; ++k) d[k] = gload<true>(ip + pk_off(k));
         } else {
-            const V* ip = w + (long long)plane * w_plane + (long long)jy * DFFT_ZY_WP + un * CB + cy;
+            const V* ip = w + (long long)plane * w_plane + (long long)jy * N2 + un * CB + cy;
 #pragma unroll
-            for (int k = 0; k < EY; ++k) d[k] = ip[(long long)(TY * k) * DFFT_ZY_WP];
+            for (int k = 0; k < EY; ++k) d[k] = ip[(long long)(TY * k) * N2];
         }
     };
     auto store_cols = [&](unsigned plane, unsigned un, const V* v) {
@@ -314,20 +302,20 @@ zy_chunk_kernel(const double2* src, double2* w, double2* dst, ZyCtl* ctl, const 
             const unsigned               thr = (unsigned)pk_thr;
 #pragma unroll
             for (int k = 0; k < EY; ++k)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(zy_u32x4, v[k]), rs, (int)((thr + pk_off(k)) * 16u), 0, DFFT_ZY_SIG_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(zy_u32x4, v[k]), rs, (int)((thr + pk_off(k)) * 16u), 0, kZySigAux);
         } else if constexpr (ROWS_PRODUCE && PACK) {
             V* op = dst + pk_base(plane, un);  // the send buffer: not read again by this device, streamed out
 #pragma unroll
             for (int k = 0; k < EY; ++k) gstore<true>(op + pk_off(k), v[k]);
         } else if constexpr (ROWS_PRODUCE) {
-            V* op = w + (long long)plane * w_plane + (long long)jy * DFFT_ZY_WP + un * CB + cy;
+            V* op = w + (long long)plane * w_plane + (long long)jy * N2 + un * CB + cy;
 #pragma unroll
-            for (int k = 0; k < EY; ++k) op[(long long)(TY * k) * DFFT_ZY_WP] = v[k];
+            for (int k = 0; k < EY; ++k) op[(long long)(TY * k) * N2] = v[k];
         } else {
             const __amdgpu_buffer_rsrc_t rs = wrsrc(plane);
 #pragma unroll
             for (int k = 0; k < EY; ++k) {
-                const unsigned elem = (unsigned)((jy + TY * k) * DFFT_ZY_WP + un * CB + cy);
+                const unsigned elem = (unsigned)((jy + TY * k) * N2 + un * CB + cy);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(zy_u32x4, v[k]), rs, (int)(elem * 16u), 0, 16 /* sc1 */);
             }
         }
@@ -502,25 +490,16 @@ template <class PZ, class PY, int DIR, bool PACK, bool LAZY = false, int SIGN = 
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), LDS_BYTES, stream, (const double2*)L.src, (double2*)L.w, (double2*)L.dst, L.ctl,
                        (const double2*)L.twz, (const double2*)L.twy, L.src_plane, L.w_plane, L.dst_plane, (unsigned)L.plane0, (unsigned)L.nplanes,
-                       (unsigned)L.chunk, L.ticket_base, L.done_base, L.pk, L.pk_plane, L.rot, L.err_host, L.spin_polls, UA + (L.fault ? 1u : 0u), L.part_done, (unsigned)L.part_planes
-#if DFFT_ZY_ROW_PITCH
-                       , (unsigned)L.w_pitch
-#endif
-    );
+                       (unsigned)L.chunk, L.ticket_base, L.done_base, L.pk, L.pk_plane, L.rot, L.err_host, L.spin_polls, UA + (L.fault ? 1u : 0u), L.part_done, (unsigned)L.part_planes);
     return hipGetLastError();
 }
 
 using P256 = Plan<256, 8, 8, 8, 4>;
 using P512 = Plan<512, 8, 8, 8, 8>;
-// the library's column plan for 768 points (dfft_plans.h), so that the arithmetic is the two-launch path's: 24 points x 32 threads
-// (256-thread units) or, -DDFFT_768_E12=1, 12 points x 64 threads (512-thread units like the other plane shapes)
-#if DFFT_768_E12
+// the library's column plan for 768 points (dfft_plans.h), so that the arithmetic is the two-launch path's: 12 points x 64 threads
+// (512-thread units like the other plane shapes)
 using P768 = Plan<768, 12, 4, 4, 4, 4, 3>;
 constexpr int ZY_E768 = 12;
-#else
-using P768 = Plan<768, 24, 8, 8, 4, 3>;
-constexpr int ZY_E768 = 24;
-#endif
 
 // host-side mirror of the kernel's geometry: threads per workgroup, columns per tile, rows per row unit
 struct ZyGeom {
@@ -585,9 +564,6 @@ unsigned zy_tickets(int n1, int n2, int dir, int packed, long long nplanes, long
 hipError_t launch_zy(const ZyLaunch& L, hipStream_t stream) {
     if (!zy_supported(L.dtype, L.n1, L.n2) || L.nplanes <= 0 || L.plane0 + L.nplanes > ZY_MAX_PLANES || L.chunk <= 0 || !L.err_host || L.spin_polls == 0)
         return hipErrorInvalidValue;
-#if DFFT_ZY_ROW_PITCH
-    if (L.w_pitch < L.n2 || (long long)L.n1 * L.w_pitch * 16 >= (1ll << 31)) return hipErrorInvalidValue;  // (32-bit buffer offsets inside a plane)
-#endif
 #define DFFT_ZY_CASE(NZ, NY, PZ_, PY_)                                                                                           \
     if (L.n2 == NZ && L.n1 == NY) {                                                                                             \
         if (L.lazy && !L.packed && L.dir > 0 && L.sign < 0) return launch_zy_t<PZ_, PY_, +1, false, true, -1>(L, stream);                         \

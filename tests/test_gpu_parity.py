@@ -844,8 +844,8 @@ def test_rotated_exchange_rows_vs_oracle(gpu, N, P, prec, monkeypatch):
                                  ((1024, 16, 32), 2), ((512, 16, 32), 1), ((256, 16, 64), 2)])
 def test_2048_point_tiles_for_every_tile_count(gpu, N, P, prec, monkeypatch):
     """The 2048-point kernels (paired half-line tiles of the transposing X pass, DIF-split full-line tiles of the other column
-    passes) are persistent: a workgroup's first, later and last tiles take different paths through the loop (more so in the
-    software-pipelined builds, -DDFFT_DUAL_PIPELINE=1 / -DDFFT_DIF2_PIPELINE=1, whose register layout alternates from tile to tile).
+    passes) are persistent: a workgroup's first, later and last tiles take different paths through the loop (more so in any
+    software-pipelined form of them, whose register layout alternates from tile to tile).
     The same holds for the staged transposed LOAD of the inverse X pass (fft_tload_tiles_kernel: fp32 column pairs of 256 ... 2048
     points, fp64 up to 256 points), which prefetches the next tile's raw elements -- the shapes with a 256- / 512- / 1024-point X axis.
     DFFT_X_GRID / DFFT_Y_GRID cap the persistent grid: 1, 2, 3 and 5 workgroups give every workgroup several tiles, odd and even

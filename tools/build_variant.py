@@ -14,7 +14,7 @@ obj = B.LIBDIR / f"obj_variant_{name}"
 obj.mkdir(parents=True, exist_ok=True)
 units = [(B.CSRC / "dfft_fft_inst.hip", obj / f"dfft_fft_inst_{g}.o", [f"-DDFFT_INST_GROUP={g}"] + flags) for g in range(B.NUM_INST_GROUPS)]
 units.append((B.CSRC / "dfft_zy.hip", obj / "dfft_zy.o", flags))  # the one-launch YZ stage has build-time switches of its own
-# ... some of which the plan has to know (DFFT_ZY_ROW_PITCH): every host unit that includes dfft_zy.h
+# ... which the plan may have to know (a switch that changes ZyLaunch): every host unit that includes dfft_zy.h
 zy_h = (B.CSRC / "dfft_zy.h").resolve()
 units += [(B.CSRC / f"{n}.cpp", obj / f"{n}.o", ["-x", "hip"] + flags) for n in B.HOST_UNITS if zy_h in B._deps(B.CSRC / f"{n}.cpp")]
 with ThreadPoolExecutor(max_workers=8) as ex:
