@@ -56,12 +56,6 @@ struct FusedLaunch {
     double      scale;
 };
 
-template <int N> struct BsPlanFor;
-#define DFFT_DECL_BS_PLAN(N, GRP, E, ...) \
-    template <> struct BsPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_BS_PLAN)
-#undef DFFT_DECL_BS_PLAN
-
 // entry point of padded length N: defined (and explicitly instantiated) in the translation unit of N's group only
 template <bool ON, int N> struct BsInst {};
 template <int N> struct BsInst<true, N> {
@@ -89,24 +83,6 @@ template <class V, class P, bool COLS> struct BsGeom {
     using KG = KernelGeom<V, P, CB, G, TuneDefault>;
 };
 
-// the forward twiddles of the M-point stages, exactly as fft_tiles_kernel sets them up
-template <class V, class P, class KG>
-__device__ __forceinline__ const typename VecTraits<V>::W* bs_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
-                                                                      const typename VecTraits<V>::W* __restrict__ tw, int j) {
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        return tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<typename VecTraits<V>::W, P, 0, +1, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        return ldstw;
-    } else {
-        load_twiddles<typename VecTraits<V>::W, P, 0, +1, true>(twreg, tw, j);
-        return twreg;
-    }
-}
-
-template <class V> __device__ __forceinline__ V bs_conj(V a) { return V{a.x, -a.y}; }
-
 // One launch per call: thread group g of a workgroup owns tile r0 + g -- a row (COLS = false: data[r][n]) or CB adjacent columns of one
 // batch item (COLS = true: data[b][n][s], tile = b * tiles_per_b + column block).  `in` and `out` may be the same buffer: a tile reads
 // all its points before the first exchange and writes them after the last one, and no two tiles share an element.
@@ -126,7 +102,7 @@ __device__ __forceinline__ void bluestein_tiles(const V* in, V* out, const typen
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * KG::LDS_ELEMS;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = bs_twiddles<V, P, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const RT  sc = (RT)scale;
     for (unsigned r0 = blockIdx.x * G; r0 < tiles; r0 += gridDim.x * G) {
         const unsigned t = r0 + g;
@@ -153,7 +129,7 @@ __device__ __forceinline__ void bluestein_tiles(const V* in, V* out, const typen
         run_stages<V, P, 0, +1, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, c);
         // A . B^, conjugated: the inverse transform is conj(FFT_M(conj(A . B^))) (1/M is in B^)
 #pragma unroll
-        for (int k = 0; k < E; ++k) v[k] = bs_conj(cmul(v[k], bhat[j + T * k]));
+        for (int k = 0; k < E; ++k) v[k] = cconj(cmul(v[k], bhat[j + T * k]));
         group_sync<KG::WAVE_LOCAL>();  // the second transform's exchanges reuse the tile
         run_stages<V, P, 0, +1, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, c);
         if (valid) {
@@ -161,7 +137,7 @@ __device__ __forceinline__ void bluestein_tiles(const V* in, V* out, const typen
 #pragma unroll
             for (int k = 0; k < E; ++k) {
                 const int idx = j + T * k;
-                if (idx < n) op[(unsigned)idx * ustep] = cscale(cmul(bs_conj(v[k]), chirp[idx]), sc);
+                if (idx < n) op[(unsigned)idx * ustep] = cscale(cmul(cconj(v[k]), chirp[idx]), sc);
             }
         }
         group_sync<KG::WAVE_LOCAL>();  // the next tile's exchanges reuse the tile
@@ -182,34 +158,18 @@ bluestein_cols_kernel(const V* in, V* out, const typename VecTraits<V>::W* __res
     bluestein_tiles<V, P, true>(in, out, tw, chirp, bhat, n, s, tiles, tiles_per_b, scale);
 }
 
-// persistent grid: resident workgroups per CU (occupancy query, once per kernel and device) times the CUs, at most one per tile group
-template <class KG> int bs_blocks_per_cu(const void* kern, std::atomic<int>* cache) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    int occ = cache[dev].load(std::memory_order_acquire);
-    if (occ > 0) return occ;
-    if (KG::LDS_BYTES > 64 * 1024 &&
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KG::LDS_BYTES) != hipSuccess)
-        return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, KG::THREADS, KG::LDS_BYTES) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-        occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, KG::LDS_BYTES));
-    }
-    cache[dev].store(occ, std::memory_order_release);
-    return occ;
-}
-
 template <class V, class P> hipError_t launch_bluestein(const FusedLaunch& F, hipStream_t stream) {
     using W = typename VecTraits<V>::W;
-    static std::atomic<int> occ_rows[64], occ_cols[64];
+    static std::atomic<int> occ_rows[kMaxDevices], occ_cols[kMaxDevices];
+    hipError_t              e;
     (void)hipGetLastError();
     if (F.s == 1) {
         using KG = typename BsGeom<V, P, false>::KG;
         constexpr int G = BsGeom<V, P, false>::G;
         if (F.batch >= (1ll << 31)) return hipErrorInvalidValue;
-        const int occ = bs_blocks_per_cu<KG>(reinterpret_cast<const void*>(bluestein_rows_kernel<V, P>), occ_rows);
-        if (occ < 0) return hipErrorInvalidDevice;
-        const long long grid = std::min<long long>((long long)device_info().cus * occ, (F.batch + G - 1) / G);
+        const int occ = resident_blocks_per_cu(reinterpret_cast<const void*>(bluestein_rows_kernel<V, P>), KG::THREADS, KG::LDS_BYTES, occ_rows, &e);
+        if (occ == 0) return e;
+        const long long grid = persistent_grid(device_info().cus, occ, (F.batch + G - 1) / G);
         hipLaunchKernelGGL((bluestein_rows_kernel<V, P>), dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const V*)F.in,
                            (V*)F.out, (const W*)F.tw, (const V*)F.chirp, (const V*)F.bhat, F.n, (unsigned)F.batch, F.scale);
     } else {
@@ -217,9 +177,9 @@ template <class V, class P> hipError_t launch_bluestein(const FusedLaunch& F, hi
         constexpr int   G = BsGeom<V, P, true>::G, CB = BsGeom<V, P, true>::CB;
         const long long per_b = (F.s + CB - 1) / CB, tiles = F.batch * per_b;
         if (tiles >= (1ll << 31) || (long long)F.n * F.s >= (1ll << 31)) return hipErrorInvalidValue;
-        const int occ = bs_blocks_per_cu<KG>(reinterpret_cast<const void*>(bluestein_cols_kernel<V, P>), occ_cols);
-        if (occ < 0) return hipErrorInvalidDevice;
-        const long long grid = std::min<long long>((long long)device_info().cus * occ, (tiles + G - 1) / G);
+        const int occ = resident_blocks_per_cu(reinterpret_cast<const void*>(bluestein_cols_kernel<V, P>), KG::THREADS, KG::LDS_BYTES, occ_cols, &e);
+        if (occ == 0) return e;
+        const long long grid = persistent_grid(device_info().cus, occ, (tiles + G - 1) / G);
         hipLaunchKernelGGL((bluestein_cols_kernel<V, P>), dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const V*)F.in,
                            (V*)F.out, (const W*)F.tw, (const V*)F.chirp, (const V*)F.bhat, F.n, F.s, (unsigned)tiles, (unsigned)per_b,
                            F.scale);
@@ -228,8 +188,8 @@ template <class V, class P> hipError_t launch_bluestein(const FusedLaunch& F, hi
 }
 
 template <int N> hipError_t BsInst<true, N>::run(const FusedLaunch& F, hipStream_t stream) {
-    if (F.dtype == F64) return launch_bluestein<double2, typename BsPlanFor<N>::type>(F, stream);
-    if (F.dtype == F32) return launch_bluestein<float2, typename BsPlanFor<N>::type>(F, stream);
+    if (F.dtype == F64) return launch_bluestein<double2, typename PlanFor<N>::type>(F, stream);
+    if (F.dtype == F32) return launch_bluestein<float2, typename PlanFor<N>::type>(F, stream);
     return hipErrorInvalidValue;
 }
 #define DFFT_BS_INST(N, GRP, E, ...) template struct BsInst<(GRP == DFFT_INST_GROUP && N >= kFusedMinM), N>;

@@ -40,6 +40,7 @@ template <int DIR, class V> __device__ __forceinline__ V mul_mi(V a) {
     return V{-a.y, a.x};
 }
 template <class V, class R> __device__ __forceinline__ V cscale(V a, R s) { return V{a.x * s, a.y * s}; }
+template <class V> __device__ __forceinline__ V cconj(V a) { return V{a.x, -a.y}; }
 
 template <int R, int DIR, class V> struct Butterfly;
 

@@ -15,12 +15,9 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the multiply and the re-layout kernel).
-#include "dfft_fft_impl.h"
+#include "dfft_conv_impl.h"
 #include "dfft_internal.h"
-#include "dfft_plans.h"
-#include "dfft_conv.h"
 
-#include <algorithm>
 #include <atomic>
 
 #ifndef DFFT_INST_GROUP
@@ -29,14 +26,6 @@
 
 namespace dfft {
 
-constexpr bool conv_fused_n(int n) { return n == 64 || n == 128 || n == 256 || n == 384 || n == 512 || n == 768 || n == 1024; }
-
-template <int N> struct XcPlanFor;
-#define DFFT_DECL_XC_PLAN(N, GRP, E, ...) \
-    template <> struct XcPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_XC_PLAN)
-#undef DFFT_DECL_XC_PLAN
-
 // entry point of length N: defined (and explicitly instantiated) in the translation unit of N's group only
 template <bool ON, int N> struct XcInst {};
 template <int N> struct XcInst<true, N> {
@@ -44,40 +33,6 @@ template <int N> struct XcInst<true, N> {
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
-
-// Geometry: full-line tiles (the C2C column kernel's cols_per_tile: 8 elements of 16 bytes for every fused length -- the 1024-point tile
-// is 128 KiB of the CU's 160 KiB LDS), at most 512 threads per workgroup so that a thread may use 256 registers: it keeps its E points
-// live across two transforms while up to E filter elements are in flight.
-template <class V, class P> struct XcGeom {
-    static constexpr int CB = cols_per_tile<V, P>();
-    static_assert(CB * (int)sizeof(V) == 128 && CB * P::T <= 512, "fused conv lengths use full-line tiles of at most 512 threads");
-    static constexpr int G = ConstMax1<256 / (CB * P::T)>::value;
-    using KG = KernelGeom<V, P, CB, G, TuneDefault>;
-    static_assert(KG::PH == 1, "single-phase tiles only");
-};
-
-// filter element as it lies in memory, per data type V and filter kind
-template <class V, bool REAL> struct XcFilter;
-template <> struct XcFilter<double2, false> {
-    using T = double2;
-    static __device__ __forceinline__ double2 mul(double2 a, T h) { return double2{a.x * h.x - a.y * h.y, a.x * h.y + a.y * h.x}; }
-};
-template <> struct XcFilter<double2, true> {
-    using T = double;
-    static __device__ __forceinline__ double2 mul(double2 a, T h) { return double2{a.x * h, a.y * h}; }
-};
-template <> struct XcFilter<cpair, false> {
-    using T = f32x4;  // (re0, im0, re1, im1) of two adjacent columns
-    static __device__ __forceinline__ cpair mul(cpair a, T g) {
-        const cpair h = VecTraits<cpair>::from_g(g);
-        return cpair{a.x * h.x - a.y * h.y, a.x * h.y + a.y * h.x};
-    }
-};
-template <> struct XcFilter<cpair, true> {
-    using T = f32x2;  // the two columns' reals
-    static __device__ __forceinline__ cpair mul(cpair a, T h) { return cpair{a.x * h, a.y * h}; }
-};
-template <class V> __device__ __forceinline__ V xc_conj(V a) { return V{a.x, -a.y}; }
 
 // One launch per X stage.  Thread group g of a workgroup owns tile r0 + g = (row r, column block b): columns [b CB, b CB + CB) of row r
 // in every plane x.  All strides in units of one V (fp32: pairs of columns).  in == out is the normal case: a tile reads all its points
@@ -95,12 +50,7 @@ xconv_cols_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* 
     using F = XcFilter<V, REAL>;
     constexpr int  E = P::E, T = P::T, G = XG::G, GT = KG::GT, CB = XG::CB;
     constexpr bool TWPOW = KG::TWMODE == TW_REG;
-    // The filter loads are issued right behind the data loads wherever data and filter fit the thread's registers together: always in
-    // workgroups of at most 256 threads (one wave per SIMD may use 512 registers: 384 points, 96 + 96), and in 512-thread workgroups (256
-    // registers) up to 12 points.  16 points of 16 bytes with a complex filter (1024 points: 64 + 64 registers, next to 16 offsets and the
-    // butterflies' temporaries) do not fit -- that form kept 92-124 bytes per lane in scratch -- and read the filter between the two
-    // transforms instead.
-    constexpr bool EARLY = REAL || E * (int)sizeof(V) / 4 < 64 || KG::THREADS <= 256;
+    constexpr bool EARLY = conv_filter_early<V, P, REAL>();
     extern __shared__ __attribute__((aligned(16))) char dfft_smem[];
     const int g = threadIdx.x / GT;
     const int tid = (int)threadIdx.x - g * GT;
@@ -108,16 +58,7 @@ xconv_cols_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* 
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * KG::LDS_ELEMS;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = twreg;
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        twr = tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<W, P, 0, +1, KG::NW>(reinterpret_cast<W*>(dfft_smem), tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        twr = reinterpret_cast<W*>(dfft_smem);
-    } else {
-        load_twiddles<W, P, 0, +1, true>(twreg, tw, j);
-    }
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     // rotated rows: point k of this thread lies in plane j + T k, whose rows are rotated by rot * (j + T k) mod the row length
     const int rot_j = ROT ? (rot * j) & mask : 0, rot_t = ROT ? (rot * T) & mask : 0;
     const RT  sc = (RT)scale;
@@ -162,55 +103,37 @@ xconv_cols_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* 
         // (A . H) conjugated: the inverse transform is conj(FFT(conj(A . H))); 1 / N is in H
 #pragma unroll
         for (int k = 0; k < E; ++k) {
-            if constexpr (EARLY) v[k] = xc_conj(F::mul(v[k], h[k]));
-            else v[k] = valid ? xc_conj(F::mul(v[k], filt[base + off[k]])) : VT::zero();
+            if constexpr (EARLY) v[k] = cconj(F::mul(v[k], h[k]));
+            else v[k] = valid ? cconj(F::mul(v[k], filt[base + off[k]])) : VT::zero();
         }
         group_sync<KG::WAVE_LOCAL>();  // the second transform's exchanges reuse the tile
         run_stages<V, P, 0, +1, CB, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, KG::PH, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, c);
         if (valid) {
 #pragma unroll
-            for (int k = 0; k < E; ++k) out[base + off[k]] = VT::to_g(xc_conj(v[k]));
+            for (int k = 0; k < E; ++k) out[base + off[k]] = VT::to_g(cconj(v[k]));
         }
         group_sync<KG::WAVE_LOCAL>();  // the next tile's exchanges reuse the tile
     }
-}
-
-// persistent grid: resident workgroups per CU (occupancy query, once per kernel and device) times the CUs
-template <class KG> int xc_blocks_per_cu(const void* kern, std::atomic<int>* cache) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    int occ = cache[dev].load(std::memory_order_acquire);
-    if (occ > 0) return occ;
-    if (KG::LDS_BYTES > 64 * 1024 &&
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KG::LDS_BYTES) != hipSuccess)
-        return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, KG::THREADS, KG::LDS_BYTES) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-        occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, KG::LDS_BYTES));
-    }
-    cache[dev].store(occ, std::memory_order_release);
-    return occ;
 }
 
 template <class V, class P, bool REAL, bool ROT> hipError_t launch_xconv(const ConvLaunch& L, hipStream_t stream) {
     using XG = XcGeom<V, P>;
     using KG = typename XG::KG;
     using VT = VecTraits<V>;
-    constexpr int           LANES = VT::LANES, CB = XG::CB, G = XG::G;
-    static std::atomic<int> occ_cache[64];
-    const long long         ncols = L.ncols / LANES, plane = L.plane / LANES, pitch = L.pitch / LANES;
-    const long long         per_row = (ncols + CB - 1) / CB, tiles = L.rows * per_row;
-    // 32-bit offsets inside a row's columns, 32-bit tile counts: the largest element offset is below (n0 - 1) * plane + pitch
-    if (tiles < 1 || tiles >= (1ll << 31) || (long long)L.n0 * plane + pitch >= (1ll << 32)) return hipErrorInvalidValue;
-    if (ROT != (L.rot > 0) || (ROT && ((ncols & (ncols - 1)) != 0 || L.rot % LANES != 0))) return hipErrorInvalidValue;
+    constexpr int           LANES = VT::LANES;
+    static std::atomic<int> occ_cache[kMaxDevices];
+    const ConvTiles<V, P>   t(L);
+    if (!t.fits32(L)) return hipErrorInvalidValue;
+    if (ROT != (L.rot > 0) || (ROT && ((t.ncols & (t.ncols - 1)) != 0 || L.rot % LANES != 0))) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    auto      kern = xconv_cols_kernel<V, P, REAL, ROT>;
-    const int occ = xc_blocks_per_cu<KG>(reinterpret_cast<const void*>(kern), occ_cache);
-    if (occ < 0) return hipErrorInvalidDevice;
-    const long long grid = std::min<long long>((long long)device_info().cus * occ, (tiles + G - 1) / G);
+    auto       kern = xconv_cols_kernel<V, P, REAL, ROT>;
+    hipError_t e;
+    const int  occ = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), KG::THREADS, KG::LDS_BYTES, occ_cache, &e);
+    if (occ == 0) return e;
+    const long long grid = persistent_grid(device_info().cus, occ, (t.tiles + XG::G - 1) / XG::G);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const typename VT::G*)L.in, (typename VT::G*)L.out,
-                       (const typename XcFilter<V, REAL>::T*)L.filt, (const typename VT::W*)L.tw, (unsigned)plane, pitch, (unsigned)tiles,
-                       (unsigned)per_row, (int)ncols, L.rot / LANES, (int)ncols - 1, L.forward_only, L.scale);
+                       (const typename XcFilter<V, REAL>::T*)L.filt, (const typename VT::W*)L.tw, (unsigned)t.plane, t.pitch, (unsigned)t.tiles,
+                       (unsigned)t.per_row, (int)t.ncols, L.rot / LANES, (int)t.ncols - 1, L.forward_only, L.scale);
     return hipGetLastError();
 }
 
@@ -220,8 +143,8 @@ template <class V, class P> hipError_t launch_xconv_vp(const ConvLaunch& L, hipS
 }
 
 template <int N> hipError_t XcInst<true, N>::run(const ConvLaunch& L, hipStream_t stream) {
-    if (L.dtype == F64) return launch_xconv_vp<double2, typename XcPlanFor<N>::type>(L, stream);
-    if (L.dtype == F32) return launch_xconv_vp<cpair, typename XcPlanFor<N>::type>(L, stream);
+    if (L.dtype == F64) return launch_xconv_vp<double2, typename PlanFor<N>::type>(L, stream);
+    if (L.dtype == F32) return launch_xconv_vp<cpair, typename PlanFor<N>::type>(L, stream);
     return hipErrorInvalidValue;
 }
 #define DFFT_XC_INST(N, GRP, E, ...) template struct XcInst<(GRP == DFFT_INST_GROUP && conv_fused_n(N)), N>;
@@ -265,8 +188,6 @@ __global__ void __launch_bounds__(256) xconv_relayout_kernel(const S* __restrict
         for (int i = 0; i < COMPS; ++i) dst[o * COMPS + i] = (S)((double)h[e * COMPS + i] * scale);
     }
 }
-
-unsigned xc_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
 
 template <int N> hipError_t xc_run(const ConvLaunch& L, hipStream_t stream) {
     if constexpr (conv_fused_n(N)) return XcInst<true, N>::run(L, stream);

@@ -21,11 +21,10 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the factor multiply).
-#define DFFT_CONV_MULTI_DEVICE 1
+#include "dfft_conv_impl.h"
 #include "dfft_conv_multi.h"
 #include "dfft_internal.h"
 
-#include <algorithm>
 #include <atomic>
 
 #ifndef DFFT_INST_GROUP
@@ -43,26 +42,25 @@ template <int N> struct XmInst<true, N> {
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
 
 // B is parked in slab 0 instead of registers: 64 registers of points per thread in workgroups of more than 256 threads
-template <class V, class P> constexpr bool xm_park() { return P::E * (int)sizeof(V) / 4 >= 64 && XmGeom<V, P>::KG::THREADS > 256; }
+template <class V, class P> constexpr bool xm_park() { return P::E * (int)sizeof(V) / 4 >= 64 && XcGeom<V, P>::KG::THREADS > 256; }
 
 // One launch per X stage.  Thread group g of a workgroup owns tile r0 + g = (row r, column block b): columns [b CB, b CB + CB) of row r in
 // every plane x.  All strides in units of one V (fp32: pairs of columns).
 template <class V, class P, bool REAL>
-__global__ void __attribute__((amdgpu_flat_work_group_size(1, XmGeom<V, P>::KG::THREADS)))
-xconv_multi_cols_kernel(const typename VecTraits<V>::G* in, const typename XmFilter<V, REAL>::T* __restrict__ filt,
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, XcGeom<V, P>::KG::THREADS)))
+xconv_multi_cols_kernel(const typename VecTraits<V>::G* in, const typename XcFilter<V, REAL>::T* __restrict__ filt,
                         const typename VecTraits<V>::W* __restrict__ tw, ConvMultiArgs M, int K, unsigned plane, long long pitch, unsigned tiles,
                         unsigned tiles_per_row, int ncols) {
-    using XG = XmGeom<V, P>;
+    using XG = XcGeom<V, P>;
     using KG = typename XG::KG;
     using VT = VecTraits<V>;
     using GV = typename VT::G;
     using W = typename VT::W;
-    using F = XmFilter<V, REAL>;
+    using F = XcFilter<V, REAL>;
     constexpr int  E = P::E, T = P::T, G = XG::G, GT = KG::GT, CB = XG::CB;
     constexpr bool TWPOW = KG::TWMODE == TW_REG;
     constexpr bool PARK = xm_park<V, P>();
-    // the filter loads fly under the forward stages wherever data and filter fit the registers together (xconv_cols_kernel's rule)
-    constexpr bool EARLY = REAL || E * (int)sizeof(V) / 4 < 64 || KG::THREADS <= 256;
+    constexpr bool EARLY = conv_filter_early<V, P, REAL>();
     extern __shared__ __attribute__((aligned(16))) char dfft_smem[];
     const int g = threadIdx.x / GT;
     const int tid = (int)threadIdx.x - g * GT;
@@ -70,16 +68,7 @@ xconv_multi_cols_kernel(const typename VecTraits<V>::G* in, const typename XmFil
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * KG::LDS_ELEMS;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = twreg;
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        twr = tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<W, P, 0, +1, KG::NW>(reinterpret_cast<W*>(dfft_smem), tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        twr = reinterpret_cast<W*>(dfft_smem);
-    } else {
-        load_twiddles<W, P, 0, +1, true>(twreg, tw, j);
-    }
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     GV* const out0 = (GV*)M.out[0];
     for (unsigned r0 = blockIdx.x * G; r0 < tiles; r0 += gridDim.x * G) {
         const unsigned t = r0 + g;
@@ -146,7 +135,7 @@ xconv_multi_cols_kernel(const typename VecTraits<V>::G* in, const typename XmFil
 #pragma unroll
             for (int k = 0; k < E; ++k) {
                 const V b = PARK ? v[k] : B[PARK ? 0 : k];
-                v[k] = xm_conj(cmul(b, cmul(s, a[j + T * k])));
+                v[k] = cconj(cmul(b, cmul(s, a[j + T * k])));
                 if constexpr (PARK) {  // the factor reads four at a time, like the late filter reads
                     if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
                 }
@@ -156,58 +145,39 @@ xconv_multi_cols_kernel(const typename VecTraits<V>::G* in, const typename XmFil
             if (valid) {
                 GV* const dst = (GV*)M.out[o];
 #pragma unroll
-                for (int k = 0; k < E; ++k) dst[base + off[k]] = VT::to_g(xm_conj(v[k]));
+                for (int k = 0; k < E; ++k) dst[base + off[k]] = VT::to_g(cconj(v[k]));
             }
         }
         group_sync<KG::WAVE_LOCAL>();  // the next tile's exchanges reuse the tile
     }
 }
 
-// persistent grid: resident workgroups per CU (occupancy query, once per kernel and device) times the CUs
-template <class KG> int xm_blocks_per_cu(const void* kern, std::atomic<int>* cache) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    int occ = cache[dev].load(std::memory_order_acquire);
-    if (occ > 0) return occ;
-    if (KG::LDS_BYTES > 64 * 1024 &&
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KG::LDS_BYTES) != hipSuccess)
-        return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, KG::THREADS, KG::LDS_BYTES) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-        occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, KG::LDS_BYTES));
-    }
-    cache[dev].store(occ, std::memory_order_release);
-    return occ;
-}
-
 template <class V, class P, bool REAL> hipError_t launch_xmulti(const ConvLaunch& L, const ConvMultiArgs& M, int K, hipStream_t stream) {
-    using XG = XmGeom<V, P>;
+    using XG = XcGeom<V, P>;
     using KG = typename XG::KG;
     using VT = VecTraits<V>;
-    constexpr int           LANES = VT::LANES, CB = XG::CB, G = XG::G;
-    static std::atomic<int> occ_cache[64];
-    const long long         ncols = L.ncols / LANES, plane = L.plane / LANES, pitch = L.pitch / LANES;
-    const long long         per_row = (ncols + CB - 1) / CB, tiles = L.rows * per_row;
-    // 32-bit offsets inside a row's columns, 32-bit tile counts: the largest element offset is below (n0 - 1) * plane + pitch
-    if (tiles < 1 || tiles >= (1ll << 31) || (long long)L.n0 * plane + pitch >= (1ll << 32)) return hipErrorInvalidValue;
+    static std::atomic<int> occ_cache[kMaxDevices];
+    const ConvTiles<V, P>   t(L);
+    if (!t.fits32(L)) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    auto      kern = xconv_multi_cols_kernel<V, P, REAL>;
-    const int occ = xm_blocks_per_cu<KG>(reinterpret_cast<const void*>(kern), occ_cache);
-    if (occ < 0) return hipErrorInvalidDevice;
-    const long long grid = std::min<long long>((long long)device_info().cus * occ, (tiles + G - 1) / G);
+    auto       kern = xconv_multi_cols_kernel<V, P, REAL>;
+    hipError_t e;
+    const int  occ = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), KG::THREADS, KG::LDS_BYTES, occ_cache, &e);
+    if (occ == 0) return e;
+    const long long grid = persistent_grid(device_info().cus, occ, (t.tiles + XG::G - 1) / XG::G);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const typename VT::G*)L.in,
-                       (const typename XmFilter<V, REAL>::T*)L.filt, (const typename VT::W*)L.tw, M, K, (unsigned)plane, pitch, (unsigned)tiles,
-                       (unsigned)per_row, (int)ncols);
+                       (const typename XcFilter<V, REAL>::T*)L.filt, (const typename VT::W*)L.tw, M, K, (unsigned)t.plane, t.pitch, (unsigned)t.tiles,
+                       (unsigned)t.per_row, (int)t.ncols);
     return hipGetLastError();
 }
 
 template <int N> hipError_t XmInst<true, N>::run(const ConvLaunch& L, const ConvMultiArgs& M, int K, hipStream_t stream) {
-    using P = typename XmPlanFor<N>::type;
+    using P = typename PlanFor<N>::type;
     if (L.dtype == F64) return L.filter_real ? launch_xmulti<double2, P, true>(L, M, K, stream) : launch_xmulti<double2, P, false>(L, M, K, stream);
     if (L.dtype == F32) return L.filter_real ? launch_xmulti<cpair, P, true>(L, M, K, stream) : launch_xmulti<cpair, P, false>(L, M, K, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_XM_INST(N, GRP, E, ...) template struct XmInst<(GRP == DFFT_INST_GROUP && xm_fused_n(N)), N>;
+#define DFFT_XM_INST(N, GRP, E, ...) template struct XmInst<(GRP == DFFT_INST_GROUP && conv_fused_n(N)), N>;
 DFFT_PLAN_TABLE(DFFT_XM_INST)
 #undef DFFT_XM_INST
 
@@ -240,7 +210,7 @@ __global__ void __launch_bounds__(256) xconv_factor_mul_kernel(const D* src, D* 
 }
 
 template <int N> hipError_t xm_run(const ConvLaunch& L, const ConvMultiArgs& M, int K, hipStream_t stream) {
-    if constexpr (xm_fused_n(N)) return XmInst<true, N>::run(L, M, K, stream);
+    if constexpr (conv_fused_n(N)) return XmInst<true, N>::run(L, M, K, stream);
     else return hipErrorInvalidValue;
 }
 
@@ -271,15 +241,13 @@ hipError_t launch_conv_factor_mul(const ConvLaunch& L, const void* src, void* ds
     if (!src || !dst || !ax || !by || !cz || L.rot != 0 || L.ncols > L.pitch || L.plane != L.rows * L.pitch) return hipErrorInvalidValue;
     (void)hipGetLastError();
     if (L.dtype == F64) {
-        const unsigned grid = (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16));
-        hipLaunchKernelGGL((xconv_factor_mul_kernel<double2, double2, 1>), dim3(grid), dim3(256), 0, stream, (const double2*)src, (double2*)dst,
+        hipLaunchKernelGGL((xconv_factor_mul_kernel<double2, double2, 1>), dim3(xc_grid(total)), dim3(256), 0, stream, (const double2*)src, (double2*)dst,
                            (const double2*)ax, (const double2*)by, (const double2*)cz, L.plane, L.pitch, L.ncols, total);
         return hipGetLastError();
     }
     if (L.dtype != F32 || ((L.ncols | L.pitch) & 1)) return hipErrorInvalidValue;  // pairs of elements: even rows
     const long long n16 = total / 2;
-    const unsigned  grid = (unsigned)std::max(1ll, std::min((n16 + 255) / 256, (long long)device_info().cus * 16));
-    hipLaunchKernelGGL((xconv_factor_mul_kernel<f32x4, float2, 2>), dim3(grid), dim3(256), 0, stream, (const f32x4*)src, (f32x4*)dst,
+    hipLaunchKernelGGL((xconv_factor_mul_kernel<f32x4, float2, 2>), dim3(xc_grid(n16)), dim3(256), 0, stream, (const f32x4*)src, (f32x4*)dst,
                        (const float2*)ax, (const float2*)by, (const float2*)cz, L.plane, L.pitch, L.ncols, n16);
     return hipGetLastError();
 }

@@ -536,6 +536,25 @@ template <class V, class P, int CB, int G, class Tune> struct KernelGeom {
     static constexpr size_t LDS_BYTES = (size_t)LDS_ELEMS * G * sizeof(V) + TW_BYTES;
 };
 
+// The twiddle prologue of every tile kernel: where KernelGeom puts the twiddles of the P-point stages (TWMODE), fetched once per thread
+// (TW_REG, into twreg) or once per workgroup (TW_LDS, into ldstw, the front of the dynamic LDS) before the tile loop.  Returns what
+// run_stages takes as twr.  TWPOW: the kernel's Tune::TWPOW (what KG::TWN was sized with).
+template <class V, class P, int DIR, class KG, bool TWPOW = true>
+__device__ __forceinline__ const typename VecTraits<V>::W* stage_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
+                                                                         const typename VecTraits<V>::W* __restrict__ tw, int j) {
+    using W = typename VecTraits<V>::W;
+    if constexpr (KG::TWMODE == TW_GLOBAL) {
+        return tw;
+    } else if constexpr (KG::TWMODE == TW_LDS) {
+        fill_stage_major<W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
+        __syncthreads();
+        return ldstw;
+    } else {
+        load_twiddles<W, P, 0, DIR, TWPOW>(twreg, tw, j);
+        return twreg;
+    }
+}
+
 template <class V> struct native_vec;
 template <> struct native_vec<double2> { typedef double type __attribute__((ext_vector_type(2))); };
 template <> struct native_vec<float2> { typedef float type __attribute__((ext_vector_type(2))); };
@@ -629,16 +648,7 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
 
     constexpr int TWN = KG::TWMODE == TW_REG ? KG::TWN : 0;
     W twreg[TWN > 0 ? TWN : 1];
-    const W* twr = twreg;
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        twr = tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        twr = ldstw;
-    } else {
-        load_twiddles<W, P, 0, DIR, Tune::TWPOW>(twreg, tw, j);
-    }
+    const W* twr = stage_twiddles<V, P, DIR, KG, Tune::TWPOW>(twreg, ldstw, tw, j);
     constexpr bool TWPOW = Tune::TWPOW && KG::TWMODE == TW_REG;
 
     // Per-thread element offsets of its E points relative to the tile base (constant over tiles).
@@ -1242,6 +1252,8 @@ fft_tload_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>
     const int tid = threadIdx.x, c = tid % CB, j = tile_j<CB, KG::NW>(tid);
     constexpr int TWN = KG::TWMODE == TW_REG ? KG::TWN : 0;
     W        twreg[TWN > 0 ? TWN : 1];
+    // (stage_twiddles written out: through the helper the two 1024-point column-pair instantiations come out with another branch form
+    // around the table fill and a different schedule behind it)
     const W* twr = twreg;
     if constexpr (KG::TWMODE == TW_GLOBAL) {
         twr = tw;
@@ -1342,47 +1354,66 @@ inline hipError_t launch_debug(hipError_t e, const char* what, int lds, int thre
     return e;
 }
 
+// ---- The launch set-up of every persistent kernel of the library ----
+constexpr int kMaxDevices = 64;  // devices one process may launch on: the length of every per-kernel cache below
+
+// Resident workgroups per CU of `kern` on the current device, set up once per kernel and device.  `cache` is the launcher's
+// function-local static, one array per kernel (0 = not set up on that device yet).  The first use on a device opts the kernel in to more
+// than 64 KiB of dynamic LDS (function attributes are per device context; at or below 64 KiB there is nothing to opt in to) and asks the
+// runtime for the occupancy.  Several device threads may launch the same instantiation at once: published with release / read with
+// acquire, set up under one lock with a second look.  Returns 0 with *err set when the device or the opt-in fails; a failed occupancy
+// query is advisory only (a grid-stride loop is correct for any grid) and falls back to the tighter of the wave-slot and LDS bounds.
+// query = false: the opt-in alone (launchers that run one workgroup per CU whatever the occupancy); the answer is then 1.
+inline int resident_blocks_per_cu(const void* kern, int threads, size_t lds_bytes, std::atomic<int> (&cache)[kMaxDevices], hipError_t* err,
+                                  bool query = true) {
+    static std::mutex setup_mutex;
+    int dev = 0;
+    *err = hipGetDevice(&dev);
+    if (*err == hipSuccess && (dev < 0 || dev >= kMaxDevices)) *err = hipErrorInvalidDevice;
+    if (*err != hipSuccess) return 0;
+    int occ = cache[dev].load(std::memory_order_acquire);
+    if (occ > 0) return occ;
+    std::lock_guard<std::mutex> lk(setup_mutex);
+    occ = cache[dev].load(std::memory_order_relaxed);
+    if (occ > 0) return occ;
+    if (lds_bytes > 64 * 1024) {
+        *err = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (*err != hipSuccess) return (void)launch_debug(*err, "hipFuncSetAttribute", (int)lds_bytes, threads), 0;
+    }
+    occ = 1;
+    if (query) {
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds_bytes);
+        if (e != hipSuccess) {
+            (void)launch_debug(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor", (int)lds_bytes, threads);
+            (void)hipGetLastError();
+            occ = 32 / ((threads + 63) / 64);
+            if (lds_bytes > 0 && (int)(160 * 1024 / lds_bytes) < occ) occ = (int)(160 * 1024 / lds_bytes);
+        }
+    }
+    if (occ < 1) occ = 1;
+    cache[dev].store(occ, std::memory_order_release);
+    return occ;
+}
+
+// Grid of a persistent kernel: resident workgroups of the whole device, at most one per unit of work (a workgroup's share of the tiles);
+// grid_limit / blocks_per_cu_limit > 0 cap it further (FftLaunch).
+inline long long persistent_grid(int cus, int blocks_per_cu, long long units, long long grid_limit = 0, int blocks_per_cu_limit = 0) {
+    if (blocks_per_cu_limit > 0 && blocks_per_cu_limit < blocks_per_cu) blocks_per_cu = blocks_per_cu_limit;
+    long long grid = (long long)cus * blocks_per_cu;
+    if (grid_limit > 0 && grid > grid_limit) grid = grid_limit;
+    return grid < units ? grid : units;
+}
+
 template <class V, class P, int CB, int G, int DIR, bool GENERAL, class Tune = TuneDefault>
 hipError_t launch_variant(const FftLaunch& L, hipStream_t stream, int* blocks_per_cu_out = nullptr) {
     using KG = KernelGeom<V, P, CB, G, Tune>;
     auto kern = fft_tiles_kernel<V, P, CB, G, DIR, GENERAL, Tune>;
-    // Per-device one-time set-up (function attributes are per device context): LDS opt-in and resident blocks per CU.
-    // (several device threads may launch the same instantiation at once: published with release / read with acquire, set up
-    // under a lock)
-    static std::atomic<int> blocks_per_cu[64];
-    static std::mutex       setup_mutex;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        if (blocks_per_cu[dev].load(std::memory_order_relaxed) == 0) {
-        if (KG::LDS_BYTES > 64 * 1024) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)KG::LDS_BYTES);
-            if (e != hipSuccess) return launch_debug(e, "hipFuncSetAttribute", (int)KG::LDS_BYTES, KG::THREADS);
-        }
-        int occ = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, KG::THREADS, KG::LDS_BYTES);
-        if (e != hipSuccess) {
-            // advisory only (the grid-stride loop is correct for any grid): fall back to the LDS / wave-slot bound
-            (void)launch_debug(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor", (int)KG::LDS_BYTES, KG::THREADS);
-            (void)hipGetLastError();
-            const int waves = (KG::THREADS + 63) / 64;
-            occ = 32 / waves;
-            if (KG::LDS_BYTES > 0 && (int)(160 * 1024 / KG::LDS_BYTES) < occ) occ = (int)(160 * 1024 / KG::LDS_BYTES);
-        }
-        blocks_per_cu[dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-        }
-    }
-    if (blocks_per_cu_out) *blocks_per_cu_out = blocks_per_cu[dev].load(std::memory_order_relaxed);
-    const long long nblocks_needed = (L.ntiles + G - 1) / G;
-    int bpc = blocks_per_cu[dev].load(std::memory_order_relaxed);
-    if (L.blocks_per_cu_limit > 0 && L.blocks_per_cu_limit < bpc) bpc = L.blocks_per_cu_limit;
-    long long grid = (long long)device_info().cus * bpc;
-    if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
-    if (grid > nblocks_needed) grid = nblocks_needed;
+    static std::atomic<int> blocks_per_cu[kMaxDevices];
+    hipError_t e;
+    const int  bpc = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), KG::THREADS, KG::LDS_BYTES, blocks_per_cu, &e);
+    if (bpc == 0) return e;
+    if (blocks_per_cu_out) *blocks_per_cu_out = bpc;
+    const long long grid = persistent_grid(device_info().cus, bpc, (L.ntiles + G - 1) / G, L.grid_limit, L.blocks_per_cu_limit);
     if (grid < 1) return hipSuccess;
     (void)hipGetLastError();  // drop any stale error of this thread (other libraries share the runtime)
     using GV = typename VecTraits<V>::G;
@@ -1400,24 +1431,14 @@ template <class V, class P, int CB, int DIR, bool NT, bool ROT = false> hipError
     using GV = typename VT::G;
     constexpr size_t LDS_BYTES = DualGeom<V, P, CB>::LDS_BYTES;
     auto kern = fft_dual_tiles_kernel<V, P, CB, DIR, NT, ROT>;
-    static std::atomic<bool> attr_set[64];
-    static std::mutex        setup_mutex;
-    int         dev = 0;
-    hipError_t  e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return launch_debug(e, "hipFuncSetAttribute", (int)LDS_BYTES, CB * P::T);
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    // one workgroup per CU whatever the occupancy (a tile pair and its table fill the LDS): the opt-in half of the set-up only
+    static std::atomic<int> attr_set[kMaxDevices];
+    hipError_t e;
+    if (resident_blocks_per_cu(reinterpret_cast<const void*>(kern), CB * P::T, LDS_BYTES, attr_set, &e, false) == 0) return e;
     const long long tiles_per_a = L.ncols / (2 * CB), ntiles = L.na * tiles_per_a;
     if (ntiles <= 0) return hipSuccess;
     if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    long long grid = (long long)device_info().cus;
-    if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
-    if (grid > ntiles) grid = ntiles;
+    const long long grid = persistent_grid(device_info().cus, 1, ntiles, L.grid_limit);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CB * P::T), LDS_BYTES, stream, (const GV*)L.in, (GV*)L.out, (const W*)L.tw, L.imap,
                        L.omap, L.itile, L.otile, (unsigned)ntiles, (unsigned)tiles_per_a, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);
@@ -1432,29 +1453,15 @@ template <class V, class PH, int CB, int DIR, bool NTL, bool NTS, bool BIN, bool
     using GV = typename VT::G;
     constexpr size_t LDS_BYTES = Dif2Geom<V, PH, CB, TOUT>::LDS_BYTES;
     auto kern = fft_dif2_tiles_kernel<V, PH, CB, DIR, NTL, NTS, BIN, BOUT, ROT, TOUT>;
-    static std::atomic<int> blocks_per_cu[64];  // 0 = not set up on that device yet
-    static std::mutex       setup_mutex;
-    int         dev = 0;
-    hipError_t  e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return launch_debug(e, "hipFuncSetAttribute", (int)LDS_BYTES, CB * PH::T);
-        int occ = 0;  // a half tile of 64 KiB (1024 points) leaves room for a second workgroup when the registers allow it
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, CB * PH::T, LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks_per_cu[dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-    }
+    // (a half tile of 64 KiB -- 1024 points -- leaves room for a second workgroup when the registers allow it)
+    static std::atomic<int> blocks_per_cu[kMaxDevices];
+    hipError_t e;
+    const int  bpc = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), CB * PH::T, LDS_BYTES, blocks_per_cu, &e);
+    if (bpc == 0) return e;
     const long long tiles_per_a = L.ncols / CB, ntiles = L.na * tiles_per_a;
     if (ntiles <= 0) return hipSuccess;
     if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    long long grid = (long long)device_info().cus * blocks_per_cu[dev].load(std::memory_order_relaxed);
-    if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
-    if (grid > ntiles) grid = ntiles;
+    const long long grid = persistent_grid(device_info().cus, bpc, ntiles, L.grid_limit);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CB * PH::T), LDS_BYTES, stream, (const GV*)L.in, (GV*)L.out, (const W*)L.tw, L.imap,
                        L.omap, L.itile, L.otile, (unsigned)ntiles, (unsigned)tiles_per_a, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);
@@ -1470,29 +1477,14 @@ template <class V, class P, int CB, int DIR, bool ROT> hipError_t launch_tload(c
     using KG = KernelGeom<V, P, CB, 1, TuneTransposedLoad>;
     constexpr size_t LDS_BYTES = KG::LDS_BYTES;
     auto kern = fft_tload_tiles_kernel<V, P, CB, DIR, ROT>;
-    static std::atomic<int> blocks_per_cu[64];  // 0 = not set up on that device yet
-    static std::mutex       setup_mutex;
-    int         dev = 0;
-    hipError_t  e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return launch_debug(e, "hipFuncSetAttribute", (int)LDS_BYTES, CB * P::T);
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, CB * P::T, LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks_per_cu[dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-    }
+    static std::atomic<int> blocks_per_cu[kMaxDevices];
+    hipError_t e;
+    const int  bpc = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), CB * P::T, LDS_BYTES, blocks_per_cu, &e);
+    if (bpc == 0) return e;
     const long long tiles_per_a = L.ncols / CB, ntiles = L.na * tiles_per_a;
     if (ntiles <= 0) return hipSuccess;
     if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    long long grid = (long long)device_info().cus * blocks_per_cu[dev].load(std::memory_order_relaxed);
-    if (L.grid_limit > 0 && grid > L.grid_limit) grid = L.grid_limit;
-    if (grid > ntiles) grid = ntiles;
+    const long long grid = persistent_grid(device_info().cus, bpc, ntiles, L.grid_limit);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CB * P::T), LDS_BYTES, stream, (const GV*)L.in, (GV*)L.out, (const W*)L.tw, L.imap,
                        L.omap, L.itile, L.otile, (unsigned)ntiles, (unsigned)tiles_per_a, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);

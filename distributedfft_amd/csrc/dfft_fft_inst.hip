@@ -9,11 +9,6 @@
 
 namespace dfft {
 
-template <int N> struct PlanFor;
-#define DFFT_DECL_PLAN(N, GRP, E, ...) \
-    template <> struct PlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; static constexpr int group = GRP; };
-DFFT_PLAN_TABLE(DFFT_DECL_PLAN)
-#undef DFFT_DECL_PLAN
 
 // fp32 uses the table's plan unless a length is listed here (measured: 16 points/thread helps 1024-point fp64 columns,
 // 3.4 -> 4.4 TB/s, but costs fp32 -- 16-column tiles then need 1024-thread blocks: 1024^3 fp32 7.4 -> 12.4 ms in t0).

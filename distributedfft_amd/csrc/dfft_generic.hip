@@ -13,10 +13,8 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
-#include "dfft_butterfly.h"
-#include "dfft_kernels.h"
+#include "dfft_fft_impl.h"
 
 namespace dfft {
 
@@ -166,29 +164,14 @@ template <class V> hipError_t launch_generic_t(const FftLaunch& Lin, hipStream_t
     if (L.ntiles <= 0) return hipSuccess;
     if (L.ntiles >= (1ll << 31)) return hipErrorInvalidValue;
     auto kern = L.dir > 0 ? fft_generic_kernel<V, +1> : fft_generic_kernel<V, -1>;
-    static std::atomic<bool> attr_set[2][64];
-    static std::mutex        setup_mutex;
-    int         dev = 0;
-    hipError_t  e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[L.dir > 0][dev].load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[L.dir > 0][dev].store(true, std::memory_order_release);
-    }
-    static thread_local int cached_dev = -1, cus = 256;
-    if (cached_dev != dev) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        cached_dev = dev;
-    }
+    // the tile size is a run-time value: the opt-in half of the set-up alone, for the whole LDS, and the bound below instead of a query
+    static std::atomic<int> attr_set[2][kMaxDevices];
+    hipError_t e;
+    if (resident_blocks_per_cu(reinterpret_cast<const void*>(kern), 1024, 160 * 1024, attr_set[L.dir > 0], &e, false) == 0) return e;
     int bpc = (int)((size_t)160 * 1024 / lds);
     if (bpc > 8) bpc = 8;
     if (bpc < 1) bpc = 1;
-    long long grid = (long long)cus * bpc;
-    if (grid > L.ntiles) grid = L.ntiles;
+    const long long grid = persistent_grid(device_info().cus, bpc, L.ntiles);
     (void)hipGetLastError();
     // about four tile elements per thread (measured: 256 threads best for 1280-element tiles, 512 for 2560, 1024 from 4000)
     int threads = ((N * cb / 4 + 63) / 64) * 64;

@@ -68,3 +68,13 @@
     X(2401, 11, 7, 7, 7, 7, 7)
 
 #define DFFT_NUM_INST_GROUPS 12
+
+// The plan of a tuned length as a type, and the group that instantiates it (one table for every unit; Plan: dfft_fft_impl.h)
+namespace dfft {
+template <int N_, int E_, int... Rs> struct Plan;
+template <int N> struct PlanFor;
+#define DFFT_DECL_PLAN(N, GRP, E, ...) \
+    template <> struct PlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; static constexpr int group = GRP; };
+DFFT_PLAN_TABLE(DFFT_DECL_PLAN)
+#undef DFFT_DECL_PLAN
+}  // namespace dfft

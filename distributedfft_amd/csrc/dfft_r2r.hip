@@ -72,12 +72,6 @@ struct R2rFusedLaunch {
     const void* wq;
 };
 
-template <int N> struct R2rPlanFor;
-#define DFFT_DECL_R2R_PLAN(N, GRP, E, ...) \
-    template <> struct R2rPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_R2R_PLAN)
-#undef DFFT_DECL_R2R_PLAN
-
 // Instantiations that would keep values in scratch memory at every tile width tried (tools/r2r_resources.py,
 // profiles/r15/kernel_resources.txt) are not built: their (n, dtype, type, form) runs the composed route.
 enum { R2R_FORM_COLS = 0, R2R_FORM_COLS_VEC = 1, R2R_FORM_ROWS = 2 };
@@ -140,22 +134,6 @@ template <class V, class P, bool THREE> struct R2rRowsGeom {
     static constexpr size_t LDS_BYTES = (size_t)EXR * G * sizeof(V) + KG::TW_BYTES;
 };
 
-// twiddles of the n-point stages, exactly as fft_tiles_kernel sets them up
-template <class V, class P, int DIR, class KG>
-__device__ __forceinline__ const typename VecTraits<V>::W* r2r_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
-                                                                       const typename VecTraits<V>::W* __restrict__ tw, int j) {
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        return tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<typename VecTraits<V>::W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        return ldstw;
-    } else {
-        load_twiddles<typename VecTraits<V>::W, P, 0, DIR, true>(twreg, tw, j);
-        return twreg;
-    }
-}
-
 // What a kernel needs besides the pointers (one by-value argument)
 struct R2rTileArgs {
     long long istep;        // reals from one tile owner (batch item / row pair) to the next
@@ -187,7 +165,7 @@ r2r2_kernel(const typename real_of<V>::type* in, typename real_of<V>::type* out,
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * GEO::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = r2r_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const long long sp = GEO::ROWS ? 1 : (A.s + 1) / 2;
     const bool      dst = A.dst != 0;
     for (unsigned r0 = blockIdx.x * G; r0 < A.tiles; r0 += gridDim.x * G) {
@@ -266,7 +244,7 @@ r2r3_kernel(const typename real_of<V>::type* in, typename real_of<V>::type* out,
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * GEO::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = r2r_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const long long sp = GEO::ROWS ? 1 : (A.s + 1) / 2;
     const bool      dst = A.dst != 0;
     for (unsigned r0 = blockIdx.x * G; r0 < A.tiles; r0 += gridDim.x * G) {
@@ -333,32 +311,14 @@ template <class V, class P, class GEO, bool VEC, bool THREE> hipError_t launch_r
     using W = typename VecTraits<V>::W;
     using RT = typename real_of<V>::type;
     constexpr int           N = P::N;
-    static std::atomic<int> blocks_per_cu[1][64];
-    static std::mutex       setup_mutex;
+    static std::atomic<int> blocks_per_cu[kMaxDevices];
     constexpr bool          three = THREE;
-    const int               d = 0;
     const void*             kern = nullptr;
     if constexpr (three) kern = reinterpret_cast<const void*>(r2r3_kernel<V, P, GEO, VEC>);
     else kern = reinterpret_cast<const void*>(r2r2_kernel<V, P, GEO, VEC>);
-    int                     dev = 0;
-    hipError_t              e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[d][dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        if (blocks_per_cu[d][dev].load(std::memory_order_relaxed) == 0) {
-            if (GEO::LDS_BYTES > 64 * 1024) {
-                e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEO::LDS_BYTES);
-                if (e != hipSuccess) return e;
-            }
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, GEO::KG::THREADS, GEO::LDS_BYTES) != hipSuccess) {
-                (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-                occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, GEO::LDS_BYTES));
-            }
-            blocks_per_cu[d][dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-        }
-    }
+    hipError_t              e;
+    const int               bpc = resident_blocks_per_cu(kern, GEO::KG::THREADS, GEO::LDS_BYTES, blocks_per_cu, &e);
+    if (bpc == 0) return e;
     // owners: batch items of [n][s] (columns), or pairs of rows (two rows of n reals each)
     const long long owners = GEO::ROWS ? (F.batch + 1) / 2 : F.batch;
     const long long per_b = GEO::ROWS ? 1 : ((F.s + 1) / 2 + GEO::CB - 1) / GEO::CB;
@@ -367,8 +327,7 @@ template <class V, class P, class GEO, bool VEC, bool THREE> hipError_t launch_r
     (void)hipGetLastError();
     for (long long b0 = 0; b0 < owners; b0 += max_b) {
         const long long nb = std::min(max_b, owners - b0), tiles = nb * per_b;
-        long long       grid = (long long)device_info().cus * blocks_per_cu[d][dev].load(std::memory_order_relaxed);
-        grid = std::max(1ll, std::min(grid, (tiles + GEO::G - 1) / GEO::G));
+        const long long grid = std::max(1ll, persistent_grid(device_info().cus, bpc, (tiles + GEO::G - 1) / GEO::G));
         R2rTileArgs A;
         A.istep = step;
         A.s = GEO::ROWS ? F.batch - 2 * b0 : F.s;
@@ -392,7 +351,7 @@ template <class V, class P, class GEO, bool VEC, bool THREE> hipError_t launch_r
 }
 
 template <class V, int N, bool THREE> hipError_t r2r_run_typed(const R2rFusedLaunch& F, hipStream_t stream) {
-    using P = typename R2rPlanFor<N>::type;
+    using P = typename PlanFor<N>::type;
     constexpr bool f64 = sizeof(V) == 16;
     if (F.s == 1) {
         if constexpr (r2r_fused_ok(N, f64, THREE, R2R_FORM_ROWS)) return launch_r2r_plan<V, P, R2rRowsGeom<V, P, THREE>, false, THREE>(F, stream);

@@ -29,12 +29,6 @@
 
 namespace dfft {
 
-template <int N> struct RealPlanFor;
-#define DFFT_DECL_REAL_PLAN(N, GRP, E, ...) \
-    template <> struct RealPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_REAL_PLAN)
-#undef DFFT_DECL_REAL_PLAN
-
 // Geometry: the C2C row kernel's (one FFT of M points per thread group, about 256 threads per workgroup, twiddles where KernelGeom puts
 // them); the LDS tile of a group also holds the M + 1 bins of the split / merge step in natural order.
 template <class V, class P> struct RealGeom {
@@ -47,22 +41,6 @@ template <class V, class P> struct RealGeom {
     // the split twiddles W^k of a thread's E bins do not depend on the row: kept in registers where they are few
     static constexpr bool TWH_REG = P::E * (int)sizeof(V) / 4 <= 32;
 };
-
-// twiddles of the M-point stages, exactly as fft_tiles_kernel sets them up
-template <class V, class P, int DIR, class KG>
-__device__ __forceinline__ const typename VecTraits<V>::W* real_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
-                                                                        const typename VecTraits<V>::W* __restrict__ tw, int j) {
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        return tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<typename VecTraits<V>::W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        return ldstw;
-    } else {
-        load_twiddles<typename VecTraits<V>::W, P, 0, DIR, true>(twreg, tw, j);
-        return twreg;
-    }
-}
 
 template <class V, class P>
 __global__ void __attribute__((amdgpu_flat_work_group_size(1, RealGeom<V, P>::KG::THREADS)))
@@ -80,7 +58,7 @@ r2c_rows_kernel(const V* __restrict__ in, V* __restrict__ out, const typename Ve
     const int j = tile_j<1, KG::NW>((int)threadIdx.x - g * GT);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * RG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = real_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     W         wh[RG::TWH_REG ? E : 1];
     if constexpr (RG::TWH_REG) {
 #pragma unroll
@@ -133,7 +111,7 @@ c2r_rows_kernel(const V* __restrict__ in, V* __restrict__ out, const typename Ve
     const int j = tile_j<1, KG::NW>((int)threadIdx.x - g * GT);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * RG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = real_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     W         wh[RG::TWH_REG ? E : 1];
     if constexpr (RG::TWH_REG) {
 #pragma unroll
@@ -182,34 +160,15 @@ template <class V, class P> hipError_t launch_real_plan(const RealLaunch& L, con
     using RG = RealGeom<V, P>;
     using W = typename VecTraits<V>::W;
     auto kern = L.dir > 0 ? r2c_rows_kernel<V, P> : c2r_rows_kernel<V, P>;
-    static std::atomic<int> blocks_per_cu[2][64];
-    static std::mutex       setup_mutex;
-    const int               d = L.dir > 0 ? 0 : 1;
-    int                     dev = 0;
-    hipError_t              e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[d][dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        if (blocks_per_cu[d][dev].load(std::memory_order_relaxed) == 0) {
-            if (RG::LDS_BYTES > 64 * 1024) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RG::LDS_BYTES);
-                if (e != hipSuccess) return e;
-            }
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RG::KG::THREADS, RG::LDS_BYTES) != hipSuccess) {
-                (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-                occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, RG::LDS_BYTES));
-            }
-            blocks_per_cu[d][dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-        }
-    }
+    static std::atomic<int> blocks_per_cu[2][kMaxDevices];  // per kernel: R2C, C2R
+    hipError_t              e;
+    const int               bpc = resident_blocks_per_cu(reinterpret_cast<const void*>(kern), RG::KG::THREADS, RG::LDS_BYTES, blocks_per_cu[L.dir > 0 ? 0 : 1], &e);
+    if (bpc == 0) return e;
     const bool      fwd = L.dir > 0;
     // in units of V: the real side's strides count reals, two per complex value
     const long long ip = fwd ? L.rpitch / 2 : L.cpitch, ipl = fwd ? L.rplane / 2 : L.cplane;
     const long long op = fwd ? L.cpitch : L.rpitch / 2, opl = fwd ? L.cplane : L.rplane / 2;
-    long long       grid = (long long)device_info().cus * blocks_per_cu[d][dev].load(std::memory_order_relaxed);
-    grid = std::min(grid, (L.rows + RG::G - 1) / RG::G);
+    const long long grid = persistent_grid(device_info().cus, bpc, (L.rows + RG::G - 1) / RG::G);
     if (grid < 1) return hipSuccess;
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RG::KG::THREADS), RG::LDS_BYTES, stream, (const V*)L.in, (V*)L.out, (const W*)tw,
@@ -226,8 +185,8 @@ template <int N> struct RealInst<true, N> {
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
 
 template <int N> hipError_t RealInst<true, N>::run(const RealLaunch& L, const void* tw, const void* twh, hipStream_t stream) {
-    if (L.dtype == F64) return launch_real_plan<double2, typename RealPlanFor<N>::type>(L, tw, twh, stream);
-    if (L.dtype == F32) return launch_real_plan<float2, typename RealPlanFor<N>::type>(L, tw, twh, stream);
+    if (L.dtype == F64) return launch_real_plan<double2, typename PlanFor<N>::type>(L, tw, twh, stream);
+    if (L.dtype == F32) return launch_real_plan<float2, typename PlanFor<N>::type>(L, tw, twh, stream);
     return hipErrorInvalidValue;
 }
 #define DFFT_REAL_INST(N, GRP, E, ...) template struct RealInst<(GRP == DFFT_INST_GROUP), N>;

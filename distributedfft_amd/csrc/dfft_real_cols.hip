@@ -37,7 +37,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <mutex>
 
 #ifndef DFFT_INST_GROUP
 #error "compile with -DDFFT_INST_GROUP=<g>"
@@ -54,12 +53,6 @@ struct ColsFusedLaunch {
     void*       out;
     const void* tw;
 };
-
-template <int N> struct ColsPlanFor;
-#define DFFT_DECL_COLS_PLAN(N, GRP, E, ...) \
-    template <> struct ColsPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_COLS_PLAN)
-#undef DFFT_DECL_COLS_PLAN
 
 // entry point of the tuned length N: defined (and explicitly instantiated) in the translation unit of N's group only
 template <bool ON, int N> struct ColsInst {};
@@ -93,22 +86,6 @@ template <class V, class P> struct ColsGeom {
     static constexpr int EXR = ((KG::LDS_ELEMS > SPLIT ? KG::LDS_ELEMS : SPLIT) + 1) / 2 * 2;
     static constexpr size_t LDS_BYTES = (size_t)EXR * G * sizeof(V) + KG::TW_BYTES;
 };
-
-// twiddles of the n-point stages, exactly as fft_tiles_kernel sets them up
-template <class V, class P, int DIR, class KG>
-__device__ __forceinline__ const typename VecTraits<V>::W* cols_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
-                                                                        const typename VecTraits<V>::W* __restrict__ tw, int j) {
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        return tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<typename VecTraits<V>::W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        return ldstw;
-    } else {
-        load_twiddles<typename VecTraits<V>::W, P, 0, DIR, true>(twreg, tw, j);
-        return twreg;
-    }
-}
 
 // XCD-aware tile order for tiles narrower than a 128-byte line, exactly as fft_tiles_kernel has it (dfft_fft_impl.h, map_tile): the Q
 // tiles that share the lines of one row segment go to workgroups Q consecutive slots apart on the SAME XCD (workgroup b runs on XCD
@@ -153,7 +130,7 @@ r2c_pair_cols_kernel(const typename real_of<V>::type* __restrict__ in, V* __rest
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * CG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = cols_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const RT  half = (RT)0.5;
     const long long sp = (s + 1) / 2;
     const unsigned  us = (unsigned)s;
@@ -220,7 +197,7 @@ c2r_pair_cols_kernel(const V* __restrict__ in, typename real_of<V>::type* __rest
     const int j = tile_j<CB, KG::NW>(tid);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * CG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = cols_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const long long sp = (s + 1) / 2;
     const unsigned  us = (unsigned)s;
     const unsigned  remap_full = cols_remap_full<V, CB, G>(tiles, tiles_per_b);
@@ -274,37 +251,18 @@ template <class V, class P> hipError_t launch_cols_plan(const ColsFusedLaunch& F
     using W = typename VecTraits<V>::W;
     using RT = typename real_of<V>::type;
     constexpr int           N = P::N, NH = N / 2 + 1;
-    static std::atomic<int> blocks_per_cu[2][2][64];
-    static std::mutex       setup_mutex;
-    const int               d = fwd ? 0 : 1, vi = F.vec ? 1 : 0;
+    static std::atomic<int> blocks_per_cu[2][2][kMaxDevices];  // per kernel: direction, VEC
     const void*             kern = F.vec ? cols_kernel<V, P, true>(fwd) : cols_kernel<V, P, false>(fwd);
-    int                     dev = 0;
-    hipError_t              e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[d][vi][dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        if (blocks_per_cu[d][vi][dev].load(std::memory_order_relaxed) == 0) {
-            if (CG::LDS_BYTES > 64 * 1024) {
-                e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG::LDS_BYTES);
-                if (e != hipSuccess) return e;
-            }
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, CG::KG::THREADS, CG::LDS_BYTES) != hipSuccess) {
-                (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-                occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, CG::LDS_BYTES));
-            }
-            blocks_per_cu[d][vi][dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-        }
-    }
+    hipError_t              e;
+    const int               bpc = resident_blocks_per_cu(kern, CG::KG::THREADS, CG::LDS_BYTES, blocks_per_cu[fwd ? 0 : 1][F.vec ? 1 : 0], &e);
+    if (bpc == 0) return e;
     const long long per_b = ((F.s + 1) / 2 + CG::CB - 1) / CG::CB;
     const long long max_b = std::max(1ll, ((1ll << 31) - 1) / per_b);  // tile indices stay below 2^31 per launch
     const long long rstep = (long long)N * F.s, cstep = (long long)NH * F.s;
     (void)hipGetLastError();
     for (long long b0 = 0; b0 < F.batch; b0 += max_b) {
         const long long nb = std::min(max_b, F.batch - b0), tiles = nb * per_b;
-        long long       grid = (long long)device_info().cus * blocks_per_cu[d][vi][dev].load(std::memory_order_relaxed);
-        grid = std::max(1ll, std::min(grid, (tiles + CG::G - 1) / CG::G));
+        const long long grid = std::max(1ll, persistent_grid(device_info().cus, bpc, (tiles + CG::G - 1) / CG::G));
         if (fwd) {
             const RT* ip = (const RT*)F.in + b0 * rstep;
             V*        op = (V*)F.out + b0 * cstep;
@@ -331,8 +289,8 @@ template <class V, class P> hipError_t launch_cols_plan(const ColsFusedLaunch& F
 }
 
 template <int N> hipError_t ColsInst<true, N>::run(const ColsFusedLaunch& F, hipStream_t stream) {
-    if (F.dtype == F64) return launch_cols_plan<double2, typename ColsPlanFor<N>::type>(F, F.dir > 0, stream);
-    if (F.dtype == F32) return launch_cols_plan<float2, typename ColsPlanFor<N>::type>(F, F.dir > 0, stream);
+    if (F.dtype == F64) return launch_cols_plan<double2, typename PlanFor<N>::type>(F, F.dir > 0, stream);
+    if (F.dtype == F32) return launch_cols_plan<float2, typename PlanFor<N>::type>(F, F.dir > 0, stream);
     return hipErrorInvalidValue;
 }
 #define DFFT_COLS_INST(N, GRP, E, ...) template struct ColsInst<(GRP == DFFT_INST_GROUP), N>;

@@ -32,19 +32,12 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <mutex>
 
 #ifndef DFFT_INST_GROUP
 #error "compile with -DDFFT_INST_GROUP=<g>"
 #endif
 
 namespace dfft {
-
-template <int N> struct PairPlanFor;
-#define DFFT_DECL_PAIR_PLAN(N, GRP, E, ...) \
-    template <> struct PairPlanFor<N> { using type = Plan<N, E, __VA_ARGS__>; };
-DFFT_PLAN_TABLE(DFFT_DECL_PAIR_PLAN)
-#undef DFFT_DECL_PAIR_PLAN
 
 // element offset of row r of a (plane, row) tiling
 __device__ __forceinline__ long long pair_row_off(unsigned r, unsigned rows_per_plane, long long pitch, long long plane) {
@@ -62,22 +55,6 @@ template <class V, class P> struct PairGeom {
     static constexpr size_t LDS_BYTES = (size_t)EXR * G * sizeof(V) + KG::TW_BYTES;
 };
 
-// twiddles of the n-point stages, exactly as fft_tiles_kernel sets them up
-template <class V, class P, int DIR, class KG>
-__device__ __forceinline__ const typename VecTraits<V>::W* pair_twiddles(typename VecTraits<V>::W* twreg, typename VecTraits<V>::W* ldstw,
-                                                                        const typename VecTraits<V>::W* __restrict__ tw, int j) {
-    if constexpr (KG::TWMODE == TW_GLOBAL) {
-        return tw;
-    } else if constexpr (KG::TWMODE == TW_LDS) {
-        fill_stage_major<typename VecTraits<V>::W, P, 0, DIR, KG::NW>(ldstw, tw, (int)threadIdx.x, KG::THREADS);
-        __syncthreads();
-        return ldstw;
-    } else {
-        load_twiddles<typename VecTraits<V>::W, P, 0, DIR, true>(twreg, tw, j);
-        return twreg;
-    }
-}
-
 // R2C: real rows (strides in reals) -> bin rows (n/2 + 1 bins; strides in complex elements)
 template <class V, class P>
 __global__ void __attribute__((amdgpu_flat_work_group_size(1, PairGeom<V, P>::KG::THREADS)))
@@ -94,7 +71,7 @@ r2c_pair_rows_kernel(const typename real_of<V>::type* __restrict__ in, V* __rest
     const int j = tile_j<1, KG::NW>((int)threadIdx.x - g * GT);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * PG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = pair_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, +1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const RT  half = (RT)0.5;
     const unsigned pairs = (rows + 1) / 2;
     for (unsigned p0 = blockIdx.x * G; p0 < pairs; p0 += gridDim.x * G) {
@@ -148,7 +125,7 @@ c2r_pair_rows_kernel(const V* __restrict__ in, typename real_of<V>::type* __rest
     const int j = tile_j<1, KG::NW>((int)threadIdx.x - g * GT);
     V*        lds = reinterpret_cast<V*>(dfft_smem + KG::TW_BYTES) + g * PG::EXR;
     W         twreg[KG::TWMODE == TW_REG && KG::TWN > 0 ? KG::TWN : 1];
-    const W*  twr = pair_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
+    const W*  twr = stage_twiddles<V, P, -1, KG>(twreg, reinterpret_cast<W*>(dfft_smem), tw, j);
     const unsigned pairs = (rows + 1) / 2;
     for (unsigned p0 = blockIdx.x * G; p0 < pairs; p0 += gridDim.x * G) {
         const unsigned pr = p0 + g;
@@ -190,31 +167,12 @@ template <class V, class P> hipError_t launch_pair_plan(const RealPairLaunch& L,
     using RT = typename real_of<V>::type;
     const bool              fwd = L.dir > 0;
     const void*             kern = fwd ? reinterpret_cast<const void*>(r2c_pair_rows_kernel<V, P>) : reinterpret_cast<const void*>(c2r_pair_rows_kernel<V, P>);
-    static std::atomic<int> blocks_per_cu[2][64];
-    static std::mutex       setup_mutex;
-    const int               d = fwd ? 0 : 1;
-    int                     dev = 0;
-    hipError_t              e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (blocks_per_cu[d][dev].load(std::memory_order_acquire) == 0) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        if (blocks_per_cu[d][dev].load(std::memory_order_relaxed) == 0) {
-            if (PG::LDS_BYTES > 64 * 1024) {
-                e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PG::LDS_BYTES);
-                if (e != hipSuccess) return e;
-            }
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, PG::KG::THREADS, PG::LDS_BYTES) != hipSuccess) {
-                (void)hipGetLastError();  // advisory only: the grid-stride loop is correct for any grid
-                occ = (int)std::max<size_t>(1, 160 * 1024 / std::max<size_t>(1, PG::LDS_BYTES));
-            }
-            blocks_per_cu[d][dev].store(occ > 0 ? occ : 1, std::memory_order_release);
-        }
-    }
+    static std::atomic<int> blocks_per_cu[2][kMaxDevices];  // per kernel: R2C, C2R
+    hipError_t              e;
+    const int               bpc = resident_blocks_per_cu(kern, PG::KG::THREADS, PG::LDS_BYTES, blocks_per_cu[fwd ? 0 : 1], &e);
+    if (bpc == 0) return e;
     const long long pairs = (L.rows + 1) / 2;
-    long long       grid = (long long)device_info().cus * blocks_per_cu[d][dev].load(std::memory_order_relaxed);
-    grid = std::min(grid, (pairs + PG::G - 1) / PG::G);
+    const long long grid = persistent_grid(device_info().cus, bpc, (pairs + PG::G - 1) / PG::G);
     if (grid < 1) return hipSuccess;
     (void)hipGetLastError();
     if (fwd)
@@ -235,8 +193,8 @@ template <int N> struct PairInst<true, N> {
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
 
 template <int N> hipError_t PairInst<true, N>::run(const RealPairLaunch& L, const void* tw, hipStream_t stream) {
-    if (L.dtype == F64) return launch_pair_plan<double2, typename PairPlanFor<N>::type>(L, tw, stream);
-    if (L.dtype == F32) return launch_pair_plan<float2, typename PairPlanFor<N>::type>(L, tw, stream);
+    if (L.dtype == F64) return launch_pair_plan<double2, typename PlanFor<N>::type>(L, tw, stream);
+    if (L.dtype == F32) return launch_pair_plan<float2, typename PlanFor<N>::type>(L, tw, stream);
     return hipErrorInvalidValue;
 }
 #define DFFT_PAIR_INST(N, GRP, E, ...) template struct PairInst<(GRP == DFFT_INST_GROUP && N % 2 == 1), N>;

@@ -469,18 +469,10 @@ template <class PZ, class PY, int DIR, bool PACK, bool LAZY = false, int SIGN = 
     constexpr size_t LDS_BYTES = 64 + TW_BYTES + (ROW_BYTES > COL_BYTES ? ROW_BYTES : COL_BYTES);
     static_assert(LDS_BYTES <= 160 * 1024, "a unit and the twiddle tables must fit the LDS of a CU");
     auto             kern = zy_chunk_kernel<PZ, PY, DIR, PACK, LAZY, SIGN, SIG>;
-    static std::atomic<bool> attr_set[64];
-    static std::mutex        setup_mutex;
-    int                      dev = 0;
-    hipError_t               e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> lk(setup_mutex);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    // one workgroup per CU (zy_grid): the opt-in half of the set-up alone
+    static std::atomic<int> attr_set[kMaxDevices];
+    hipError_t              e;
+    if (resident_blocks_per_cu(reinterpret_cast<const void*>(kern), THREADS, LDS_BYTES, attr_set, &e, false) == 0) return e;
     constexpr int PK_GRAIN = (PY::T == 64 && (LAZY || PY::N == 768)) ? 32 : PY::T;  // (PK2 in the kernel)
     if (SIG && (!L.part_done || L.part_planes <= 0)) return hipErrorInvalidValue;
     if (PACK && (L.pk.blk <= 0 || L.pk.blk % PK_GRAIN != 0 || L.pk.last_delta != 0)) return hipErrorInvalidValue;

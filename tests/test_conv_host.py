@@ -176,7 +176,7 @@ def test_inventory_belongs_to_the_sources_and_nothing_spills():
     every required (length x dtype x filter kind x map) and shows scratch=0 everywhere."""
     text = INVENTORY.read_text()
     h = hashlib.sha256()
-    for name in ("dfft_conv.hip", "dfft_conv.h"):
+    for name in ("dfft_conv.hip", "dfft_conv.h", "dfft_conv_impl.h"):
         h.update((CSRC / name).read_bytes())
     m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
     assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/conv_resources.py profiles/r12/kernel_resources.txt"

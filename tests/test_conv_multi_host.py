@@ -233,7 +233,7 @@ def test_inventory_belongs_to_the_sources_and_nothing_spills():
     kernel of every fused length in both precisions and for both filter kinds and the factor multiply, and shows scratch=0 everywhere."""
     text = INVENTORY.read_text()
     h = hashlib.sha256()
-    for name in ("dfft_conv_multi.hip", "dfft_conv_multi.h"):
+    for name in ("dfft_conv_multi.hip", "dfft_conv_multi.h", "dfft_conv_impl.h"):
         h.update((CSRC / name).read_bytes())
     m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
     assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/conv_multi_resources.py profiles/r14/kernel_resources.txt"
@@ -243,12 +243,14 @@ def test_inventory_belongs_to_the_sources_and_nothing_spills():
         f = re.match(r"xconv_multi_cols_kernel (f64|f32pair) N=(\d+) E=\d+ filter=(complex|real) ", ln)
         if f:
             fused.add((f.group(1), int(f.group(2)), f.group(3)))
-    # the lengths that claim xconv=fused: conv_fused_length of dfft_conv.hip, restated as xm_fused_n in the new header
-    hdr = (CSRC / "dfft_conv_multi.h").read_text()
-    claimed = tuple(int(v) for v in re.findall(r"n == (\d+)", re.search(r"constexpr bool xm_fused_n\(int n\) \{([^}]*)\}", hdr).group(1)))
-    old = (CSRC / "dfft_conv.hip").read_text()
-    assert claimed == tuple(int(v) for v in re.findall(r"n == (\d+)", re.search(r"constexpr bool conv_fused_n\(int n\) \{([^}]*)\}", old).group(1)))
+    # the lengths that claim xconv=fused: the one conv_fused_n of dfft_conv_impl.h, which both kernel units take -- no list of their own
+    shared = (CSRC / "dfft_conv_impl.h").read_text()
+    claimed = tuple(int(v) for v in re.findall(r"n == (\d+)", re.search(r"constexpr bool conv_fused_n\(int n\) \{([^}]*)\}", shared).group(1)))
     assert claimed == FUSED_LENGTHS
+    for name in ("dfft_conv_multi.h", "dfft_conv_multi.hip", "dfft_conv.hip"):
+        own = (CSRC / name).read_text()
+        assert not re.search(r"\bn == \d+", own) and not re.search(r"constexpr bool \w*fused_n\b", own), name
+        assert name.endswith(".h") or '#include "dfft_conv_impl.h"' in own, name
     assert fused == {(t, n, k) for t in ("f64", "f32pair") for n in FUSED_LENGTHS for k in ("complex", "real")}, fused
     assert {ln.split()[1] for ln in kernels if ln.startswith("xconv_factor_mul_kernel ")} == {"f64", "f32x2"}
     for ln in kernels:
@@ -267,8 +269,9 @@ def test_build_compiles_the_conv_multi_unit():
 
 
 def test_the_single_output_sources_are_untouched():
-    """The four existing conv sources are pinned by sha256 into profiles/r12 and r13; this file only adds."""
-    for inv, names in ((ROOT / "profiles" / "r12" / "kernel_resources.txt", ("dfft_conv.hip", "dfft_conv.h")),
+    """The conv sources the multi-output kernel shares its traits with (dfft_conv_impl.h among them) are the ones pinned by sha256 into
+    profiles/r12 and r13: a change to the shared header shows up in the single-output inventory too."""
+    for inv, names in ((ROOT / "profiles" / "r12" / "kernel_resources.txt", ("dfft_conv.hip", "dfft_conv.h", "dfft_conv_impl.h")),
                        (ROOT / "profiles" / "r13" / "kernel_resources.txt", ("dfft_conv_real.hip", "dfft_conv_real.h"))):
         h = hashlib.sha256()
         for name in names:

@@ -16,7 +16,7 @@ sys.path.insert(0, str(ROOT))
 from distributedfft_amd.build import NUM_INST_GROUPS as GROUPS  # noqa: E402
 
 CSRC = ROOT / "distributedfft_amd" / "csrc"
-SOURCES = ("dfft_conv_multi.hip", "dfft_conv_multi.h")
+SOURCES = ("dfft_conv_multi.hip", "dfft_conv_multi.h", "dfft_conv_impl.h")
 
 
 def sources_sha256():
@@ -69,7 +69,7 @@ def main():
     rows.sort(key=lambda r: (r["N"], r["kind"], r["type"], r["filter"]))
     lines = [f"# sources sha256 {sources_sha256()} ({' + '.join(SOURCES)})",
              "# X stage of the multi-output spectral-filter plans, gfx950 (hipcc -O3 -Rpass-analysis=kernel-resource-usage; tools/conv_multi_resources.py)",
-             "# kernel type N E filter vgpr agpr scratch_bytes_per_lane static_lds_bytes waves_per_simd (fused kernels: dynamic LDS, see XmGeom)"]
+             "# kernel type N E filter vgpr agpr scratch_bytes_per_lane static_lds_bytes waves_per_simd (fused kernels: dynamic LDS, see XcGeom)"]
     for r in rows:
         lines.append(f"{r['kind']}_kernel {r['type']} N={r['N']} E={r['E']} filter={r['filter']} vgpr={r.get('vgpr')} "
                      f"agpr={r.get('agpr')} scratch={r.get('scratch')} lds={r.get('lds')} occ={r.get('occ')}")

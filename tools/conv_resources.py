@@ -1,6 +1,6 @@
 """Register / scratch / LDS / occupancy of the spectral-filter plans' X stage (csrc/dfft_conv.hip): the fused xconv_cols_kernel of every
 instantiation group and the multiply / re-layout kernels of the dispatcher unit, from the compiler's
--Rpass-analysis=kernel-resource-usage remarks (no GPU needed).  The first line carries the sha256 of dfft_conv.hip and dfft_conv.h, so
+-Rpass-analysis=kernel-resource-usage remarks (no GPU needed).  The first line carries the sha256 of dfft_conv.hip, dfft_conv.h and dfft_conv_impl.h, so
 tests/test_conv_host.py can tell whether the inventory belongs to the sources in the tree.
 
   python tools/conv_resources.py [out.txt]        one line per kernel, sorted by length"""
@@ -16,7 +16,7 @@ sys.path.insert(0, str(ROOT))
 from distributedfft_amd.build import NUM_INST_GROUPS as GROUPS  # noqa: E402
 
 CSRC = ROOT / "distributedfft_amd" / "csrc"
-SOURCES = ("dfft_conv.hip", "dfft_conv.h")
+SOURCES = ("dfft_conv.hip", "dfft_conv.h", "dfft_conv_impl.h")
 
 
 def sources_sha256():
