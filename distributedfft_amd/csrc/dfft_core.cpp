@@ -199,6 +199,12 @@ int dfft_cols_extent_supported(long long n, long long width, int dtype, int pair
     if (n < 1 || width < 1 || !valid_dtype(dtype) || length_kind(n) == 0 || length_kind(n) == 3) return 0;
     return cols_extent_ok(n, width, dtype, pairs != 0, pairs != 0) ? 1 : 0;
 }
+// The ticket base of a plan's X pass (dfft_plan_impl.h, x_ticket) after `launches` launches, stepped exactly as launch_variant steps it.
+// Not part of the C-ABI of include/dfft.h: exported for tests/test_x_ticket_host.py only, which binds it itself.
+unsigned dfft_x_ticket_base_after(unsigned base, long long ntiles, long long grid, long long launches) {
+    for (long long g = 0; g < launches; ++g) base += x_ticket_count((unsigned)ntiles, (unsigned)grid);
+    return base;
+}
 // The same for dfft_fft1d_any along the middle axis of [batch][n][s], every kind of length; in16 / out16: that pointer is 16-byte aligned.
 int dfft_fft1d_any_extent_supported(long long n, long long s, int dtype, int in16, int out16) {
     if (n < 1 || s < 1 || !valid_dtype(dtype) || length_kind(n) == 0) return 0;

@@ -110,6 +110,21 @@ struct TuneTransposedStoreFullEarly : TuneTransposedStoreFull {
 struct TuneTransposedStoreEarly : TuneTransposedStore {
     static constexpr bool EARLY_WAIT = true;
 };
+// TICKET: tiles are handed out by a counter in device memory instead of the static grid-stride loop -- the forward X pass of a plan,
+// which owns the counter (FftLaunch::x_ticket).  Read latency behind the L2 depends on where a request lands, so workgroups do not
+// progress at one rate and a static share ends with the slowest of them.  Thread 0 takes the next ticket with a relaxed agent-scope
+// fetch_add TWO tiles ahead (as zy_chunk_kernel does), so that the atomic's round trip lies underneath a whole tile and the prefetch
+// of the next tile uses the ticket taken one tile earlier.  Every workgroup ends on its second ticket past the last tile; a launch
+// therefore advances the counter by ntiles + 2 * grid (x_ticket_count), which is what the host adds to its running ticket base -- the
+// counter is never reset, and nothing waits or polls: a tile depends on nothing inside the launch.
+struct TuneTransposedStoreTicket : TuneTransposedStore {
+    static constexpr bool TICKET = true;
+};
+struct TuneTransposedStoreTicketEarly : TuneTransposedStoreEarly {
+    static constexpr bool TICKET = true;
+};
+template <class T, class = void> struct tune_ticket : std::false_type {};
+template <class T> struct tune_ticket<T, std::void_t<decltype(T::TICKET)>> : std::bool_constant<T::TICKET> {};
 
 // Column kernel default: the next tile's loads are issued before the current tile's exchanges (0.945 -> 0.869 ms on the
 // 512^3 fp64 Y pass; no gain for the barrier-free row kernel, which keeps TuneDefault).
@@ -631,7 +646,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, KernelGeom<V, P, C
                                amdgpu_waves_per_eu(Tune::MIN_WAVES > 0 ? Tune::MIN_WAVES : 1)))
 fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* out,
                  const typename VecTraits<V>::W* __restrict__ tw, AxisMap imap, AxisMap omap, TileMap itile, TileMap otile,
-                 unsigned ntiles, unsigned tiles_per_a, int ncols, unsigned a_first, double scale, RotMap rm) {
+                 unsigned ntiles, unsigned tiles_per_a, int ncols, unsigned a_first, double scale, RotMap rm, unsigned* ticket_ctr,
+                 unsigned ticket_base) {
     using KG = KernelGeom<V, P, CB, G, Tune>;
     using VT = VecTraits<V>;
     using W = typename VT::W;
@@ -776,12 +792,40 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
     using KE = std::integral_constant<int, E>;
     V v[E];
     V vnext[PF > 0 ? PF : 1];
-    if constexpr (PREFETCH) {
+    // Tiles by ticket (Tune::TICKET, see TuneTransposedStoreTicket): `first` and `second` are the tickets the workgroup holds, i.e. the
+    // tile it is working on and the one it prefetches; map_tile is applied to a ticket as it is to a tile of the static loop.
+    constexpr bool TICKET = tune_ticket<Tune>::value;
+    static_assert(!TICKET || (G == 1 && PREFETCH && KG::OSTAGE && KG::PH == 1 && !KG::WAVE_LOCAL && !GENERAL),
+                  "tickets: one block-wide tile per workgroup, whole-tile prefetch, one-phase staged store");
+    unsigned  first = 0, second = 0;
+    unsigned* ticket_word = nullptr;  // LDS word through which thread 0 hands a ticket to the workgroup
+    auto take = [&]() -> unsigned {   // thread 0: the next ticket (the atomic's latency hides behind a tile)
+        return threadIdx.x == 0 ? __hip_atomic_fetch_add(ticket_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - ticket_base : 0u;
+    };
+    if constexpr (TICKET) {
+        __shared__ unsigned ticket_lds[2];
+        ticket_word = ticket_lds;
+        const unsigned ta = take(), tb = take();
+        if (threadIdx.x == 0) {
+            ticket_lds[0] = ta;
+            ticket_lds[1] = tb;
+        }
+        __syncthreads();
+        // block-uniform: tickets and what is decoded from them stay in scalar registers
+        first = __builtin_amdgcn_readfirstlane(ticket_lds[0]);
+        second = __builtin_amdgcn_readfirstlane(ticket_lds[1]);
+        if (first < ntiles) load_tile(first, v);
+    } else if constexpr (PREFETCH) {
         if (blockIdx.x * G < ntiles) load_tile(blockIdx.x * G, v);
     } else if constexpr (PARTIAL) {
         if (blockIdx.x * G < ntiles) load_part(blockIdx.x * G, v, K0{}, KP{});
     }
-    for (unsigned t0 = blockIdx.x * G; t0 < ntiles; t0 += tstep) {
+    // tickets grow from take to take, so a workgroup whose `first` lies past the end holds a `second` past the end too, and one that
+    // runs out of tiles has drawn exactly two such tickets: ntiles + 2 * grid per launch (x_ticket_count)
+    for (unsigned t0 = TICKET ? first : blockIdx.x * G; t0 < ntiles; t0 = TICKET ? first : t0 + tstep) {
+        const unsigned tn = TICKET ? second : t0 + tstep;  // the tile group this workgroup takes up next
+        unsigned       drawn = 0;                           // TICKET: the ticket thread 0 draws now, for the tile after next
+        if constexpr (TICKET) drawn = take();
         const unsigned tile = map_tile(t0 + g);
         bool valid = tile < ntiles;
         const unsigned al = tile / tiles_per_a;
@@ -794,10 +838,10 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
 
         if constexpr (PREFETCH) {
             // issue the next tile's HBM loads now; they complete underneath this tile's exchanges and stores
-            if (t0 + tstep < ntiles) load_tile(t0 + tstep, vnext);
+            if (tn < ntiles) load_tile(tn, vnext);
         } else if constexpr (PARTIAL) {
-            load_part(t0, v + PF, KP{}, KE{});                                   // the rest of this tile
-            if (t0 + tstep < ntiles) load_part(t0 + tstep, vnext, K0{}, KP{});  // the first points of the next one
+            load_part(t0, v + PF, KP{}, KE{});                     // the rest of this tile
+            if (tn < ntiles) load_part(tn, vnext, K0{}, KP{});  // the first points of the next one
         } else {
             load_tile(t0, v);
         }
@@ -822,7 +866,11 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
                 for (int k = 0; k < E; ++k)
 #pragma unroll
                     for (int l = 0; l < LANES; ++l) img[(c * LANES + l) * ROW + j + T * k] = VT::lane(cscale(v[k], sc), l);
+                if constexpr (TICKET) {  // (the word was last read behind the previous tile's second barrier)
+                    if (threadIdx.x == 0) ticket_word[0] = drawn;
+                }
                 group_sync<KG::WAVE_LOCAL>();
+                if constexpr (TICKET) drawn = __builtin_amdgcn_readfirstlane(ticket_word[0]);  // the workgroup's copy
                 if constexpr (EARLY && PF > 0) {
 #pragma unroll
                     for (int k = 0; k < PF; ++k) pin_loaded(vnext[k]);
@@ -877,6 +925,10 @@ fft_tiles_kernel(const typename VecTraits<V>::G* in, typename VecTraits<V>::G* o
         if constexpr (PF > 0) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) v[k] = vnext[k];
+        }
+        if constexpr (TICKET) {
+            first = second;
+            second = drawn;
         }
     }
 }
@@ -1415,13 +1467,18 @@ hipError_t launch_variant(const FftLaunch& L, hipStream_t stream, int* blocks_pe
     if (blocks_per_cu_out) *blocks_per_cu_out = bpc;
     const long long grid = persistent_grid(device_info().cus, bpc, (L.ntiles + G - 1) / G, L.grid_limit, L.blocks_per_cu_limit);
     if (grid < 1) return hipSuccess;
+    // tiles by ticket: the launch starts at the caller's running ticket base, which then moves on by what the launch draws
+    constexpr bool TICKET = tune_ticket<Tune>::value;
+    if (TICKET && (!L.x_ticket || !L.x_ticket_base)) return hipErrorInvalidValue;
     (void)hipGetLastError();  // drop any stale error of this thread (other libraries share the runtime)
     using GV = typename VecTraits<V>::G;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(KG::THREADS), KG::LDS_BYTES, stream, (const GV*)L.in, (GV*)L.out,
                        (const typename VecTraits<V>::W*)L.tw, L.imap, L.omap, L.itile, L.otile, (unsigned)L.ntiles,
-                       (unsigned)L.tiles_per_a, L.ncols, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot);
+                       (unsigned)L.tiles_per_a, L.ncols, (unsigned)L.a_first, L.scale == 0.0 ? 1.0 : L.scale, L.rot,
+                       TICKET ? L.x_ticket : nullptr, TICKET ? *L.x_ticket_base : 0u);
     e = hipGetLastError();
     if (e != hipSuccess) return launch_debug(e, "kernel launch", (int)KG::LDS_BYTES, KG::THREADS);
+    if (TICKET) *L.x_ticket_base += x_ticket_count((unsigned)L.ntiles, (unsigned)grid);
     return hipSuccess;
 }
 
@@ -1649,9 +1706,19 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
         const bool single_in = L.imap.nblk == 1 && L.imap.sub <= 1 && L.imap.last_delta == 0;
         const bool want_early = (L.hints & FFT_HINT_EARLY_WAIT) != 0;
         const int  full = (can_full && staged && L.dir > 0 && single_in && !(L.hints & FFT_HINT_HALF_PREFETCH)) ? (want_early ? 2 : 1) : 0;
-        // (8 points per thread, the 512-point X pass: the early wait is a measurement switch only)
+        // 8 points per thread, the 512-point X pass.  The whole-slab X pass of a single-GPU fp64 plan -- the launch that carries the plan's
+        // ticket counter -- hands its tiles out by ticket and waits early for the prefetched tile; the kernel is chosen by the element type
+        // at compile time, so fp32 column pairs (which lose a quarter with the early wait, profiles/r03/README.md section 6) and every
+        // launch without a counter (plan-less entry points, P > 1 plans, sub-block launches) keep the static loop and the late wait.
+        // FFT_HINT_STATIC_TILES / FFT_HINT_LATE_WAIT select the A/B partners; FFT_HINT_EARLY_WAIT stays the measurement switch of both
+        // types.  Each change measured alone and both together: profiles/2026-10-19_x_ticket/README.md.
         constexpr bool can_early = can_stage && P::N == 512 && sizeof(V) == 16;
-        const bool early = can_early && staged && L.dir > 0 && want_early;
+        constexpr bool x512_f64 = can_early && VecTraits<V>::LANES == 1 && CBO == 0;
+        using TTK = TuneTransposedStoreTicket;
+        using TTKE = TuneTransposedStoreTicketEarly;
+        const bool plan_x = x512_f64 && staged && L.dir > 0 && !rot && L.x_ticket && L.x_ticket_base;
+        const bool early = can_early && staged && L.dir > 0 && (want_early || (plan_x && !(L.hints & FFT_HINT_LATE_WAIT)));
+        const bool ticket = plan_x && !(L.hints & FFT_HINT_STATIC_TILES);
         // half-line tiles (2048 points) with the transposing store: pair the two tiles of every 128-byte line in one workgroup
         // when columns are adjacent in memory on the input side (forward X pass)
         constexpr bool can_dual = P::S > 1 && sizeof(V) == 16 && 2 * CBC * sizeof(V) == 128 && (P::N & (P::N - 1)) == 0 && (P::N / VecTraits<V>::LANES) % (CBC * P::T) == 0 &&
@@ -1808,6 +1875,10 @@ template <class V, class P, class PH = void, int CBO = 0> hipError_t launch_plan
             if constexpr (can_full) {
                 if (full == 2) return launch_variant<V, P, CBC, GC, +1, false, TTFE>(L, stream);
                 if (full == 1) return launch_variant<V, P, CBC, GC, +1, false, TTF>(L, stream);
+            }
+            if constexpr (x512_f64) {
+                if (plan_x && L.x_form) *L.x_form = X_FORM_512_F64 | (early ? X_FORM_EARLY : 0) | (ticket ? X_FORM_TICKET : 0);
+                if (ticket) return early ? launch_variant<V, P, CBC, GC, +1, false, TTKE>(L, stream) : launch_variant<V, P, CBC, GC, +1, false, TTK>(L, stream);
             }
             if constexpr (can_early)
                 if (early) return launch_variant<V, P, CBC, GC, +1, false, TTE>(L, stream);

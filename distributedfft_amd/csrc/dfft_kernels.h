@@ -68,13 +68,27 @@ struct FftLaunch {
     RotMap      rot;                  // row rotation of an exchange-buffer side (all zero: none)
     int         grid_limit;           // > 0: cap the persistent grid at this many workgroups (HBM writes run faster from
                                       // fewer concurrent writers, profiles/r02/README.md section 1; tuning knob)
+    // Tiles by ticket (forward X pass of a plan through the staged store, fp64, 512 points): the plan's counter in device memory and
+    // the host's running base, i.e. the counter's value when the next launch starts.  The launch reads *x_ticket_base and adds
+    // x_ticket_count() to it.  Both null: the static grid-stride loop (every plan-less entry point).
+    unsigned*   x_ticket;
+    unsigned*   x_ticket_base;
+    int*        x_form;  // not null: receives the X_FORM_* bits of the kernel the launch selected (dfft_plan_describe)
 };
+enum { X_FORM_512_F64 = 1, X_FORM_EARLY = 2, X_FORM_TICKET = 4 };  // the 512-point fp64 staged store ran | with the early wait | by ticket
+// Tickets one launch of `grid` workgroups over `ntiles` tiles draws: one per tile and two past the end per workgroup (each holds two
+// ahead and stops on its second ticket past the end), whatever the order.  The counter is never reset; the base steps by this per
+// launch in wrapping 32-bit arithmetic, and a kernel decodes ticket - base in the same arithmetic.
+inline unsigned x_ticket_count(unsigned ntiles, unsigned grid) { return ntiles + 2u * grid; }
 enum {
     FFT_HINT_STREAM_IN = 1,   // input is read once and must not displace the cache-resident chunk: non-temporal loads
     FFT_HINT_STREAM_OUT = 2,  // output goes to a different buffer and is not re-read soon: non-temporal stores
     // kernel-variant switches of the staged transposing store (forward X pass); measurement switches, never change results
     FFT_HINT_HALF_PREFETCH = 4,  // 16 points per thread: half-tile prefetch instead of the whole-tile one
     FFT_HINT_EARLY_WAIT = 8,     // wait for the prefetched tile before this tile's stores are issued
+    // 512-point fp64 X pass, whose defaults are the early wait and (with FftLaunch::x_ticket) tiles by ticket: the A/B partners
+    FFT_HINT_LATE_WAIT = 16,     // wait for the prefetched tile at the end of the iteration
+    FFT_HINT_STATIC_TILES = 32,  // the static grid-stride loop although the launch carries a ticket counter
 };
 
 // fft_tiles_kernel keeps a thread's point offsets relative to its tile base in 32 bits, in units of one V (16 bytes for fp64 and for the

@@ -181,6 +181,14 @@ int launch_x(dfft_plan_s* p, const void* in, void* out, bool keep_slab, long lon
     }
     L.grid_limit = p->grid_x;
     L.hints |= p->x_hints;
+    if (p->x_ticket_ctr && ys_part <= 0 && !keep_slab) {  // whole-slab launches draw their tiles from the plan's counter (dfft_plan_impl.h)
+        L.x_ticket = p->x_ticket_ctr;
+        L.x_ticket_base = &p->x_ticket;
+    }
+    if (ys_part <= 0) {
+        p->x_form = 0;
+        L.x_form = &p->x_form;
+    }
     return check_launch(launch_fft(L, p->stream), "X pass");
 }
 
@@ -873,11 +881,25 @@ int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2
     {
         // kernel-variant switches (A/B measurements; results are bit-identical either way), read when the plan is created:
         //   DFFT_X_VARIANT=half|full|fullearly  1024-point forward X pass: half-tile prefetch / whole-tile prefetch (default) / + early wait
-        //   DFFT_X_VARIANT=early                512-point forward X pass: early wait for the prefetched tile
+        //   DFFT_X_VARIANT=early                512-point forward X pass: early wait for the prefetched tile (the default in fp64)
+        //   DFFT_X_VARIANT=static|late|static-late  512-point forward X pass in fp64, whose default draws its tiles by ticket and waits
+        //                                       early: the static grid-stride loop / the late wait / both (the form up to round 6)
         //   DFFT_ZY_LAZY=0                      one-launch YZ stage (P = 1): the eager-publish kernel instead of the lazy one
         const char* xv = getenv("DFFT_X_VARIANT");
         if (xv && !strcmp(xv, "half")) p->x_hints = FFT_HINT_HALF_PREFETCH;
         else if (xv && (!strcmp(xv, "fullearly") || !strcmp(xv, "early"))) p->x_hints = FFT_HINT_EARLY_WAIT;
+        else if (xv && !strcmp(xv, "static")) p->x_hints = FFT_HINT_STATIC_TILES;
+        else if (xv && !strcmp(xv, "late")) p->x_hints = FFT_HINT_LATE_WAIT;
+        else if (xv && !strcmp(xv, "static-late")) p->x_hints = FFT_HINT_STATIC_TILES | FFT_HINT_LATE_WAIT;
+        // the ticket counter of the X pass (dfft_plan_impl.h): single-GPU forward plans whose X pass is the 512-point fp64 staged store;
+        // zeroed on the plan's stream and waited for, like the YZ stage's control block below
+        if (dtype == F64 && n0 == 512 && direction == DFFT_FORWARD && n2 % 8 == 0 && !p->exch && !(flags & DFFT_PLAN_NATURAL) && !p->long_axis) {
+            if (hipMalloc((void**)&p->x_ticket_ctr, sizeof(unsigned)) != hipSuccess || hipMemsetAsync(p->x_ticket_ctr, 0, sizeof(unsigned), p->stream) != hipSuccess ||
+                hipStreamSynchronize(p->stream) != hipSuccess)
+                return fail(DFFT_EHIP, "dfft_plan_create: no ticket counter for the X pass");
+            // what the X pass will run on, until a launch has said so itself (dfft_plan_describe)
+            p->x_form = X_FORM_512_F64 | ((p->x_hints & FFT_HINT_LATE_WAIT) ? 0 : X_FORM_EARLY) | ((p->x_hints & FFT_HINT_STATIC_TILES) ? 0 : X_FORM_TICKET);
+        }
         const char* zl = getenv("DFFT_ZY_LAZY");
         p->zy_lazy = !(zl && *zl == '0');  // default on: t0 of 512^3 fp64 1.278 -> 1.163 ms (profiles/r03/experiments/variant_ab.log)
         const char* rf = getenv("DFFT_ZY_INV_ROWS_FIRST");
@@ -1153,6 +1175,17 @@ int dfft_execute(dfft_plan_t plan, unsigned exec_flags) {
     return DFFT_OK;
 }
 
+// x_variant= of dfft_plan_describe: the kernel form of the forward X pass.  The 512-point fp64 staged store reports what its last launch
+// selected (before the first one: what the plan's shape and switches select); every other kernel reports its switch, as before.
+static const char* x_variant_name(const dfft_plan_s* p) {
+    if (p->x_form & X_FORM_512_F64) {
+        const bool early = (p->x_form & X_FORM_EARLY) != 0;
+        if (p->x_form & X_FORM_TICKET) return early ? "ticket-early-wait" : "ticket-late-wait";
+        return early ? "static-early-wait" : "static-late-wait";
+    }
+    return (p->x_hints & FFT_HINT_HALF_PREFETCH) ? "half-prefetch" : ((p->x_hints & FFT_HINT_EARLY_WAIT) ? "early-wait" : "default");
+}
+
 int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
     if (!plan || !buf || len < 64) return fail(DFFT_EINVAL, "dfft_plan_describe: bad arguments");
     const dfft_plan_s* p = plan;
@@ -1183,7 +1216,7 @@ int dfft_plan_describe(dfft_plan_t plan, char* buf, int len) {
              (p->flags & DFFT_PLAN_NATURAL) ? "natural" : (fused ? "fused" : "unfused"),
              (p->zy_on && fused) ? "one-launch" : "two-launches-per-chunk", (p->zy_on && fused && p->zy_lazy) ? "-lazy" : "", nch, cp,
              (fused && p->wbuf && !p->exch) ? "padded-buffer" : "bufferDev1", p->rot_elems, p->part_planes, p->ycuts, (p->zy_on && fused && p->zy_part_done) ? 1 : 0, p->w_kept >= 0 ? 1 : 0,
-             (p->x_hints & FFT_HINT_HALF_PREFETCH) ? "half-prefetch" : ((p->x_hints & FFT_HINT_EARLY_WAIT) ? "early-wait" : "default"));
+             x_variant_name(p));
     for (int a = 0; a < 3; ++a) {  // Bluestein axes: "bluestein_axis0=n11/M24/fused"
         if (length_kind(p->N[a]) != 3 || p->bs.tables.empty()) continue;
         const size_t used = strlen(buf);
@@ -1291,6 +1324,7 @@ int dfft_plan_destroy(dfft_plan_t plan) {
     if (plan->rscratch) hipFree(plan->rscratch);
     if (plan->cbuf && (!plan->borrowed || plan->own_cbuf)) hipFree(plan->cbuf);
     if (plan->zy_ctl) hipFree(plan->zy_ctl);
+    if (plan->x_ticket_ctr) hipFree(plan->x_ticket_ctr);
     if (plan->zy_part_done) hipFree(plan->zy_part_done);
     if (plan->zy_err) hipHostFree(plan->zy_err);
     delete plan;

@@ -168,7 +168,18 @@ struct dfft_plan_s {
     unsigned                zy_sig_execs = 0;
     bool                    zy_lazy = false;           // lazy-publish form of the one-launch kernel (un-packed launches; DFFT_ZY_LAZY=0: eager)
     bool                    zy_inv_rows_first = true;  // backward single-GPU plans: inverse stage rows first (DFFT_ZY_INV_ROWS_FIRST=0: columns first)
-    int                     x_hints = 0;               // DFFT_X_VARIANT when the plan was created: FFT_HINT_HALF_PREFETCH / _EARLY_WAIT
+    int                     x_hints = 0;               // DFFT_X_VARIANT when the plan was created: FFT_HINT_HALF_PREFETCH / _EARLY_WAIT / _LATE_WAIT / _STATIC_TILES
+    // Forward fp64 plans with a 512-point X axis: the X pass hands its tiles out by ticket (TuneTransposedStoreTicket, dfft_fft_impl.h).
+    // x_ticket_ctr: the counter in device memory, zeroed once and never reset; x_ticket: its value when the next launch starts -- every
+    // whole-slab launch_x (executes and the probe launches of dfft_plan_tune alike) reads it and moves it on.  The host steps the base in
+    // the order it queues launches on the plan's stream: a plan executed from two streams or threads at once is outside the contract
+    // anyway, and here it would hand the tiles of one launch to the other.
+    // The base is a kernel ARGUMENT, fixed when the launch is queued: an execute captured into a hipGraph and replayed would replay a stale
+    // base -- every ticket would decode past the last tile and the output would be left unwritten.  The library has no graph path and
+    // plans must not be captured (the one-launch YZ stage steps its ticket and done bases the same way).
+    unsigned*               x_ticket_ctr = nullptr;
+    unsigned                x_ticket = 0;
+    int                     x_form = 0;  // X_FORM_* of the kernel the last whole-slab X pass ran on (before the first one: will run on); 0: another kernel
     int                     grid_x = 0, grid_y = 0, grid_z = 0;  // DFFT_X_GRID / DFFT_Y_GRID / DFFT_Z_GRID when the plan was created (0 = no cap)
     // Rows of the exchange buffers rotated by rot_elems elements per X plane (RotMap, dfft_kernels.h): P > 1 fused plans whose
     // received planes are a power-of-two distance apart.  0 = off.
