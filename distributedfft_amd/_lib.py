@@ -98,6 +98,10 @@ SIGNATURES = {
     "dfft_rfft1d_strided": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_rfft2d_batch": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_r2r1d_strided": (C.c_int, [_VP, _VP, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rconv1d": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rconv1d_fused_applies": (C.c_int, [_LL, _LL, C.c_int, C.c_int, C.c_int]),
+    "dfft_rconv1d_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, C.c_int]),
+    "dfft_rconv1d_length": (_LL, [_LL]),
     "dfft_scale": (C.c_int, [_VP, _LL, C.c_int, C.c_double, _VP]),
     "dfft_trim": (C.c_int, []),
     "dfft_boot_init": (C.c_int, []),

@@ -729,6 +729,52 @@ def r2rn(x, kinds, dims=None, out=None):
     return out
 
 
+def rconv1d_length(at_least: int) -> int:
+    """The smallest padded length m >= at_least that rconv1d accepts (dfft_rconv1d_length: m even, m/2 a single-pass length, so at most
+    8192); 0 if there is none."""
+    return int(L.load().dfft_rconv1d_length(int(at_least)))
+
+
+def rconv1d(x, H, m: Optional[int] = None, out=None):
+    """y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c], m)[:n] for every row of a contiguous float64 / float32
+    device tensor (..., channels, n) (dfft_rconv1d).  H is (channels, m//2 + 1) of the matching complex dtype, or of x's own dtype (a
+    real filter: half the filter bytes); m defaults to 2 * (H.shape[-1] - 1) and must be a length rconv1d_length returns.  m == n is
+    the circular convolution, m >= n + taps - 1 the head of the linear one.  Normalised: H == 1 gives y == x.  out=x runs in place."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    channels, n = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    assert H.is_cuda and H.device == x.device and H.is_contiguous() and H.dim() == 2 and H.dtype in (cdt, x.dtype), \
+        f"H must be a contiguous {cdt} or {x.dtype} tensor (channels, m//2 + 1) on {x.device}"
+    m = 2 * (int(H.shape[-1]) - 1) if m is None else int(m)
+    assert tuple(H.shape) == (channels, m // 2 + 1), f"H must have shape {(channels, m // 2 + 1)}, got {tuple(H.shape)}"
+    out = _check_out(x, out)
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rconv1d(x.data_ptr(), out.data_ptr(), H.data_ptr(), n, m, channels, batch, F64 if x.dtype == torch.float64 else F32,
+                                      FILTER_COMPLEX if H.dtype == cdt else FILTER_REAL, None), "dfft_rconv1d")
+        torch.cuda.synchronize()
+    return out
+
+
+def fftconv1d(x, k, out=None):
+    """numpy.convolve(x[..., c, :], k[c])[:n] for every row of a contiguous float64 / float32 device tensor (..., channels, n): the
+    causal "long convolution" with the real taps k (channels, taps), through rconv1d on m = rconv1d_length(n + taps - 1) with the
+    filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 8192."""
+    import torch
+    assert x.is_cuda and x.dim() >= 2 and k.is_cuda and k.dim() == 2 and k.dtype == x.dtype and k.device == x.device
+    channels, n, taps = int(x.shape[-2]), int(x.shape[-1]), int(k.shape[-1])
+    assert int(k.shape[0]) == channels, f"k must hold one row of taps per channel: ({channels}, taps), got {tuple(k.shape)}"
+    m = rconv1d_length(n + taps - 1)
+    if m == 0:
+        raise ValueError(f"fftconv1d: n + taps - 1 = {n + taps - 1} is beyond the longest padded length (8192)")
+    kp = torch.zeros((channels, m), dtype=k.dtype, device=k.device)
+    kp[:, :taps] = k
+    return rconv1d(x, rfft1d(kp), m, out=out)
+
+
 def rfft2d_batch(x, out=None):
     """numpy.fft.rfft2 of every (n1, n2) plane of a contiguous float64 / float32 device tensor [..., n1, n2] -> complex128 / complex64
     [..., n1, n2//2 + 1] (dfft_rfft2d_batch): n2 of any real form, n1 of any length kind.  Unnormalised, out of place."""

@@ -1,11 +1,12 @@
 // dfft_batch.cpp -- the plan-less batched entry points: complex and real 1-D transforms along rows or a strided axis, batched 2-D
-// transforms, real-to-real transforms, dfft_scale and dfft_trim.
+// transforms, real-to-real transforms, the 1-D real FFT convolution, dfft_scale and dfft_trim.
 #include <map>
 #include <mutex>
 #include <tuple>
 
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
+#include "dfft_rconv.h"
 #include "dfft_real.h"
 #include "dfft_real_cols.h"
 #include "dfft_real_pair.h"
@@ -466,6 +467,43 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_r2r1d_strided: cannot allocate the scratch buffer");
     return r2r(L, *w, fused_on, t.get(), bs_fused, lease.get(), need, st);
+}
+
+// Batched 1-D real FFT convolution of the rows of reals [batch][channels][n] with the spectra h [channels][m/2 + 1] (dfft_rconv.hip)
+int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long long m, long long channels, long long batch, int dtype, int filter_kind,
+                 void* stream) {
+    if (!in || !out || !h || n < 1 || m < 1 || channels < 1 || batch < 1 || m < n || !valid_dtype(dtype) ||
+        (filter_kind != DFFT_FILTER_COMPLEX && filter_kind != DFFT_FILTER_REAL))
+        return fail(DFFT_EINVAL, "dfft_rconv1d: bad arguments");
+    if (real_form(m) != 1)
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d: m = " + std::to_string(m) + " -- the padded length must be of dfft_real_form 1 (even, m/2 a single-pass "
+                                       "length, so at most 8192; dfft_rconv1d_length); longer sequences are not built");
+    if (channels >= (1ll << 31) || batch >= (1ll << 31) || batch * channels >= (1ll << 31))
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d: batch * channels = 2^31 or more rows: split the batch");
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const uintptr_t bytes = (uintptr_t)batch * channels * n * rs;
+    if (partly_overlap(in, out, bytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d: in and out overlap partly (the convolution runs out of place or exactly in place)");
+    if (ranges_overlap(h, (uintptr_t)channels * (m / 2 + 1) * (filter_kind == DFFT_FILTER_REAL ? rs : cs), out, bytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d: the filter overlaps out");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d: no HIP device visible (no CPU fallback)");
+    const hipStream_t st = (hipStream_t)stream;
+    const bool        fused_on = rconv_fused_env();
+    RconvLaunch       L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.filter_kind = filter_kind;
+    L.n = n;
+    L.m = m;
+    L.channels = channels;
+    L.batch = batch;
+    L.in = in;
+    L.out = out;
+    L.h = h;
+    const size_t need = rconv_scratch_bytes(L, fused_on);
+    ScratchLease lease;
+    if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d: cannot allocate the scratch buffer");
+    return rconv(L, fused_on, lease.get(), need, st);
 }
 
 // `batch` planes of [n1][n2] reals <-> [n1][n2/2 + 1] bins, in groups of planes sized for the 256 MiB Infinity Cache (dfft_fft2d_batch's

@@ -9,6 +9,7 @@
 
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
+#include "dfft_rconv.h"
 #include "dfft_real.h"
 #include "dfft_real_cols.h"
 
@@ -177,6 +178,11 @@ int dfft_r2r_fused_applies(long long n, long long s, int dtype, int kind, int ve
     if (!valid_dtype(dtype) || kind < DFFT_R2R_DCT2 || kind > DFFT_R2R_DST3 || n < 1 || s < 1) return 0;
     return r2r_fused_env() && r2r_fused(n, s, dtype, kind, vec != 0);
 }
+int dfft_rconv1d_fused_applies(long long n, long long m, int dtype, int filter_kind, int vec) {
+    if (!valid_dtype(dtype)) return 0;
+    return rconv_fused_env() && rconv_fused(n, m, dtype, filter_kind, vec != 0);
+}
+long long dfft_rconv1d_length(long long at_least) { return rconv_length(at_least); }
 int dfft_conv_fused_applies(int dtype, long long n0, long long rows, long long ncols, long long plane, long long pitch, int rot, const void* in,
                             const void* out) {
     if (!valid_dtype(dtype) || n0 < 1 || n0 > 4096 || rows < 1 || ncols < 1 || plane < 1 || pitch < 1 || rot < 0) return 0;
@@ -249,6 +255,20 @@ unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, lo
     L.batch = batch;
     L.in = L.out = (void*)(uintptr_t)(vec ? 64 : elem_bytes(dtype) / 2);  // r2r_vec looks at the alignment only
     return r2r_scratch_bytes(L, r2r_fused_env(), lk == 3 ? &T : nullptr, bluestein_fused_env());
+}
+
+unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || channels >= (1ll << 31) || batch >= (1ll << 31) ||
+        batch * channels >= (1ll << 31) || real_form(m) != 1)
+        return 0;
+    RconvLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.n = n;
+    L.m = m;
+    L.channels = channels;
+    L.batch = batch;
+    return rconv_scratch_bytes(L, rconv_fused_env());  // (the route depends on neither the filter kind nor the alignment)
 }
 
 int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,

@@ -448,6 +448,33 @@ int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long
 #define DFFT_R2R_DST3 3
 int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int kind, void* stream);
 
+/* Batched 1-D real FFT convolution: every contiguous row of reals in [batch][channels][n] filtered by its channel's spectrum
+ * h [channels][m/2 + 1],
+ *     out[b, c, :] = numpy.fft.irfft(numpy.fft.rfft(in[b, c, :], m) * h[c, :], m)[:n]        (row r uses filter row r % channels)
+ * normalised like the spectral-filter plans (h == 1 gives out == in).  m == n is the circular convolution; m >= n + taps - 1 gives the
+ * first n samples of the linear convolution with a kernel of `taps` taps (h = rfft of the zero-padded taps).  Like dfft_rfft1d backward,
+ * the imaginary parts of the products at bins 0 and m/2 are ignored.  dtype DFFT_F64 (double) or DFFT_F32 (float); filter_kind
+ * DFFT_FILTER_COMPLEX (h holds elements of the complex type) or DFFT_FILTER_REAL (elements of the real type, half the filter bytes).
+ * Accepted: 1 <= n <= m, dfft_real_form(m) == 1 (m even, m/2 a single-pass length, so m <= 8192; dfft_rconv1d_length(a) is the smallest
+ * such m >= a, 0 if none), channels >= 1, batch >= 1, batch * channels < 2^31 rows (row bases are 64-bit); any element-aligned pointers.
+ * Longer sequences (overlap-save, four-step halves) are NOT built.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the
+ * batch); NULL pointers, sizes below 1, m < n, a bad dtype or filter kind, in and out overlapping partly, h overlapping out:
+ * DFFT_EINVAL -- all decided before the device is queried.  out == in (exactly) is allowed; with out != in, `in` is never written; h is
+ * never written; nothing outside the batch * channels * n reals of out is written.
+ * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_rconv.hip) that loads the n reals of a row, runs the forward m/2-point
+ * transform, splits, multiplies, merges and runs the inverse in registers and LDS, and stores n reals: the row is read once and written
+ * once, the zero padding and the spectrum never exist in memory.  Every other accepted m, the few (m/2, dtype) whose kernels would spill
+ * or measured slower, and every m under DFFT_RCONV_FUSED=0 (read per call) run pad -> R2C rows -> multiply -> C2R rows -> truncate in
+ * batch chunks of at most max(256 MiB, one row's) scratch from the per-(device, stream) buffer dfft_trim frees; a call allocates nothing
+ * once that is warm.  dfft_rconv1d_fused_applies tells the route (vec: n even and both pointers aligned to two reals -- the one-launch
+ * kernel then moves two reals per access; the route itself does not depend on it), dfft_rconv1d_scratch_bytes the lease (0 for the one
+ * launch, and for a call that is refused).  Both are host arithmetic. */
+int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long long m, long long channels, long long batch, int dtype, int filter_kind,
+                 void* stream);
+int dfft_rconv1d_fused_applies(long long n, long long m, int dtype, int filter_kind, int vec);
+unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
+long long dfft_rconv1d_length(long long at_least);
+
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
  * `batch` planes of [n1][n2] complex elements (n2 contiguous), each transformed along both axes, in place (out == in) or out
