@@ -775,6 +775,75 @@ def fftconv1d(x, k, out=None):
     return rconv1d(x, rfft1d(kp), m, out=out)
 
 
+def rconv1d_os_block(taps: int, n_out: int, dtype) -> tuple:
+    """(m, discard) that dfft_rconv1d_os_block chooses for `taps` taps and n_out results per row of a float64 / float32 tensor (dtype a
+    torch dtype or F64 / F32): discard = taps - 1 rounded up to even, m the accepted block length with the smallest estimated time.
+    ValueError beyond 8191 taps."""
+    import ctypes as C
+    if not isinstance(dtype, int):
+        import torch
+        assert dtype in (torch.float64, torch.float32)
+        dtype = F64 if dtype == torch.float64 else F32
+    m, d = C.c_longlong(0), C.c_longlong(0)
+    rc = L.load().dfft_rconv1d_os_block(int(taps), int(n_out), int(dtype), C.byref(m), C.byref(d))
+    if rc == L.EUNSUPPORTED:
+        raise ValueError(f"rconv1d_os_block: {taps} taps are beyond the longest block (8191 taps)")
+    L.check(rc, "dfft_rconv1d_os_block")
+    return int(m.value), int(d.value)
+
+
+def rconv1d_os(x, H, m: Optional[int] = None, discard: int = 0, n_out: Optional[int] = None, out=None):
+    """Overlap-save rconv1d for rows of any length (dfft_rconv1d_os): x (..., channels, n) -> (..., channels, n_out), in blocks of m reals
+    that advance by S = m - discard; block b of a row is irfft(rfft(x[b S - discard : b S - discard + m], m) * H[c], m) with zeros outside
+    the row, and its results from `discard` on become y[b S : b S + S].  H as in rconv1d, m defaults to 2 * (H.shape[-1] - 1), n_out to
+    n (at most n + discard).  With H the spectrum of taps <= discard + 1 taps this is numpy.convolve(x, k)[:n_out].  Out of place only."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    channels, n = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    assert H.is_cuda and H.device == x.device and H.is_contiguous() and H.dim() == 2 and H.dtype in (cdt, x.dtype), \
+        f"H must be a contiguous {cdt} or {x.dtype} tensor (channels, m//2 + 1) on {x.device}"
+    m = 2 * (int(H.shape[-1]) - 1) if m is None else int(m)
+    assert tuple(H.shape) == (channels, m // 2 + 1), f"H must have shape {(channels, m // 2 + 1)}, got {tuple(H.shape)}"
+    n_out = n if n_out is None else int(n_out)
+    shape = tuple(x.shape[:-1]) + (n_out,)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    assert out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == x.dtype and tuple(out.shape) == shape, \
+        f"out must be a contiguous {x.dtype} tensor of shape {shape} on {x.device}"
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rconv1d_os(x.data_ptr(), out.data_ptr(), H.data_ptr(), n, n_out, m, int(discard), channels, batch,
+                                         F64 if x.dtype == torch.float64 else F32, FILTER_COMPLEX if H.dtype == cdt else FILTER_REAL, None), "dfft_rconv1d_os")
+        torch.cuda.synchronize()
+    return out
+
+
+def fftfilt1d(x, k, mode: str = "head", m: Optional[int] = None, out=None):
+    """numpy.convolve(x[..., c, :], k[c]) for every row of a contiguous float64 / float32 device tensor (..., channels, n) of ANY length
+    with the real taps k (channels, taps), taps <= 8191: its first n samples (mode "head", the causal filter) or all n + taps - 1
+    (mode "full").  Overlap-save through rconv1d_os: the block (m, discard) comes from rconv1d_os_block unless m is given (then discard
+    = taps - 1 rounded up to even, which m must exceed); the filter spectrum is rfft1d of the taps zero-padded to m."""
+    import torch
+    assert x.is_cuda and x.dim() >= 2 and k.is_cuda and k.dim() == 2 and k.dtype == x.dtype and k.device == x.device
+    if mode not in ("head", "full"):
+        raise ValueError(f"mode must be 'head' or 'full', got {mode!r}")
+    channels, n, taps = int(x.shape[-2]), int(x.shape[-1]), int(k.shape[-1])
+    assert int(k.shape[0]) == channels, f"k must hold one row of taps per channel: ({channels}, taps), got {tuple(k.shape)}"
+    n_out = n if mode == "head" else n + taps - 1
+    if m is None:
+        m, discard = rconv1d_os_block(taps, n_out, x.dtype)
+    else:
+        m, discard = int(m), taps - 1 + ((taps - 1) & 1)
+        if m <= discard:
+            raise ValueError(f"fftfilt1d: a block of m = {m} leaves no room behind the {discard} samples that {taps} taps discard")
+    kp = torch.zeros((channels, m), dtype=k.dtype, device=k.device)
+    kp[:, :taps] = k
+    return rconv1d_os(x, rfft1d(kp), m, discard, n_out, out=out)
+
+
 def rfft2d_batch(x, out=None):
     """numpy.fft.rfft2 of every (n1, n2) plane of a contiguous float64 / float32 device tensor [..., n1, n2] -> complex128 / complex64
     [..., n1, n2//2 + 1] (dfft_rfft2d_batch): n2 of any real form, n1 of any length kind.  Unnormalised, out of place."""

@@ -106,6 +106,10 @@ def units():
     # batched 1-D real FFT convolution: the fused kernels of the tuned half-lengths of each group, plus the dispatcher and the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_rconv.hip", OBJ / f"dfft_rconv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # overlap-save 1-D real FFT convolution: the block kernels of the tuned half-lengths of each group, plus the dispatcher, the block
+    # chooser and the composed form
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_osconv.hip", OBJ / f"dfft_osconv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))

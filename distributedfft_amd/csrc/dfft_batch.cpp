@@ -1,9 +1,10 @@
 // dfft_batch.cpp -- the plan-less batched entry points: complex and real 1-D transforms along rows or a strided axis, batched 2-D
-// transforms, real-to-real transforms, the 1-D real FFT convolution, dfft_scale and dfft_trim.
+// transforms, real-to-real transforms, the 1-D real FFT convolution and its overlap-save form, dfft_scale and dfft_trim.
 #include <map>
 #include <mutex>
 #include <tuple>
 
+#include "dfft_osconv.h"
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
 #include "dfft_rconv.h"
@@ -504,6 +505,47 @@ int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long lon
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d: cannot allocate the scratch buffer");
     return rconv(L, fused_on, lease.get(), need, st);
+}
+
+// Overlap-save 1-D real FFT convolution: rows of reals [batch][channels][n] of any length, filtered in blocks of m reals of which the
+// first `discard` results are dropped, into [batch][channels][n_out] (dfft_osconv.hip)
+int dfft_rconv1d_os(const void* in, void* out, const void* h, long long n, long long n_out, long long m, long long discard, long long channels,
+                    long long batch, int dtype, int filter_kind, void* stream) {
+    if (!in || !out || !h || n < 1 || n_out < 1 || m < 1 || discard < 0 || discard > m - 1 || channels < 1 || batch < 1 || n_out - discard > n ||
+        !valid_dtype(dtype) || (filter_kind != DFFT_FILTER_COMPLEX && filter_kind != DFFT_FILTER_REAL))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_os: bad arguments");
+    if (real_form(m) != 1)
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d_os: m = " + std::to_string(m) + " -- the block length must be of dfft_real_form 1 (even, m/2 a single-pass "
+                                       "length, so at most 8192; dfft_rconv1d_length); four-step and Bluestein halves are not built");
+    const long long nb = osconv_blocks(n_out, m, discard);
+    if (channels >= (1ll << 31) || batch >= (1ll << 31) || batch * channels >= (1ll << 31) || nb > ((1ll << 31) - 1) / (batch * channels))
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d_os: batch * channels * blocks per row = 2^31 or more items: split the batch");
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const uintptr_t ibytes = (uintptr_t)batch * channels * n * rs, obytes = (uintptr_t)batch * channels * n_out * rs;
+    if (ranges_overlap(in, ibytes, out, obytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_os: in and out overlap (blocks read what their neighbours write: there is no in-place form)");
+    if (ranges_overlap(h, (uintptr_t)channels * (m / 2 + 1) * (filter_kind == DFFT_FILTER_REAL ? rs : cs), out, obytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_os: the filter overlaps out");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d_os: no HIP device visible (no CPU fallback)");
+    const hipStream_t st = (hipStream_t)stream;
+    const bool        fused_on = rconv_fused_env();
+    OsconvLaunch      L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.filter_kind = filter_kind;
+    L.n = n;
+    L.n_out = n_out;
+    L.m = m;
+    L.discard = discard;
+    L.channels = channels;
+    L.batch = batch;
+    L.in = in;
+    L.out = out;
+    L.h = h;
+    const size_t need = osconv_scratch_bytes(L, fused_on);
+    ScratchLease lease;
+    if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d_os: cannot allocate the scratch buffer");
+    return osconv(L, fused_on, lease.get(), need, st);
 }
 
 // `batch` planes of [n1][n2] reals <-> [n1][n2/2 + 1] bins, in groups of planes sized for the 256 MiB Infinity Cache (dfft_fft2d_batch's

@@ -9,6 +9,7 @@
 
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
+#include "dfft_osconv.h"
 #include "dfft_rconv.h"
 #include "dfft_real.h"
 #include "dfft_real_cols.h"
@@ -183,6 +184,14 @@ int dfft_rconv1d_fused_applies(long long n, long long m, int dtype, int filter_k
     return rconv_fused_env() && rconv_fused(n, m, dtype, filter_kind, vec != 0);
 }
 long long dfft_rconv1d_length(long long at_least) { return rconv_length(at_least); }
+int dfft_rconv1d_os_fused_applies(long long m, int dtype) { return valid_dtype(dtype) && rconv_fused_env() && osconv_fused(m, dtype); }
+int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long* m, long long* discard) {
+    if (!m || !discard || taps < 1 || n_out < 1 || !valid_dtype(dtype)) return fail(DFFT_EINVAL, "dfft_rconv1d_os_block: bad arguments");
+    if (!osconv_block(taps, n_out, dtype, m, discard))
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d_os_block: taps = " + std::to_string(taps) + " -- no block length leaves room for more than 8191 taps "
+                                       "(four-step and Bluestein halves are not built)");
+    return DFFT_OK;
+}
 int dfft_conv_fused_applies(int dtype, long long n0, long long rows, long long ncols, long long plane, long long pitch, int rot, const void* in,
                             const void* out) {
     if (!valid_dtype(dtype) || n0 < 1 || n0 > 4096 || rows < 1 || ncols < 1 || plane < 1 || pitch < 1 || rot < 0) return 0;
@@ -269,6 +278,20 @@ unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long lon
     L.channels = channels;
     L.batch = batch;
     return rconv_scratch_bytes(L, rconv_fused_env());  // (the route depends on neither the filter kind nor the alignment)
+}
+
+unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, long long discard, long long channels, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || n_out < 1 || discard < 0 || m <= discard || real_form(m) != 1) return 0;
+    OsconvLaunch L;
+    std::memset(&L, 0, sizeof(L));
+    L.dtype = dtype;
+    L.n = n_out;  // the lease does not depend on n: any n the entry point accepts with this n_out
+    L.n_out = n_out;
+    L.m = m;
+    L.discard = discard;
+    L.channels = channels;
+    L.batch = batch;
+    return osconv_scratch_bytes(L, rconv_fused_env());  // (0 for refused sizes; the route depends on neither the filter kind nor the alignment)
 }
 
 int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,

@@ -1,7 +1,7 @@
 // dfft_rconv.hip -- batched 1-D real FFT convolution: every row of reals [batch][channels][n] filtered by its channel's spectrum,
 //     y[b, c, :] = irfft(rfft(x[b, c, :], m) * H[c, :], m)[:n],        H [channels][m/2 + 1],  n <= m,  m = 2 M,
 // for M a single-pass length (real form 1, m <= 8192).  m == n is the circular convolution, m >= n + taps - 1 the first n samples of
-// the linear one.  Longer sequences (overlap-save, four-step halves) are not built.
+// the linear one.  Longer sequences run block by block through dfft_osconv.hip (overlap-save); four-step and Bluestein halves are not built.
 //
 // Fused form, rconv_rows_kernel (M with a tuned plan of dfft_plans.h): ONE launch that reads a row once and writes it once.  The row
 // is loaded as the M complex values z[j] = x[2j] + i x[2j+1], zeros beyond n -- the padded part of the row exists in registers only --
@@ -33,6 +33,7 @@
 #include "dfft_plans.h"
 #include "dfft_real.h"
 #include "dfft_rconv.h"
+#include "dfft_rconv_impl.h"
 
 #include <algorithm>
 #include <atomic>
@@ -73,34 +74,8 @@ template <int M> struct RconvInst<true, M> {
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
 
-// Geometry: RealGeom of dfft_real.hip (one M-point FFT per thread group, about 256 threads per workgroup, twiddles where KernelGeom
-// puts them; the tile of a group holds the M bins of the pairing step in natural order).
-template <class V, class P> struct RconvGeom {
-    static constexpr int G = ConstMax1<256 / P::T>::value;
-    using KG = KernelGeom<V, P, 1, G, TuneDefault>;
-    static constexpr int M = P::N;
-    static constexpr int SPLIT = (KG::PAD ? M + M / 8 : M) + 1;
-    static constexpr int EXR = ((KG::LDS_ELEMS > SPLIT ? KG::LDS_ELEMS : SPLIT) + 1) / 2 * 2;
-    static constexpr size_t LDS_BYTES = (size_t)EXR * G * sizeof(V) + KG::TW_BYTES;
-    // the pairing twiddles W^k of a thread's E bins do not depend on the row: kept in registers where they are few
-    static constexpr bool TWH_REG = P::E * (int)sizeof(V) / 4 <= 32;
-};
-
-// filter element times 1 / (2 m) (the halves of Xe, Xo are folded in), and its product with a bin
-template <class V, bool HREAL> struct RconvFilter;
-template <class V> struct RconvFilter<V, false> {
-    using T = V;
-    using RT = typename real_of<V>::type;
-    static __device__ __forceinline__ V mul(V a, V h, RT sc) { return cmul(a, V{h.x * sc, h.y * sc}); }
-};
-template <class V> struct RconvFilter<V, true> {
-    using RT = typename real_of<V>::type;
-    using T = RT;
-    static __device__ __forceinline__ V mul(V a, RT h, RT sc) {
-        const RT s = h * sc;
-        return V{a.x * s, a.y * s};
-    }
-};
+// RconvGeom (the geometry) and RconvFilter (a filter element and its product with a bin): dfft_rconv_impl.h, shared with the overlap-save
+// kernel of dfft_osconv.hip, which repeats the pairing / multiply / merge step below (as a shared function it changed this kernel's registers).
 
 template <class V, class P, bool HREAL, bool VEC>
 __global__ void __attribute__((amdgpu_flat_work_group_size(1, RconvGeom<V, P>::KG::THREADS)))

@@ -457,7 +457,7 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
  * DFFT_FILTER_COMPLEX (h holds elements of the complex type) or DFFT_FILTER_REAL (elements of the real type, half the filter bytes).
  * Accepted: 1 <= n <= m, dfft_real_form(m) == 1 (m even, m/2 a single-pass length, so m <= 8192; dfft_rconv1d_length(a) is the smallest
  * such m >= a, 0 if none), channels >= 1, batch >= 1, batch * channels < 2^31 rows (row bases are 64-bit); any element-aligned pointers.
- * Longer sequences (overlap-save, four-step halves) are NOT built.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the
+ * Longer sequences run block by block through dfft_rconv1d_os below (overlap-save); four-step and Bluestein halves are NOT built.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the
  * batch); NULL pointers, sizes below 1, m < n, a bad dtype or filter kind, in and out overlapping partly, h overlapping out:
  * DFFT_EINVAL -- all decided before the device is queried.  out == in (exactly) is allowed; with out != in, `in` is never written; h is
  * never written; nothing outside the batch * channels * n reals of out is written.
@@ -474,6 +474,34 @@ int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long lon
 int dfft_rconv1d_fused_applies(long long n, long long m, int dtype, int filter_kind, int vec);
 unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
 long long dfft_rconv1d_length(long long at_least);
+
+/* Overlap-save form of dfft_rconv1d for rows of ANY length: in [batch][channels][n], out [batch][channels][n_out], h [channels][m/2 + 1]
+ * as above.  m is the block length and `discard` (d) the samples dropped per block; with S = m - d and nb = ceil(n_out / S), block b of
+ * row r is
+ *     xb[i]           = in[r, b S - d + i]  if 0 <= b S - d + i < n, else 0                        (0 <= i < m)
+ *     cb              = numpy.fft.irfft(numpy.fft.rfft(xb, m) * h[r % channels], m)                (h == 1 gives cb == xb)
+ *     out[r, b S + j] = cb[d + j]                                                                  (0 <= j < S, b S + j < n_out)
+ * With h = rfft of `taps` <= d + 1 taps zero-padded to m, out[r] = numpy.convolve(in[r], k)[:n_out]: n_out = n is the causal head,
+ * n_out = n + taps - 1 the full convolution.  The imaginary parts of the products at bins 0 and m/2 are ignored.
+ * Accepted: n >= 1, 1 <= n_out <= n + discard, dfft_real_form(m) == 1, 0 <= discard <= m - 1, channels, batch >= 1, batch * channels * nb
+ * < 2^31 block items (element offsets are 64-bit); any element-aligned pointers.  NULL pointers, sizes out of range, a bad dtype or
+ * filter kind, in and out overlapping AT ALL (blocks read what their neighbours write: there is no in-place form), h overlapping out:
+ * DFFT_EINVAL; every other m, and 2^31 or more items: DFFT_EUNSUPPORTED -- all decided before the device is queried.  in and h are never
+ * written; nothing outside the batch * channels * n_out reals of out is written.
+ * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_osconv.hip): the kernel of dfft_rconv1d run per (row, block) item with the
+ * load base, the store window and the filter row taken from the item -- the padded blocks, the dropped samples and the spectrum never
+ * exist in memory; two reals per access where n, n_out and discard are even and both pointers are aligned to two reals.  Every other
+ * accepted m, the (m/2, dtype) dfft_rconv1d routes, and every m under DFFT_RCONV_FUSED=0 (read per call) run gather -> R2C rows ->
+ * multiply -> C2R rows -> scatter in chunks of items of at most max(256 MiB, one item's) scratch from the buffer dfft_trim frees; a call
+ * allocates nothing once that is warm.  dfft_rconv1d_os_fused_applies tells the route, dfft_rconv1d_os_scratch_bytes the lease (0 for the
+ * one launch, and for sizes that are refused).  dfft_rconv1d_os_block chooses the block for `taps` taps and n_out results per row:
+ * discard = taps - 1 rounded up to even, and the accepted m > discard with the smallest ceil(n_out / (m - discard)) * t(m) over a table of
+ * per-block times (one block where one fits); DFFT_EUNSUPPORTED for taps > 8191.  All three are host arithmetic. */
+int dfft_rconv1d_os(const void* in, void* out, const void* h, long long n, long long n_out, long long m, long long discard, long long channels,
+                    long long batch, int dtype, int filter_kind, void* stream);
+int dfft_rconv1d_os_fused_applies(long long m, int dtype);
+unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, long long discard, long long channels, long long batch, int dtype);
+int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long* m, long long* discard);
 
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
