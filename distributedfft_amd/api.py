@@ -844,6 +844,140 @@ def fftfilt1d(x, k, mode: str = "head", m: Optional[int] = None, out=None):
     return rconv1d_os(x, rfft1d(kp), m, discard, n_out, out=out)
 
 
+STFT_PAD_ZERO, STFT_PAD_REFLECT = 0, 1
+STFT_OUT_COMPLEX, STFT_OUT_POWER = 0, 1
+
+
+def stft_frames(n: int, n_fft: int, hop: int, pad: int) -> int:
+    """Frames that rows of n samples give (dfft_stft1d_frames): 1 + (n + 2 pad - n_fft) // hop where n + 2 pad >= n_fft, else 0."""
+    return int(L.load().dfft_stft1d_frames(int(n), int(n_fft), int(hop), int(pad)))
+
+
+def _stft_window(window, n_fft, win_length, dtype, device):
+    """The window of n_fft reals the library takes: ones (window None), or `window` of win_length values centred and zero-padded."""
+    import torch
+    win_length = n_fft if win_length is None else int(win_length)
+    if not 1 <= win_length <= n_fft:
+        raise ValueError(f"win_length must be in [1, n_fft = {n_fft}], got {win_length}")
+    if window is None:
+        w = torch.ones(win_length, dtype=dtype, device=device)
+    else:
+        if window.dim() != 1 or int(window.shape[0]) != win_length:
+            raise ValueError(f"window must be a 1-D tensor of win_length = {win_length} values, got shape {tuple(window.shape)}")
+        w = window.to(device=device, dtype=dtype)
+    if win_length < n_fft:
+        left = (n_fft - win_length) // 2
+        w = torch.nn.functional.pad(w, (left, n_fft - win_length - left))
+    return w.contiguous()
+
+
+def stft(x, n_fft: int, hop_length: Optional[int] = None, window=None, center: bool = True, pad_mode: str = "reflect", normalized: bool = False,
+         win_length: Optional[int] = None, frames_last: bool = True, power=None, out=None):
+    """torch.stft(x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided=True, return_complex=True) of a
+    contiguous float64 / float32 device tensor (..., n) (dfft_stft1d): frames of n_fft samples that advance by hop_length (default
+    n_fft // 4), each multiplied by the window (None: rectangular; win_length < n_fft: centred and zero-padded) and transformed.
+    center pads n_fft // 2 samples on both sides, mirrored (pad_mode "reflect", which needs n_fft // 2 < n) or zero ("constant").
+    The storage is (..., frames, bins) contiguous, bins = n_fft // 2 + 1; frames_last=True returns its (..., bins, frames) transposed view
+    (torch's order), False the storage itself.  power=2 returns the real power spectrogram |X|^2 (half the bytes) instead of X.
+    n_fft must be of real form 1 (even, n_fft // 2 a single-pass length, at most 8192).  `out`: the (..., frames, bins) storage.  No
+    autograd."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    if power not in (None, 2, 2.0):
+        raise ValueError(f"power must be None (complex bins) or 2 (the power spectrogram), got {power!r}")
+    n_fft, n = int(n_fft), int(x.shape[-1])
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if hop < 1:
+        raise ValueError(f"hop_length must be at least 1, got {hop}")
+    pad = n_fft // 2 if center else 0
+    if center and pad_mode == "reflect" and pad >= n:
+        raise ValueError(f"reflect padding of {pad} samples needs rows longer than that, got n = {n}")
+    frames = stft_frames(n, n_fft, hop, pad)
+    if frames < 1:
+        raise ValueError(f"rows of {n} samples{' (padded)' if center else ''} are shorter than one frame of n_fft = {n_fft}")
+    w = _stft_window(window, n_fft, win_length, x.dtype, x.device)
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    odt = x.dtype if power is not None else cdt
+    shape = tuple(x.shape[:-1]) + (frames, n_fft // 2 + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    assert out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == odt and tuple(out.shape) == shape, \
+        f"out must be a contiguous {odt} tensor of shape {shape} on {x.device}"
+    rows = math.prod(int(v) for v in x.shape[:-1])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_stft1d(x.data_ptr(), out.data_ptr(), w.data_ptr(), n, n_fft, hop, pad, frames, rows, F64 if x.dtype == torch.float64 else F32,
+                                     STFT_PAD_REFLECT if (center and pad_mode == "reflect") else STFT_PAD_ZERO,
+                                     STFT_OUT_POWER if power is not None else STFT_OUT_COMPLEX, n_fft ** -0.5 if normalized else 1.0, None), "dfft_stft1d")
+        torch.cuda.synchronize()
+    return out.transpose(-1, -2) if frames_last else out
+
+
+def istft_envelope(window, n_fft: int, hop: int, frames: int):
+    """sum_f win^2[s - f hop] for s in [0, (frames - 1) hop + n_fft): the overlap-add of the squared window, in float64 on its device."""
+    import torch
+    shifts = -(-n_fft // hop)                                      # frames that reach one sample, at most
+    w2 = torch.nn.functional.pad(window.to(torch.float64) ** 2, (0, shifts * hop - n_fft))
+    env = torch.zeros((frames - 1 + shifts) * hop, dtype=torch.float64, device=window.device)
+    for j in range(shifts):                                        # hop values of win^2 at a time, laid end to end once per frame: O(n) each
+        env[j * hop:(j + frames) * hop] += w2[j * hop:(j + 1) * hop].repeat(frames)
+    return env[:(frames - 1) * hop + n_fft]
+
+
+def istft(X, n_fft: int, hop_length: Optional[int] = None, window=None, center: bool = True, normalized: bool = False, win_length: Optional[int] = None,
+          length: Optional[int] = None, frames_last: bool = True, out=None):
+    """torch.istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided=True, length) of a complex128 / complex64
+    device tensor (..., bins, frames) (frames_last=True, torch's order) or (..., frames, bins) (False), bins = n_fft // 2 + 1
+    (dfft_istft1d): the least-squares overlap-add sum_f win irfft(X_f) / sum_f win^2.  center drops the n_fft // 2 padded samples in
+    front; the result holds `length` samples (default: (frames - 1) hop, or + n_fft without center; beyond the last frame: zeros).
+    ValueError where the window envelope sum_f win^2 falls to 1e-11 or below inside the result (torch's NOLA check).  A (..., bins, frames)
+    tensor that is not the transposed view of contiguous (..., frames, bins) storage is copied into that layout.  No autograd."""
+    import math
+
+    import torch
+    assert X.is_cuda and X.dim() >= 2 and X.dtype in (torch.complex128, torch.complex64) and X.numel() > 0
+    Xs = X.transpose(-1, -2) if frames_last else X
+    if not Xs.is_contiguous():
+        Xs = Xs.contiguous()
+    n_fft = int(n_fft)
+    frames, bins = int(Xs.shape[-2]), int(Xs.shape[-1])
+    if bins != n_fft // 2 + 1:
+        raise ValueError(f"X must hold n_fft // 2 + 1 = {n_fft // 2 + 1} bins, got {bins}")
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if hop < 1:
+        raise ValueError(f"hop_length must be at least 1, got {hop}")
+    rdt = torch.float64 if X.dtype == torch.complex128 else torch.float32
+    w = _stft_window(window, n_fft, win_length, rdt, X.device)
+    pad = n_fft // 2 if center else 0
+    most = (frames - 1) * hop + n_fft - pad                       # samples the frames reach behind the padding in front
+    n = (most - pad if center else most) if length is None else int(length)
+    if n < 1:
+        raise ValueError(f"the result would hold {n} samples")
+    have = min(n, most)
+    env = istft_envelope(w, n_fft, hop, frames)[pad:pad + have]
+    if float(env.abs().min()) <= 1e-11:
+        raise ValueError("istft: the window overlap-add envelope falls to 1e-11 or below (NOLA): these frames do not determine the signal")
+    inv_env = ((n_fft ** 0.5 if normalized else 1.0) / env).to(rdt).contiguous()
+    shape = tuple(Xs.shape[:-2]) + (n,)
+    if out is None:
+        out = torch.empty(shape, dtype=rdt, device=X.device)
+    assert out.is_cuda and out.device == X.device and out.is_contiguous() and out.dtype == rdt and tuple(out.shape) == shape, \
+        f"out must be a contiguous {rdt} tensor of shape {shape} on {X.device}"
+    rows = math.prod(int(v) for v in Xs.shape[:-2])
+    dst = out if have == n else torch.empty(tuple(Xs.shape[:-2]) + (have,), dtype=rdt, device=X.device)
+    with torch.cuda.device(X.device):
+        L.check(L.load().dfft_istft1d(Xs.data_ptr(), dst.data_ptr(), w.data_ptr(), inv_env.data_ptr(), have, n_fft, hop, pad, frames, rows,
+                                      F64 if rdt == torch.float64 else F32, None), "dfft_istft1d")
+        torch.cuda.synchronize()
+    if dst is not out:
+        out[..., :have] = dst
+        out[..., have:] = 0
+    return out
+
+
 def rfft2d_batch(x, out=None):
     """numpy.fft.rfft2 of every (n1, n2) plane of a contiguous float64 / float32 device tensor [..., n1, n2] -> complex128 / complex64
     [..., n1, n2//2 + 1] (dfft_rfft2d_batch): n2 of any real form, n1 of any length kind.  Unnormalised, out of place."""

@@ -503,6 +503,51 @@ int dfft_rconv1d_os_fused_applies(long long m, int dtype);
 unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, long long discard, long long channels, long long batch, int dtype);
 int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long* m, long long* discard);
 
+/* Batched short-time Fourier transform and its inverse (unnormalised, numpy conventions).  Rows of reals in [rows][n], a window win [m]
+ * of reals, frames of m reals that advance by hop >= 1, 0 <= pad < m samples of padding in front of every row.  Frame f of row r is
+ *     xb[i]        = P(in[r], f hop - pad + i) win[i]                                              (0 <= i < m)
+ *     out[r, f, k] = scale numpy.fft.rfft(xb)[k]                  out [rows][frames][m/2 + 1] complex   (out_kind DFFT_STFT_OUT_COMPLEX)
+ *     out[r, f, k] = scale^2 |numpy.fft.rfft(xb)[k]|^2            out [rows][frames][m/2 + 1] reals     (out_kind DFFT_STFT_OUT_POWER)
+ * where P(row, s) is row[s] inside [0, n) and outside it 0 (pad_mode DFFT_STFT_PAD_ZERO) or the mirrored sample row[-s] / row[2 (n - 1) - s]
+ * (DFFT_STFT_PAD_REFLECT, which needs pad < n).  dfft_stft1d_frames is 1 + (n + 2 pad - m) / hop where n + 2 pad >= m, else 0; a call
+ * may ask for fewer frames.  With pad = m/2 this is torch.stft(center=True), with pad = 0 center=False; the (bins, frames) order of
+ * torch is the transpose of out's last two axes.
+ * Accepted: n >= 1, dfft_real_form(m) == 1 (m even, m/2 a single-pass length, so m <= 8192), 1 <= frames <= the count above, rows >= 1,
+ * rows * frames < 2^31 items (element offsets are 64-bit); any element-aligned pointers.  NULL pointers, sizes out of range, a bad
+ * dtype, pad mode or out kind, reflect padding with pad >= n, in, out and win overlapping: DFFT_EINVAL; every other m, and 2^31 or more
+ * items: DFFT_EUNSUPPORTED -- all decided before the device is queried.  in and win are never written; nothing outside out is written.
+ * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_stft.hip): the thread group of an item reads its frame straight from the
+ * row -- two reals per access for whole frames where n, hop and pad are even and `in` is aligned to two reals, else real by real with
+ * the zero or mirrored index --, applies the window in registers, transforms, and stores the bins or their squared moduli: the framed
+ * copy (m / hop times the signal) never exists in memory.  Every other accepted m, the (m/2, dtype) whose kernel would spill, and every
+ * m under DFFT_STFT_FUSED=0 (read per call) run gather-and-window -> R2C rows (-> modulus) in chunks of items of at most max(256 MiB,
+ * one item's) scratch from the buffer dfft_trim frees.  dfft_stft1d_fused_applies tells the route, dfft_stft1d_scratch_bytes the lease
+ * (0 for the one launch, and for sizes that are refused).
+ *
+ * dfft_istft1d is the least-squares overlap-add of torch.istft: in [rows][frames][m/2 + 1] complex, out [rows][n] reals with
+ * 1 <= n <= (frames - 1) hop + m - pad, inv_env [n] reals shared by all rows (the caller's 1 / sum_f win^2[t + pad - f hop]):
+ *     c_f       = m numpy.fft.irfft(in[r, f], m)                     (the imaginary parts of bins 0 and m/2 are ignored)
+ *     out[r, t] = inv_env[t] sum_f win[t + pad - f hop] c_f[t + pad - f hop] / m       over the f with 0 <= t + pad - f hop < m
+ * Refusals as above (in, out, win and inv_env must not overlap; in, win and inv_env are never written).  Composed only: per chunk of
+ * frames C2R rows into scratch (from a copy of the bins where m/2 is untuned), then one thread per output sample sums its at most
+ * ceil(m / hop) contributions in ascending frame order -- no atomics, the result does not depend on the chunking.  Chunks hold whole
+ * rows where a row fits; a longer row is cut and every cut transforms again the frames its first outputs share with the cut before.
+ * dfft_istft1d_scratch_bytes is the lease: chunks of at most max(256 MiB, one item's) -- except that a chunk never holds fewer than the
+ * ceil(m / hop) frames one sample sums, which exceeds that only where hop is a few samples and m several thousand.
+ * NOT built: a fused inverse, m > 8192 (four-step and Bluestein frames), two-sided output, reflect padding with pad >= n. */
+#define DFFT_STFT_PAD_ZERO 0
+#define DFFT_STFT_PAD_REFLECT 1
+#define DFFT_STFT_OUT_COMPLEX 0
+#define DFFT_STFT_OUT_POWER 1
+int dfft_stft1d(const void* in, void* out, const void* win, long long n, long long m, long long hop, long long pad, long long frames, long long rows,
+                int dtype, int pad_mode, int out_kind, double scale, void* stream);
+int dfft_istft1d(const void* in, void* out, const void* win, const void* inv_env, long long n, long long m, long long hop, long long pad, long long frames,
+                 long long rows, int dtype, void* stream);
+long long dfft_stft1d_frames(long long n, long long m, long long hop, long long pad);
+int dfft_stft1d_fused_applies(long long m, int dtype);
+unsigned long long dfft_stft1d_scratch_bytes(long long m, long long frames, long long rows, int dtype, int out_kind);
+unsigned long long dfft_istft1d_scratch_bytes(long long m, long long frames, long long rows, int dtype);
+
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
  * `batch` planes of [n1][n2] complex elements (n2 contiguous), each transformed along both axes, in place (out == in) or out
