@@ -47,11 +47,12 @@ def rows_per_group(M):
 
 
 def batch_for(M, channels):
-    """A batch whose rows fill more than one workgroup and leave a ragged last row group (G > 1)"""
+    """A batch whose rows fill more than one workgroup and leave a ragged last row group (G > 1; where G divides the channel count,
+    M = 729 with three channels, every row count is a whole number of groups)"""
     G = rows_per_group(M)
     rows = G + G // 2 + 1 if G > 1 else 4
     batch = -(-rows // channels)
-    while G > 1 and (batch * channels) % G == 0:
+    while G > 1 and channels % G and (batch * channels) % G == 0:
         batch += 1
     return batch
 

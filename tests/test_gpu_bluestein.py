@@ -2,7 +2,9 @@
 both forms (fused for n <= 2048, multi-pass above and under DFFT_BLUESTEIN_FUSED=0), bit-identity with the existing 1-D entry points on
 7-smooth lengths, and 3D plans with DFFT_PLAN_ANY_LENGTH on one GPU and on virtual devices.
 
-Error bound: max|err| / max|ref| < 1e-11 in fp64 (heFFTe's bar), < 1e-4 in fp32."""
+Error bound: max|err| / max|ref| < 1e-11 in fp64 (heFFTe's bar), < 1e-4 in fp32.
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import os
 import re
 import subprocess

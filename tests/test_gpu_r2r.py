@@ -10,7 +10,9 @@ tests/test_gpu_real_strided.py -- the same pair arithmetic plus one twiddle mult
 
 Cross-talk: the two sequences of a pair share one complex transform, so a sequence's rounding error is bounded by the tolerance times
 the PAIR's combined magnitude, not its own: a column 10^-6 the size of its neighbour keeps an absolute error of at most the tolerance
-times the neighbour's magnitude (test_pair_cross_talk_bound)."""
+times the neighbour's magnitude (test_pair_cross_talk_bound).
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import ctypes as C
 import os
 import re

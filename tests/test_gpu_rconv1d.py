@@ -4,7 +4,9 @@ half-lengths of rconv1d_cases.HALVES, n = m, m/2, m/2 - 1 and 1, one and three c
 make a workgroup loop, every fused case once more on the composed route (DFFT_RCONV_FUSED=0), in place bit-identical to out of place,
 fftconv1d against numpy.convolve, the buffer contract on guarded buffers, and a call sequence with dfft_trim in it.
 
-Error measure: accuracy_ref.nu per row with n_eff = m."""
+Error measure: accuracy_ref.nu per row with n_eff = m.
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import ctypes as C
 import os
 

@@ -4,7 +4,9 @@ rconv1d_os_cases.ENTRIES with n = 1, S - 1, S, S + 1, 2 S + S / 2, 3 S and n_out
 loop, every fused case once more on the composed route (DFFT_RCONV_FUSED=0), fftfilt1d against numpy.convolve and against fftconv1d,
 the buffer contract on guarded buffers whose input guards hold NaN, and a call sequence with dfft_trim in it.
 
-Error measure: accuracy_ref.nu per output row with n_eff = m."""
+Error measure: accuracy_ref.nu per output row with n_eff = m.
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import ctypes as C
 import os
 

@@ -1,6 +1,8 @@
 """-m gpu: any-length real transforms -- dfft_rfft1d (api.rfft1d / api.irfft1d) against numpy's rfft / irfft for every real form, and
 dfft_plan_create_r2c_any (api.PlanR2C(any_length=True)) against rfftn / irfftn on one GPU and on P virtual devices; guard regions,
-INPUT_FROM_IN, determinism, the cross-talk bound of the two-for-one pairs, and bit-identity with dfft_plan_create_r2c for form-1 axes."""
+INPUT_FROM_IN, determinism, the cross-talk bound of the two-for-one pairs, and bit-identity with dfft_plan_create_r2c for form-1 axes.
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import threading
 
 import numpy as np

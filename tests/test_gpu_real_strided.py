@@ -1,7 +1,9 @@
 """-m gpu: real transforms along a strided axis and batched 2-D real transforms -- dfft_rfft1d_strided against numpy.fft.rfft(axis=1) /
 n * irfft(axis=1) for every form of n (fused tuned lengths, odd and even; run-time-scheduled, four-step and Bluestein lengths on the
 multi-pass form) and odd and even s, bit-identity with dfft_rfft1d at s = 1, guard regions, misaligned pointers, batch chunks, two
-streams, the cross-talk bound of the column pairs, api.rfft1d / irfft1d with dim, and dfft_rfft2d_batch against rfft2 / irfft2."""
+streams, the cross-talk bound of the column pairs, api.rfft1d / irfft1d with dim, and dfft_rfft2d_batch against rfft2 / irfft2.
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import ctypes as C
 
 import numpy as np

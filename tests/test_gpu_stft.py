@@ -15,7 +15,9 @@ Worst nu measured on an MI355X (fp64 / fp32; the cap is 3.6 / 3.2):
     fused against composed 0.603 / 1.549 (both on power spectrograms, M = 8 / M = 2)      (cap; power: cap x 2)
     inverse 0.706 / 0.883 (M = 25, hop 12)
     round trip 0.597 (n_fft = 36) / 0.387 (n_fft = 128)                                   (cap x 2)
-    against torch on the CPU 1.592 / 1.058 (both on power spectrograms)                   (cap; power: cap x 2)"""
+    against torch on the CPU 1.592 / 1.058 (both on power spectrograms)                   (cap; power: cap x 2)
+
+The per-length sweep -- every tuned length of this family, both precisions, every kernel variant -- lives in tests/test_gpu_tuned_sweep.py."""
 import ctypes as C
 import os
 
