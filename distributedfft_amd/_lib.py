@@ -106,6 +106,12 @@ SIGNATURES = {
     "dfft_rconv1d_os_fused_applies": (C.c_int, [_LL, C.c_int]),
     "dfft_rconv1d_os_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, _LL, C.c_int]),
     "dfft_rconv1d_os_block": (C.c_int, [_LL, _LL, C.c_int, C.POINTER(_LL), C.POINTER(_LL)]),
+    "dfft_rconv1d_long_length": (_LL, [_LL]),
+    "dfft_rconv1d_long_split": (C.c_int, [_LL, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfft_rconv1d_long_filter": (C.c_int, [_VP, _VP, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rconv1d_long": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rconv1d_long_fused_applies": (C.c_int, [_LL, C.c_int]),
+    "dfft_rconv1d_long_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, C.c_int]),
     "dfft_stft1d": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, _LL, C.c_int, C.c_int, C.c_int, C.c_double, _VP]),
     "dfft_istft1d": (C.c_int, [_VP, _VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, _LL, C.c_int, _VP]),
     "dfft_stft1d_frames": (_LL, [_LL, _LL, _LL, _LL]),

@@ -775,6 +775,73 @@ def fftconv1d(x, k, out=None):
     return rconv1d(x, rfft1d(kp), m, out=out)
 
 
+def rconv1d_long_length(at_least: int) -> int:
+    """The smallest padded length m >= at_least that rconv1d_long accepts (dfft_rconv1d_long_length: m even, 8192 < m <= 2^23, m/2 a
+    product of two tuned single-pass lengths); 0 if there is none."""
+    return int(L.load().dfft_rconv1d_long_length(int(at_least)))
+
+
+def rconv1d_long_filter(H, m: Optional[int] = None):
+    """The filter H (channels, m//2 + 1) of rconv1d, complex or real, in the order rconv1d_long reads it (dfft_rconv1d_long_filter): a
+    new tensor of the same shape and dtype, Hp[c, k1 * N2 + k2] = H[c, k1 + N1 * k2], Hp[c, m//2] = H[c, m//2] for the split
+    m//2 = N1 * N2 of the library.  m defaults to 2 * (H.shape[-1] - 1)."""
+    import torch
+    assert H.is_cuda and H.is_contiguous() and H.dim() == 2 and H.dtype in (torch.complex128, torch.complex64, torch.float64, torch.float32), \
+        "H must be a contiguous complex or real device tensor (channels, m//2 + 1)"
+    m = 2 * (int(H.shape[-1]) - 1) if m is None else int(m)
+    assert int(H.shape[-1]) == m // 2 + 1, f"H must have shape (channels, {m // 2 + 1}), got {tuple(H.shape)}"
+    Hp = torch.empty_like(H)
+    with torch.cuda.device(H.device):
+        L.check(L.load().dfft_rconv1d_long_filter(H.data_ptr(), Hp.data_ptr(), m, int(H.shape[0]),
+                                                  F64 if H.dtype in (torch.complex128, torch.float64) else F32,
+                                                  FILTER_COMPLEX if H.dtype.is_complex else FILTER_REAL, None), "dfft_rconv1d_long_filter")
+        torch.cuda.synchronize()
+    return Hp
+
+
+def rconv1d_long(x, Hp, m: Optional[int] = None, out=None):
+    """rconv1d for padded lengths beyond 8192 (dfft_rconv1d_long): y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c],
+    m)[:n] for every row of a contiguous float64 / float32 device tensor (..., channels, n), with Hp = rconv1d_long_filter(H).  m
+    defaults to 2 * (Hp.shape[-1] - 1) and must be a length rconv1d_long_length returns.  Normalised: H == 1 gives y == x.  out=x runs
+    in place."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    channels, n = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    assert Hp.is_cuda and Hp.device == x.device and Hp.is_contiguous() and Hp.dim() == 2 and Hp.dtype in (cdt, x.dtype), \
+        f"Hp must be a contiguous {cdt} or {x.dtype} tensor (channels, m//2 + 1) on {x.device}"
+    m = 2 * (int(Hp.shape[-1]) - 1) if m is None else int(m)
+    assert tuple(Hp.shape) == (channels, m // 2 + 1), f"Hp must have shape {(channels, m // 2 + 1)}, got {tuple(Hp.shape)}"
+    out = _check_out(x, out)
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rconv1d_long(x.data_ptr(), out.data_ptr(), Hp.data_ptr(), n, m, channels, batch,
+                                           F64 if x.dtype == torch.float64 else F32, FILTER_COMPLEX if Hp.dtype == cdt else FILTER_REAL, None),
+                "dfft_rconv1d_long")
+        torch.cuda.synchronize()
+    return out
+
+
+def fftconv1d_long(x, k, out=None):
+    """fftconv1d for n + taps - 1 > 8192: numpy.convolve(x[..., c, :], k[c])[:n] for every row of a contiguous float64 / float32 device
+    tensor (..., channels, n) with the real taps k (channels, taps), through rconv1d_long on m = rconv1d_long_length(n + taps - 1) with
+    the filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 2^23."""
+    import torch
+    assert x.is_cuda and x.dim() >= 2 and k.is_cuda and k.dim() == 2 and k.dtype == x.dtype and k.device == x.device
+    channels, n, taps = int(x.shape[-2]), int(x.shape[-1]), int(k.shape[-1])
+    assert int(k.shape[0]) == channels, f"k must hold one row of taps per channel: ({channels}, taps), got {tuple(k.shape)}"
+    if n + taps - 1 <= 8192:
+        raise ValueError(f"fftconv1d_long: n + taps - 1 = {n + taps - 1} is within the single-pass range (at most 8192): use fftconv1d")
+    m = rconv1d_long_length(n + taps - 1)
+    if m == 0:
+        raise ValueError(f"fftconv1d_long: n + taps - 1 = {n + taps - 1} is beyond the longest padded length (2^23)")
+    kp = torch.zeros((channels, m), dtype=k.dtype, device=k.device)
+    kp[:, :taps] = k
+    return rconv1d_long(x, rconv1d_long_filter(rfft1d(kp)), m, out=out)
+
+
 def rconv1d_os_block(taps: int, n_out: int, dtype) -> tuple:
     """(m, discard) that dfft_rconv1d_os_block chooses for `taps` taps and n_out results per row of a float64 / float32 tensor (dtype a
     torch dtype or F64 / F32): discard = taps - 1 rounded up to even, m the accepted block length with the smallest estimated time.

@@ -110,6 +110,10 @@ def units():
     # chooser and the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_osconv.hip", OBJ / f"dfft_osconv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # long 1-D real FFT convolution (four-step halves): the column and row-pair kernels of the factor lengths of each group, plus the
+    # dispatcher, the filter permutation and the kernels of the composed form
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_lconv.hip", OBJ / f"dfft_lconv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # short-time Fourier transform: the frame kernels of the tuned half-lengths of each group, plus the dispatcher, the composed forward
     # form and the inverse
     for g in range(NUM_INST_GROUPS + 1):

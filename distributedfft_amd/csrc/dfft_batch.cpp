@@ -1,9 +1,10 @@
 // dfft_batch.cpp -- the plan-less batched entry points: complex and real 1-D transforms along rows or a strided axis, batched 2-D
-// transforms, real-to-real transforms, the 1-D real FFT convolution and its overlap-save form, dfft_scale and dfft_trim.
+// transforms, real-to-real transforms, the 1-D real FFT convolution with its overlap-save and long forms, dfft_scale and dfft_trim.
 #include <map>
 #include <mutex>
 #include <tuple>
 
+#include "dfft_lconv.h"
 #include "dfft_osconv.h"
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
@@ -546,6 +547,99 @@ int dfft_rconv1d_os(const void* in, void* out, const void* h, long long n, long 
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d_os: cannot allocate the scratch buffer");
     return osconv(L, fused_on, lease.get(), need, st);
+}
+
+// Long 1-D real FFT convolution (dfft_lconv.hip): the padded lengths beyond dfft_rconv1d's, m/2 = N1 * N2
+static std::string lconv_length_message(const char* who, long long m) {
+    return std::string(who) + ": m = " + std::to_string(m) + " -- the padded length must be even, 8192 < m <= 2^23, with m/2 a product of two tuned "
+           "single-pass lengths (2^a, 3 * 2^a, 5 * 2^a in [64, 2048], 81, 125; dfft_rconv1d_long_length); Bluestein halves are not built";
+}
+
+long long dfft_rconv1d_long_length(long long at_least) { return lconv_length(at_least); }
+
+int dfft_rconv1d_long_split(long long m, int* n1, int* n2) {
+    int a = 0, b = 0;
+    if (!lconv_split(m, &a, &b)) return 0;
+    if (n1) *n1 = a;
+    if (n2) *n2 = b;
+    return 1;
+}
+
+int dfft_rconv1d_long_fused_applies(long long m, int dtype) { return valid_dtype(dtype) && lconv_fused_env() && lconv_fused(m, dtype); }
+
+unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || channels >= (1ll << 31) || batch >= (1ll << 31) ||
+        batch * channels >= (1ll << 31))
+        return 0;
+    return lconv_scratch_bytes(m, dtype, batch * channels);
+}
+
+int dfft_rconv1d_long_filter(const void* h, void* hp, long long m, long long channels, int dtype, int filter_kind, void* stream) {
+    if (!h || !hp || m < 1 || channels < 1 || !valid_dtype(dtype) || (filter_kind != DFFT_FILTER_COMPLEX && filter_kind != DFFT_FILTER_REAL))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_long_filter: bad arguments");
+    if (!lconv_split(m, nullptr, nullptr)) return fail(DFFT_EUNSUPPORTED, lconv_length_message("dfft_rconv1d_long_filter", m));
+    const size_t    es = filter_kind == DFFT_FILTER_REAL ? elem_bytes(dtype) / 2 : elem_bytes(dtype);
+    const uintptr_t bytes = (uintptr_t)channels * (m / 2 + 1) * es;
+    if (ranges_overlap(h, bytes, hp, bytes)) return fail(DFFT_EINVAL, "dfft_rconv1d_long_filter: h and hp overlap (the permutation is out of place)");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d_long_filter: no HIP device visible (no CPU fallback)");
+    return lconv_filter(h, hp, m, channels, (int)es, (hipStream_t)stream);
+}
+
+int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long long m, long long channels, long long batch, int dtype, int filter_kind,
+                      void* stream) {
+    if (!in || !out || !hp || n < 1 || m < 1 || channels < 1 || batch < 1 || m < n || !valid_dtype(dtype) ||
+        (filter_kind != DFFT_FILTER_COMPLEX && filter_kind != DFFT_FILTER_REAL))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_long: bad arguments");
+    if (!lconv_split(m, nullptr, nullptr)) return fail(DFFT_EUNSUPPORTED, lconv_length_message("dfft_rconv1d_long", m));
+    if (channels >= (1ll << 31) || batch >= (1ll << 31) || batch * channels >= (1ll << 31))
+        return fail(DFFT_EUNSUPPORTED, "dfft_rconv1d_long: batch * channels = 2^31 or more rows: split the batch");
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const long long rows = batch * channels, nh = m / 2 + 1;
+    const uintptr_t bytes = (uintptr_t)rows * n * rs;
+    if (partly_overlap(in, out, bytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_long: in and out overlap partly (the convolution runs out of place or exactly in place)");
+    if (ranges_overlap(hp, (uintptr_t)channels * nh * (filter_kind == DFFT_FILTER_REAL ? rs : cs), out, bytes))
+        return fail(DFFT_EINVAL, "dfft_rconv1d_long: the filter overlaps out");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d_long: no HIP device visible (no CPU fallback)");
+    const hipStream_t st = (hipStream_t)stream;
+    ScratchLease      lease;
+    if (lconv_fused_env() && lconv_fused(m, dtype)) {
+        LconvLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.dtype = dtype;
+        L.filter_kind = filter_kind;
+        L.n = n;
+        L.m = m;
+        L.channels = channels;
+        L.batch = batch;
+        L.in = in;
+        L.out = out;
+        L.hp = hp;
+        const size_t need = lconv_scratch_bytes(m, dtype, rows);
+        if (!lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d_long: cannot allocate the scratch buffer");
+        return lconv_run(L, lease.get(), need, st);
+    }
+    // composed route, per chunk of rows of at most max(256 MiB, one row's) bins and padded rows: pad, the real rows of length m as
+    // dfft_rfft1d runs them, multiply by H / m, the inverse rows, truncate -- on ONE lease (bins, padded rows, the transforms' own scratch)
+    const size_t    rb = (size_t)nh * cs + (size_t)m * rs;
+    const long long nr = std::max(1ll, std::min(rows, (long long)(std::max((size_t)(256ull << 20), rb) / rb)));
+    RealRowsPass    Rf, Rb;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_BACKWARD, true, &Rb)) return rc;
+    const size_t data_b = ((size_t)nr * rb + 255) / 256 * 256;
+    if (!lease.acquire(data_b + std::max(Rf.need, Rb.need), st)) return fail(DFFT_EHIP, "dfft_rconv1d_long: cannot allocate the scratch buffer");
+    char* bins = (char*)lease.get();          // [nr][nh] complex
+    char* pad = bins + (size_t)nr * nh * cs;  // [nr][m] reals
+    void* inner = bins + data_b;
+    for (long long r0 = 0; r0 < rows; r0 += nr) {
+        const long long k = std::min(nr, rows - r0);
+        if (int rc = lconv_pad((const char*)in + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+        if (int rc = real_rows_run(Rf, pad, bins, k, inner, st)) return rc;
+        if (int rc = lconv_mul(bins, hp, m, r0, channels, k, dtype, filter_kind, st)) return rc;
+        if (int rc = real_rows_run(Rb, bins, pad, k, inner, st)) return rc;
+        if (int rc = lconv_trunc(pad, (char*)out + (size_t)r0 * n * rs, n, m, k, dtype, st)) return rc;
+    }
+    return DFFT_OK;
 }
 
 // `batch` planes of [n1][n2] reals <-> [n1][n2/2 + 1] bins, in groups of planes sized for the 256 MiB Infinity Cache (dfft_fft2d_batch's

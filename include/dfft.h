@@ -503,6 +503,37 @@ int dfft_rconv1d_os_fused_applies(long long m, int dtype);
 unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, long long discard, long long channels, long long batch, int dtype);
 int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long* m, long long* discard);
 
+/* dfft_rconv1d for padded lengths beyond 8192 -- taps about as long as the row ("long convolution"): the same definition, normalisation
+ * and DC / Nyquist rule,
+ *     out[b, c, :] = numpy.fft.irfft(numpy.fft.rfft(in[b, c, :], m) * H[c, :], m)[:n]        (row r uses filter row r % channels)
+ * with the filter handed over as hp = dfft_rconv1d_long_filter(H): a pure permutation of H [channels][M + 1], M = m/2 = N1 * N2,
+ *     hp[c][k1 * N2 + k2] = H[c][k1 + N1 * k2]   (k1 < N1, k2 < N2),        hp[c][M] = H[c][M],
+ * of the same element type (hp must not overlap h), which is the order the kernels read coalesced.
+ * Accepted: 1 <= n <= m, m even, 8192 < m <= 2^23, M = N1 * N2 with both factors tuned single-pass lengths out of { 2^a, 3 * 2^a, 5 * 2^a
+ * in [64, 2048], 81, 125 }; the split is the most balanced such pair with N1 <= N2 (dfft_rconv1d_long_split: 1 and the pair, or 0;
+ * dfft_rconv1d_long_length(a): the smallest accepted m >= a, 0 if none).  channels >= 1, batch >= 1, batch * channels < 2^31 rows; any
+ * element-aligned pointers.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the batch); NULL pointers, sizes below 1,
+ * m < n, a bad dtype or filter kind, in and out overlapping partly, hp overlapping out: DFFT_EINVAL -- all decided before the device is
+ * queried.  out == in (exactly) is allowed; with out != in, `in` is never written; hp is never written; nothing outside the
+ * batch * channels * n reals of out is written.  Bluestein halves, strided rows and autograd are NOT built.
+ * The call is THREE launches per chunk of rows (csrc/dfft_lconv.hip), the fused kernel of dfft_rconv1d cut along the four-step
+ * decomposition: N1-point columns read straight from the reals (times the four-step twiddle) into M complex of scratch per row; per pair
+ * of scratch rows the N2-point transform, the split / multiply / merge step and the N2-point inverse, in place; the inverse N1-point columns
+ * stored as the first n reals -- 2 n + 4 m reals of traffic per row; the zero padding, the spectrum and the truncated tail never exist in
+ * memory.  Chunks hold at most max(256 MiB, one row's) scratch from the per-(device, stream) buffer dfft_trim frees; a call allocates
+ * nothing once that and the small twiddle tables of (device, m, dtype) are warm.  The splits whose kernels would spill or measured slower,
+ * and every m under DFFT_RCONV_LONG_FUSED=0 (read per call), run pad -> the real rows of length m as dfft_rfft1d runs them -> multiply ->
+ * inverse rows -> truncate.  dfft_rconv1d_long_fused_applies tells the route; dfft_rconv1d_long_scratch_bytes the lease of the three-launch
+ * route: min(rows, rows per chunk) * M complex (0 for sizes that are refused; the composed route leases its bins, padded rows and the
+ * transforms' own scratch instead).  Both, the length and the split are host arithmetic. */
+long long dfft_rconv1d_long_length(long long at_least);
+int dfft_rconv1d_long_split(long long m, int* n1, int* n2);
+int dfft_rconv1d_long_filter(const void* h, void* hp, long long m, long long channels, int dtype, int filter_kind, void* stream);
+int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long long m, long long channels, long long batch, int dtype, int filter_kind,
+                      void* stream);
+int dfft_rconv1d_long_fused_applies(long long m, int dtype);
+unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
+
 /* Batched short-time Fourier transform and its inverse (unnormalised, numpy conventions).  Rows of reals in [rows][n], a window win [m]
  * of reals, frames of m reals that advance by hop >= 1, 0 <= pad < m samples of padding in front of every row.  Frame f of row r is
  *     xb[i]        = P(in[r], f hop - pad + i) win[i]                                              (0 <= i < m)
