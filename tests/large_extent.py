@@ -12,6 +12,13 @@ line and its (b, c) are reported.  (3) Out of place: `out` starts as NaN (an unw
 compared bit for bit afterwards.  In place an unwritten line still holds its input and fails (2).  (4) wrap_distinct: an access that lands
 2^31, 2^32 or 2^33 elements (or 2^31 / 2^32 bytes) away from where it should finds a DIFFERENT value there, a different (L mod K, k).
 
+ROWS WHOSE NEIGHBOURING LINES INTERACT (Band, run_band_case: one long row of overlap-save blocks, STFT frames and their inverse).  Input
+and output have their own line counts and lengths, and an output line depends on a few neighbouring input lines, so it is a function of
+its index modulo K only away from a row's ends.  The base lines of check (2) are therefore the output lines K ... 2K - 1, the lines at a
+row's ends are held against their own longdouble reference (rows past the first K: against the same lines of row r mod K), and the
+reference of the K interior lines is the family's own reference on a short tiled row, whose lines K ... 2K - 1 see whole windows -- the
+period-K circular form.  Families outside accuracy_ref.BOUND register the bound their own GPU module asserts in EXTRA_BOUND.
+
 Everything takes torch tensors on any device: the host tests run the same code on CPU tensors with numpy standing in for the transform.
 Temporaries stay under 1 GiB (SLICE_BYTES per temporary, a handful alive at once).
 
@@ -181,9 +188,25 @@ def worst_line(out, K):
     return float(vals[j]), (b0 + idxs[j] // nc, c0 + idxs[j] % nc)
 
 
+EXTRA_BOUND = {}   # family -> {prec: bound}: the bounds that a family's own GPU module asserts, for families outside accuracy_ref.BOUND
+
+
+def family_bound(family, prec):
+    """The BOUND of check (1): accuracy_ref's, or the one a family outside accuracy_ref registered in EXTRA_BOUND (no new tolerance)."""
+    return EXTRA_BOUND[family][prec] if family in EXTRA_BOUND else A.BOUND[family][prec]
+
+
 def line_limit(family, prec, n_eff):
     """2 BOUND eps sqrt(log2 n): two results within BOUND eps sqrt(log2 n) (relative L2) of one true line."""
-    return 2 * A.BOUND[family][prec] * A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
+    return 2 * family_bound(family, prec) * A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
+
+
+def check_bound(family, prec, value, what):
+    """accuracy_ref.check for every family: prints the figure and holds it against the family's BOUND."""
+    if family in A.BOUND:
+        return A.check(family, prec, value, what)
+    print(f"accuracy {family} {prec} {what}: nu {value:.3f}")
+    assert value <= family_bound(family, prec), (family, prec, what, value, family_bound(family, prec))
 
 
 WORST_LINES = {}   # (family, prec) -> (worst line difference in units of its limit's eps sqrt(log2 n), case) of this process
@@ -195,17 +218,17 @@ def check_output(out, ref, K, family, prec, n_eff, what):
     per_line = [A.nu(got[i:i + 1], ref[i:i + 1], n_eff, prec, (1,)) for i in range(K)]
     i = max(range(K), key=lambda q: per_line[q] if per_line[q] == per_line[q] else math.inf)   # a NaN line is the worst
     try:
-        A.check(family, prec, max(per_line[i], A.nu(got, ref, n_eff, prec, (1,))), f"{what} base lines")
+        check_bound(family, prec, max(per_line[i], A.nu(got, ref, n_eff, prec, (1,))), f"{what} base lines")
     except AssertionError as e:
         raise AssertionError((what, "worst base line", i, "at (b, c) =", divmod(i, out.shape[2]), per_line[i]) + tuple(e.args)) from None
     worst, (b, c) = worst_line(out, K)
     unit = A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
     print(f"large-extent {family} {prec} {what}: worst line (b={b}, c={c}) differs from its base line by {worst / unit:.3f} eps sqrt(log2 n)"
-          f" (limit {2 * A.BOUND[family][prec]})")
+          f" (limit {2 * family_bound(family, prec)})")
     if worst / unit > WORST_LINES.get((family, prec), (-1.0, ""))[0]:
         WORST_LINES[(family, prec)] = (worst / unit, what)
     assert worst <= line_limit(family, prec, n_eff), (what, "line", (b, c), "base line", (b * out.shape[2] + c) % K, worst / unit,
-                                                     2 * A.BOUND[family][prec])
+                                                     2 * family_bound(family, prec))
 
 
 def case_plan(prec, base_in, ref, batch, s, inplace, scratch=0, K=None):
@@ -256,6 +279,215 @@ def run_case(device, what, family, prec, n_eff, base_in, ref, batch, s, call, in
             hit = input_intact(x, baseT, K)
             assert hit is None, (what, "the input changed at (b, k, c) =", hit)
         check_output(out, ref, K, family, prec, n_eff, what)
+    finally:
+        del x, out, baseT
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+        print(f"large-extent {what}: case wall time {time.perf_counter() - t_case:.2f} s")
+    return dt, peak
+
+
+# ---- rows whose neighbouring lines interact (overlap-save, STFT, inverse STFT) ----------------------------------------------------------------
+class Band:
+    """`rows` rows cut into lines: a row holds `lin` input lines of p_in elements and `lout` output lines of p_out elements, and output
+    line t of a row depends on the row's input lines t - qb ... t + qa (those inside [0, lin)).  Input line g = r * lin + i of the whole
+    tensor holds base line g mod K, so output line (r, t) is a function of (r * lin + t) mod K alone wherever its window is whole:
+    qb <= t < lin - qa, the INTERIOR lines.  The first qb lines of a row (head) and its last tail = lout - (lin - qa) lines see a cut
+    window: EDGE lines.
+        overlap-save, lines of S = m - d samples     qb = ceil(d / S), qa = 0, lout = lin
+        STFT without centring, lines of hop samples  qb = 0, qa = m / hop - 1, lout = lin - qa (frames of m/2 + 1 bins): no edge line
+        inverse STFT, lines of hop samples           qb = m / hop - 1, qa = 0, lout = lin + qb (lin frames)
+    The base lines of check (2) are the output lines K ... 2K - 1 of row 0 (all interior: K >= qb, lin >= 2K + qa)."""
+
+    def __init__(self, rows, lin, lout, qb, qa):
+        self.rows, self.lin, self.lout, self.qb, self.qa = rows, lin, lout, qb, qa
+        self.tail = lout - (lin - qa)
+        assert rows >= 1 and qb >= 0 and qa >= 0 and self.tail >= 0 and lout >= 1, vars(self)
+
+    def edge_rows(self, K):
+        """rows whose edge lines are held against their own reference: row r's edges equal those of row r mod K"""
+        return min(self.rows, K)
+
+    def head_ids(self, K):
+        """input lines of the small signal whose output lines 0 ... 2K - 1 are those of row 0"""
+        return [g % K for g in range(2 * K + self.qa + self.qb)]
+
+    def edge_ids(self, K, r, head):
+        """input lines of a small signal that starts (head) or ends (not head) as row r does"""
+        T = 2 * (self.qa + self.qb) + 2
+        first = r * self.lin + (0 if head else self.lin - T)
+        return [(first + i) % K for i in range(T)]
+
+
+def band_wrap_hits(band, p_out, K, shift):
+    """The output tensor [rows][lout][p_out] of a Band: (carry, class delta) at which element e and e + shift are the same element k of
+    interior lines of one class; [] is a pass.  shift = (a lout + b) p_out moves line (r, t) to (r + a, t + b) or (r + a + 1, t + b -
+    lout), and the class (r lin + t) mod K by a lin + b or (a + 1) lin + b - lout."""
+    if shift >= band.rows * band.lout * p_out or shift % p_out:
+        return []
+    a, b = divmod(shift // p_out, band.lout)
+    hits = []
+    if (a * band.lin + b) % K == 0:
+        hits.append((0, a * band.lin + b))
+    if b and a + 1 < band.rows and ((a + 1) * band.lin + b - band.lout) % K == 0:
+        hits.append((1, (a + 1) * band.lin + b - band.lout))
+    return hits
+
+
+def band_wrap_distinct(band, p_in, p_out, K, eb_in, eb_out):
+    """wrap_distinct for both tensors of a Band: the input is [rows * lin][p_in][1] with line g = base line g mod K"""
+    shifts = list(WRAPS_ELEMS) + [w // eb_out for w in WRAPS_BYTES if w % eb_out == 0]
+    return (wrap_distinct(band.rows * band.lin, p_in, 1, K, eb_in) and all(not band_wrap_hits(band, p_out, K, d) for d in shifts)
+            and band.lin >= 2 * K + band.qa and K >= band.qb)
+
+
+def band_pick_k(band, p_in, p_out, eb_in, eb_out):
+    for K in K_CANDIDATES:
+        if band_wrap_distinct(band, p_in, p_out, K, eb_in, eb_out):
+            return K
+    raise AssertionError(f"no K of {K_CANDIDATES} keeps wrapped accesses apart for {vars(band)}, lines of {p_in} / {p_out}")
+
+
+def band_refs(band, K, small):
+    """The longdouble references of a Band from `small(ids) -> [lines][p_out]`, the family's reference of ONE complete row whose input
+    lines are the base lines ids: (the K interior classes [K][p_out], heads [edge rows][qb][p_out], tails [edge rows][tail][p_out]).
+    The classes are the period-K form of the reference: lines K ... 2K - 1 of a row of 2K + qa + qb tiled lines see whole windows."""
+    o = np.asarray(small(band.head_ids(K)))
+    assert o.shape[0] >= 2 * K, o.shape
+    classes = o[K:2 * K]
+    nk = band.edge_rows(K)
+    heads = np.stack([np.asarray(small(band.edge_ids(K, r, True)))[:band.qb] for r in range(nk)]) if band.qb else None
+    tails = np.stack([np.asarray(small(band.edge_ids(K, r, False)))[-band.tail:] for r in range(nk)]) if band.tail else None
+    return classes, heads, tails
+
+
+def band_table(out2, band, K):
+    """out2 [rows * lout][p_out] -> what every line is compared with, [K + nk qb + nk tail][p_out]: the interior classes (lines K ...
+    2K - 1 of row 0), then the head and the tail lines of the first nk = min(rows, K) rows."""
+    import torch
+    nk, o3 = band.edge_rows(K), out2.view(band.rows, band.lout, -1)
+    parts = [out2[K:2 * K]]
+    if band.qb:
+        parts.append(o3[:nk, :band.qb].reshape(nk * band.qb, -1))
+    if band.tail:
+        parts.append(o3[:nk, band.lout - band.tail:].reshape(nk * band.tail, -1))
+    return torch.cat(parts).contiguous()
+
+
+def _band_index(g0, g1, band, K, device):
+    """row of band_table for the output lines g0 ... g1 - 1 (g = r lout + t)"""
+    import torch
+    g = torch.arange(g0, g1, device=device, dtype=torch.int64)
+    r = g // band.lout
+    t = g - r * band.lout
+    nk, rk = band.edge_rows(K), r % K
+    idx = (r * band.lin + t) % K
+    if band.qb:
+        idx = torch.where(t < band.qb, K + rk * band.qb + t, idx)
+    if band.tail:
+        idx = torch.where(t >= band.lout - band.tail, K + nk * band.qb + rk * band.tail + (t - (band.lout - band.tail)), idx)
+    return idx
+
+
+def band_worst_line(out2, band, K):
+    """Every line of out2 [rows * lout][p_out] against the line of band_table it must equal: (worst per-line relative L2 difference in
+    fp64, (r, t) of that line).  A line holding a NaN or an infinity counts as infinitely far."""
+    import torch
+    lines, p = out2.shape
+    wide = torch.complex128 if out2.is_complex() else torch.float64
+    table = band_table(out2, band, K).to(wide)
+
+    def sq(v):
+        return torch.view_as_real(v).pow(2).sum((1, -1)) if v.is_complex() else v.pow(2).sum(1)
+
+    den = sq(table)
+    nl = max(1, SLICE_BYTES // 2 // (p * (16 if out2.is_complex() else 8)))
+    found = []
+    for g0 in range(0, lines, nl):
+        g1 = min(lines, g0 + nl)
+        idx = _band_index(g0, g1, band, K, out2.device)
+        rel = torch.sqrt(sq(out2[g0:g1].to(wide) - table[idx]) / den[idx])
+        v, i = torch.nan_to_num(rel, nan=math.inf, posinf=math.inf).max(0)
+        found.append((v, i + g0))
+    vals = torch.stack([f[0] for f in found]).cpu().tolist()
+    at = torch.stack([f[1] for f in found]).cpu().tolist()
+    j = max(range(len(found)), key=lambda q: vals[q])
+    return float(vals[j]), divmod(at[j], band.lout)
+
+
+def band_check_output(out2, refs, band, K, family, prec, n_eff, what):
+    """Checks (1) and (2) for a Band: the K interior classes and every edge line of the first min(rows, K) rows against their longdouble
+    references under the family's BOUND; every line against the line of those it must equal under twice that bound."""
+    classes, heads, tails = refs
+    table = band_table(out2, band, K).cpu().numpy()
+    nk = band.edge_rows(K)
+    named = [(table[:K], classes, [(0, K + i) for i in range(K)], "interior")]
+    if band.qb:
+        named.append((table[K:K + nk * band.qb], heads.reshape(nk * band.qb, -1), [(r, t) for r in range(nk) for t in range(band.qb)], "head"))
+    if band.tail:
+        named.append((table[K + nk * band.qb:], tails.reshape(nk * band.tail, -1),
+                      [(r, band.lout - band.tail + t) for r in range(nk) for t in range(band.tail)], "tail"))
+    worst = (-1.0, None, "")
+    for got, ref, where, kind in named:
+        assert got.shape == ref.shape, (kind, got.shape, ref.shape)
+        for i in range(len(where)):
+            v = A.nu(got[i:i + 1], ref[i:i + 1], n_eff, prec, (1,))
+            v = math.inf if v != v else v                      # a NaN line is the worst
+            if v > worst[0]:
+                worst = (v, where[i], kind)
+    try:
+        check_bound(family, prec, worst[0], f"{what} base and edge lines")
+    except AssertionError as e:
+        raise AssertionError((what, "worst", worst[2], "line at (r, t) =", worst[1], worst[0]) + tuple(e.args)) from None
+    far, (r, t) = band_worst_line(out2, band, K)
+    unit = A.EPS[prec] * math.sqrt(math.log2(max(n_eff, 2)))
+    print(f"large-extent {family} {prec} {what}: worst line (r={r}, t={t}) differs from its base line by {far / unit:.3f} eps sqrt(log2 n)"
+          f" (limit {2 * family_bound(family, prec)})")
+    if far / unit > WORST_LINES.get((family, prec), (-1.0, ""))[0]:
+        WORST_LINES[(family, prec)] = (far / unit, what)
+    assert far <= line_limit(family, prec, n_eff), (what, "line at (r, t) =", (r, t), "class", (r * band.lin + t) % K, far / unit,
+                                                    2 * family_bound(family, prec))
+
+
+def band_plan(prec, base_in, band, p_out, out_complex, scratch=0, K=None):
+    """case_plan for a Band: (K, peak bytes, input dtype, output dtype) before anything is allocated"""
+    import torch
+    p_in = base_in.shape[1]
+    tin, tout = torch_dtype(prec, np.iscomplexobj(base_in)), torch_dtype(prec, out_complex)
+    eb_in, eb_out = torch.empty(0, dtype=tin).element_size(), torch.empty(0, dtype=tout).element_size()
+    K = band_pick_k(band, p_in, p_out, eb_in, eb_out) if K is None else K
+    assert base_in.shape[0] == K and band_wrap_distinct(band, p_in, p_out, K, eb_in, eb_out), (vars(band), K)
+    peak = peak_bytes(band.rows * band.lin * p_in * eb_in, band.rows * band.lout * p_out * eb_out, scratch)
+    assert peak <= CAP_80, peak
+    return K, peak, tin, tout
+
+
+def run_band_case(device, what, family, prec, n_eff, base_in, small, band, p_out, out_complex, call, K=None, scratch=0):
+    """One tiled case of a Band, out of place.  base_in [K][p_in] (numpy) fixes the input [rows * lin][p_in]; small(ids) is the family's
+    longdouble reference of one complete row of the base lines ids; call(x, out) runs the transform on x [rows * lin][p_in] and out
+    [rows * lout][p_out].  Prints and returns what run_case does."""
+    import torch
+    t_case = time.perf_counter()
+    K, peak, tin, tout = band_plan(prec, base_in, band, p_out, out_complex, scratch, K)
+    refs = band_refs(band, K, small)
+    p_in = base_in.shape[1]
+    baseT = base_tensor(base_in, prec, device)
+    x = torch.empty((band.rows * band.lin, p_in, 1), dtype=tin, device=device)
+    fill(x, baseT, K)
+    out = torch.full((band.rows * band.lout, p_out), math.nan, dtype=tout, device=device)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    call(x.view(band.rows * band.lin, p_in), out)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"large-extent {what}: call {dt:.3f} s, peak {peak} bytes = {peak / 2**30:.1f} GiB (K = {K})")
+    try:
+        hit = input_intact(x, baseT, K)
+        assert hit is None, (what, "the input changed at (line, k, 0) =", hit)
+        band_check_output(out, refs, band, K, family, prec, n_eff, what)
     finally:
         del x, out, baseT
         if device.type == "cuda":

@@ -5,7 +5,8 @@ One case per 32-bit guard of the plan-less routes that a call of at most 80 GiB 
 over it where both fit ("32-bit guards of the plan-less routes", lists every guard with the case that brackets it).  The larger
 tensor of a pair runs in place.  A case whose peak (buffers + the library's scratch + 1 GiB) exceeds the free HBM skips; on a 288 GB
 MI355X none does.  The case tables are module constants so that tests/test_large_extent_host.py can hold the wrap assertion for every shape
-and the route predicates for every switch without a GPU."""
+and the route predicates for every switch without a GPU.  The 1-D real convolution and STFT entry points run in the sibling module
+tests/test_gpu_large_extent_rows.py, whose tensors all_shapes() covers."""
 import pytest
 
 import accuracy_ref as A
@@ -94,7 +95,8 @@ def all_shapes():
         out.append((cid, b, n1 * n2, 1, c[p]))
     for cid, n1, n2, b, p in RFFT2D:
         out += [(cid + " reals", b, n1 * n2, 1, c[p] // 2), (cid + " bins", b, n1 * (n2 // 2 + 1), 1, c[p])]
-    return out
+    import test_gpu_large_extent_rows as rows_module   # the 1-D real convolution and STFT entry points: the sibling module's tensors
+    return out + rows_module.shapes()
 
 
 # ---- running a case --------------------------------------------------------------------------------------------------------------------------

@@ -4,14 +4,23 @@ A correct output passes; an unwritten line, a line written at its offset modulo 
 column pair, a chunk shifted by one unit and a changed input element are each rejected, and the report names the line.  The wrap assertion
 is held for every tensor of tests/test_gpu_large_extent.py's case tables and against a brute-force count at small shapes; the mirrors of
 the library's chunk rules are held against its dfft_*_scratch_bytes exports; the extent rule of dfft_fft1d_cols and the one-launch
-predicates are pinned on both sides of every switch, at the shapes no test can allocate as well."""
+predicates are pinned on both sides of every switch, at the shapes no test can allocate as well.
+
+The second half does the same for rows whose neighbouring lines interact (large_extent.Band: overlap-save, STFT, inverse STFT, one row
+and many) and for the tables of tests/test_gpu_large_extent_rows.py: a correct output passes; an unwritten line, a line written at its
+offset modulo 1024, a chunk shifted by one item, a wrong filter row for rows past an index, a changed input sample and an edge line
+treated as an interior line are rejected with the line named; the wrap assertion holds for every tensor and every Band; the routes and
+scratch sizes the cases rely on are pinned on both sides, and so is every 2^31 refusal that a run case sits just under."""
 import itertools
 
 import numpy as np
 import pytest
 
 import large_extent as LE
+import rconv1d_os_cases as OC
+import stft_cases as SC
 import test_gpu_large_extent as G
+import test_gpu_large_extent_rows as GR
 
 F64, F32 = 0, 1
 K = LE.K_DEFAULT
@@ -299,3 +308,290 @@ def test_one_launch_predicates_switch_at_2_pow_31(native_lib, monkeypatch):
     assert (lib.dfft_rfft_cols_fused_applies(512, 4194303, F64), lib.dfft_rfft_cols_fused_applies(512, 4194304, F64)) == (1, 0)
     assert (lib.dfft_r2r_fused_applies(512, 4194302, F64, 0, 1), lib.dfft_r2r_fused_applies(512, 4194304, F64, 0, 1)) == (1, 0)
     assert lib.dfft_r2r_fused_applies(512, 1, F32, 1, 0) == 1     # rows have no such limit
+
+
+# ---- rows whose neighbouring lines interact: the Band helper on CPU tensors --------------------------------------------------------------------
+@pytest.fixture
+def band_slices(monkeypatch):
+    """slices of a few dozen lines, so that many blocks are walked"""
+    monkeypatch.setattr(LE, "SLICE_BYTES", 1 << 13)
+    GR.register_bounds()
+
+
+def _os_host():
+    """overlap-save, one row: m = 16, d = 6, lines of S = 10 samples"""
+    M, d, lines = 8, 6, 200
+    band = LE.Band(1, lines, lines, 1, 0)
+    base, H, small = GR.os_band_base(M, d, "complex", K)
+
+    def call(x, out):
+        import torch
+        out.copy_(torch.from_numpy(OC.reference(x.numpy().reshape(1, -1), H, 2 * M, d, lines * 10).astype(np.float64).reshape(lines, 10)))
+    return "rconv1d_os", 2 * M, base, small, band, 10, False, call
+
+
+def _stft_host(kind="complex"):
+    """STFT, one row: m = 16, hop = 4 (every frame spans four lines), no edge line"""
+    M, hop, lines = 8, 4, 300
+    band = LE.Band(1, lines, lines - 3, 0, 3)
+    base, win, small = GR.stft_base(M, hop, kind, K)
+
+    def call(x, out):
+        import torch
+        X = SC.reference(x.numpy().reshape(1, -1), win, 2 * M, hop, 0, lines - 3, "zero")[0]
+        out.copy_(torch.from_numpy((SC.power(X).astype(np.float64) if kind == "power" else X.astype(np.complex128))))
+    return "stft" if kind == "complex" else "stft-power", 2 * M, base, small, band, M + 1, kind == "complex", call
+
+
+def _istft_host(rows=1, frames=200):
+    """inverse STFT: m = 16, hop = 4: three head and three tail lines per row"""
+    M, hop = 8, 4
+    band = LE.Band(rows, frames, frames + 3, 3, 0)
+    base, win, small = GR.istft_base(M, hop, K)
+    inv = GR.istft_envelope_lines(win, 2 * M, hop, frames).reshape(-1)
+
+    def call(x, out):
+        import torch
+        y = SC.inverse_reference(x.numpy().reshape(rows, frames, M + 1), win, inv, (frames + 3) * hop, 2 * M, hop, 0)
+        out.copy_(torch.from_numpy(y.astype(np.float64).reshape(-1, hop)))
+    return "istft", 2 * M, base, small, band, hop, False, call
+
+
+BAND_HOSTS = {"os": _os_host, "stft": _stft_host, "stft-power": lambda: _stft_host("power"), "istft": _istft_host,
+              "istft-rows": lambda: _istft_host(70, 130)}
+
+
+def _band_case(host, spoil=None):
+    family, m, base, small, band, p_out, cplx, call = host
+
+    def spoiled(x, out):
+        call(x, out)
+        if spoil:
+            spoil(x, out)
+    return LE.run_band_case(_cpu(), "host stand-in", family, "f64", m, base, small, band, p_out, cplx, spoiled, K=K)
+
+
+def _band_rejected(host, spoil, *lines):
+    with pytest.raises(AssertionError) as e:
+        _band_case(host, spoil)
+    text = str(e.value)
+    assert any(f"({r}, {t})" in text for r, t in lines), (text, lines)
+
+
+@pytest.mark.parametrize("name", sorted(BAND_HOSTS))
+def test_band_a_correct_output_passes(band_slices, name):
+    host = BAND_HOSTS[name]()
+    dt, peak = _band_case(host)
+    band = host[4]
+    assert band.tail == {"os": 0, "stft": 0, "stft-power": 0, "istft": 3, "istft-rows": 3}[name]
+    assert peak > LE.GIB
+
+
+def test_band_inverse_envelope_of_a_long_row_is_its_head_interior_and_tail(band_slices):
+    win = SC.window(16, "hann")
+    want = GR.istft_envelope_lines(win, 16, 4, 200).reshape(-1)
+    got = GR.istft_inv_env(win, 16, 4, 200, "f64", _cpu()).numpy()
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("name", ["os", "stft", "istft", "istft-rows"])
+def test_band_an_unwritten_line_is_rejected(band_slices, name):
+    host = BAND_HOSTS[name]()
+    band = host[4]
+    r, t = band.rows - 1, band.lout // 2 + 7
+
+    def unwritten(x, out):
+        out[r * band.lout + t] = float("nan")
+    _band_rejected(host, unwritten, (r, t))
+
+
+@pytest.mark.parametrize("name", ["os", "stft", "istft-rows"])
+def test_band_a_line_written_at_its_offset_modulo_a_power_of_two_is_rejected(band_slices, name):
+    host = BAND_HOSTS[name]()
+    band, p = host[4], host[5]
+    g, W = band.rows * band.lout - 9, 1024
+
+    def wrapped(x, out):
+        flat = out.view(-1)
+        line = out[g].clone()
+        out[g] = float("nan")
+        for k in range(p):
+            flat[(g * p + k) % W] = line[k]
+    hit = {divmod(g, band.lout)} | {divmod(((g * p + k) % W) // p, band.lout) for k in range(p)}
+    _band_rejected(host, wrapped, *hit)
+
+
+@pytest.mark.parametrize("name", ["os", "stft", "istft", "istft-rows"])
+def test_band_a_chunk_shifted_by_one_item_is_rejected(band_slices, name):
+    host = BAND_HOSTS[name]()
+    band = host[4]
+    g0 = (band.rows - 1) * band.lout + 140 if band.rows == 1 else 5 * band.lout + 40
+
+    def shifted(x, out):
+        out[g0:g0 + 16] = out[g0 + 1:g0 + 17].clone()
+    _band_rejected(host, shifted, *[divmod(g, band.lout) for g in range(g0, g0 + 16)])
+
+
+@pytest.mark.parametrize("name", ["os", "stft", "istft-rows"])
+def test_band_a_changed_input_sample_is_rejected(band_slices, name):
+    host = BAND_HOSTS[name]()
+
+    def touched(x, out):
+        x[150, 2] += 1
+    with pytest.raises(AssertionError) as e:
+        _band_case(host, touched)
+    assert "(150, 2, 0)" in str(e.value) and "input" in str(e.value)
+
+
+@pytest.mark.parametrize("name,edge", [("os", "head"), ("istft", "head"), ("istft", "tail"), ("istft-rows", "head"), ("istft-rows", "tail")])
+def test_band_an_edge_line_treated_as_an_interior_line_is_rejected(band_slices, name, edge):
+    """The edge line holds what an interior line of its class holds (a window that wrapped round the row's end instead of being cut)."""
+    host = BAND_HOSTS[name]()
+    band = host[4]
+    r = band.rows - 1
+    t = 0 if edge == "head" else band.lout - 1
+    cls = (r * band.lin + t) % K
+
+    def as_interior(x, out):
+        out[r * band.lout + t] = out[K + cls]     # line K + cls of row 0 is the interior line of that class
+    _band_rejected(host, as_interior, (r, t))
+
+
+def test_band_rows_past_the_first_K_have_their_edges_compared(band_slices):
+    """Row 69 of 70: a head line that holds row 9's head line is rejected although its own reference is never computed (it is held against
+    the head line of row 69 mod 61 = 8, which starts with the same base lines)."""
+    host = BAND_HOSTS["istft-rows"]()
+    band = host[4]
+
+    def spoil(x, out):
+        out[69 * band.lout + 1] = out[9 * band.lout + 1]
+    _band_rejected(host, spoil, (69, 1))
+
+
+def test_band_wrap_hits_agrees_with_brute_force():
+    for rows, lin, lout, p, K_, dq in itertools.product((1, 4, 9), (11, 13), (0, 2), (1, 3), (3, 5, 7), (1, 5, 7, 12, 15, 26, 35)):
+        band = LE.Band(rows, lin, lin + lout, lout, 0)
+        shift = dq * p
+        g = np.arange(rows * band.lout)
+        r, t = np.divmod(g, band.lout)
+        cls = (r * lin + t) % K_
+        ok = g + dq < rows * band.lout
+        same = bool(np.any(cls[g[ok]] == cls[(g + dq)[ok]]))
+        assert same <= bool(LE.band_wrap_hits(band, p, K_, shift)), (rows, lin, lout, p, K_, dq)
+        assert LE.band_wrap_hits(band, p, K_, shift + 1) == [] or p == 1
+    assert not LE.band_wrap_hits(LE.Band(1, 500, 500, 1, 0), 4, 61, 4 * 60) and LE.band_wrap_hits(LE.Band(1, 500, 500, 1, 0), 4, 61, 4 * 122)
+
+
+# ---- rows with one filter row each: a wrong filter row shows ----------------------------------------------------------------------------------
+def test_a_wrong_filter_row_for_rows_past_an_index_is_rejected(small_slices):
+    GR.register_bounds()
+    M, n, rows = 8, 12, 3 * K + 5
+    x, H, ref = GR.rconv_base(M, n, "complex", K)
+
+    def conv(first_wrong):
+        def call(t, out):
+            import torch
+            xs = t.numpy().reshape(rows, n)
+            r = np.arange(rows)
+            Hr = H[np.where(r >= first_wrong, (r + 1) % K, r % K)]          # rows past first_wrong take their neighbour's filter
+            out.copy_(torch.from_numpy(np.fft.irfft(np.fft.rfft(xs, 2 * M, axis=1) * Hr, 2 * M, axis=1)[:, :n].reshape(rows, n, 1)))
+        return call
+    LE.run_case(_cpu(), "host stand-in", "rconv1d", "f64", 2 * M, x, ref, rows, 1, conv(rows), False, K=K)
+    with pytest.raises(AssertionError) as e:
+        LE.run_case(_cpu(), "host stand-in", "rconv1d", "f64", 2 * M, x, ref, rows, 1, conv(2 * K + 3), False, K=K)
+    assert any(f"({b}, 0)" in str(e.value) for b in range(2 * K + 3, rows)), str(e.value)
+
+
+# ---- the tables of tests/test_gpu_large_extent_rows.py ---------------------------------------------------------------------------------------
+def test_wrapped_accesses_land_on_other_values_for_every_band():
+    assert {s[0] for s in GR.shapes()} <= {s[0] for s in G.all_shapes()}        # all_shapes() covers the sibling module
+    bands = GR.band_shapes()
+    assert len(bands) == len(GR.OS_BAND) + len(GR.STFT) + len(GR.ISTFT)
+    for what, band, p_in, p_out, eb_in, eb_out in bands:
+        assert LE.band_pick_k(band, p_in, p_out, eb_in, eb_out) in LE.K_CANDIDATES, what
+        peak = band.rows * (band.lin * p_in * eb_in + band.lout * p_out * eb_out)
+        assert peak + 10 * LE.GIB <= LE.CAP_80, what
+    # a K that divides the class shift of a wrap is rejected: rows of 9 lines from 7 frames, 15 lines on are one row and 6 lines, class + 13,
+    # or two rows less 3 lines, class + 11
+    b = LE.Band(40, 7, 9, 2, 0)
+    assert LE.band_wrap_hits(b, 4, 13, 60) == [(0, 13)] and LE.band_wrap_hits(b, 4, 11, 60) == [(1, 11)] and LE.band_wrap_hits(b, 4, 17, 60) == []
+
+
+def test_row_cases_sit_where_the_table_says():
+    """rows * n, items and offsets of every case against the powers of two they are there for"""
+    P31, P32 = 2 ** 31, 2 ** 32
+    plans = {c[0][:2]: GR.rconv_plan(c) for c in GR.RCONV}
+    assert plans["R1"][1] * 1000 > P32 and plans["R1"][2] == plans["R1"][0] and plans["R1"][1] % plans["R1"][0] == 0
+    assert plans["R2"][1:] == (P31 - 1, P31 - 1, 1)
+    assert plans["R3"][1] * 70 > P32 and plans["R4"][1] * 512 > P31
+    assert GR.os_rows_plan(GR.OS_ROWS[0])[1] * 65538 > P32
+    for c in GR.LONG:
+        assert GR.long_plan(c)[1] * c[2] > P32 and c[2] < c[1] and c[2] % 2 == 0
+    o1, o2, o4 = [GR.os_band(c) for c in GR.OS_BAND]
+    assert o1[0].lin * o1[1] > P32 and o2[0].lin == P31 - 1 and o2[1] == 3 and o4[0].lin * o4[1] > P31
+    s1, s2, s3, s4 = [GR.stft_band(c)[0] for c in GR.STFT]
+    assert s1.lin * 1024 > P32 and s2.lin * 256 > P32 and s2.qa == 3 and s3.lout == P31 - 1 and s3.lout * 3 > P32 and s4.lin * 1024 > P32
+    i1a, i1b, i2 = [GR.istft_band(c)[0] for c in GR.ISTFT]
+    assert i1a.lout * 256 == 2 ** 20 == i1b.lout * 512 and i1a.rows * 2 ** 20 > P31 and i1a.rows * i1a.lin * 513 > P32
+    assert i1b.rows * 2 ** 20 > P32 and i2.rows == 1 and i2.lout * 512 > P31 and i1a.lin % K and i1b.lin % K
+
+
+def test_row_case_routes_and_the_refusals_just_over_their_guards(native_lib, monkeypatch):
+    """Both sides of every switch the cases rely on, and every refusal a run case sits just under: through the entry points, which answer
+    DFFT_EUNSUPPORTED before asking for a device (the pointers, a small host array, are never used)."""
+    from distributedfft_amd import _lib
+    lib = native_lib
+    for name in ("DFFT_RCONV_FUSED", "DFFT_STFT_FUSED", "DFFT_RCONV_LONG_FUSED", "DFFT_STFT_CHUNK_BYTES"):
+        monkeypatch.delenv(name, raising=False)
+    P31 = 2 ** 31
+    # dfft_rconv1d: a tuned half runs fused and leases nothing, M = 36 and DFFT_RCONV_FUSED=0 run composed on a 256 MiB chunk
+    for cid, M, n, kind, prec, _, _, composed, _ in GR.RCONV:
+        assert bool(lib.dfft_rconv1d_fused_applies(n, 2 * M, G.CODE[prec], GR.KIND[kind], 1)) == (not composed), cid
+    rb = 37 * 8 + 72 * 4
+    assert lib.dfft_rconv1d_scratch_bytes(70, 72, 61, 10 ** 6, F32) == (256 << 20) // rb * rb and lib.dfft_rconv1d_scratch_bytes(2, 4, P31 - 1, 1, F32) == 0
+    monkeypatch.setenv("DFFT_RCONV_FUSED", "0")
+    assert lib.dfft_rconv1d_fused_applies(1000, 1024, F32, 0, 1) == 0 and lib.dfft_rconv1d_scratch_bytes(1000, 1024, 61, 1000, F32) > 0
+    assert lib.dfft_rconv1d_os_fused_applies(1024, F32) == 0 and lib.dfft_rconv1d_os_scratch_bytes(7680, 1024, 256, 1, 1, F32) == 10 * (513 * 8 + 1024 * 4)
+    monkeypatch.delenv("DFFT_RCONV_FUSED")
+    # dfft_rconv1d_os: M = 1536 is routed to the composed form in fp64 only
+    assert [lib.dfft_rconv1d_os_fused_applies(m, p) for m, p in ((1024, F32), (4, F32), (3072, F32), (3072, F64), (72, F32))] == [1, 1, 1, 0, 0]
+    ib = 1537 * 16 + 3072 * 8
+    assert lib.dfft_rconv1d_os_scratch_bytes(2 ** 31 + 2048, 3072, 1024, 1, 1, F64) == (256 << 20) // ib * ib
+    assert lib.dfft_rconv1d_os_scratch_bytes(3 * (P31 - 1), 4, 1, 1, 1, F32) == 0
+    # dfft_stft1d / dfft_istft1d
+    assert lib.dfft_stft1d_fused_applies(1024, F32) == 1 and lib.dfft_stft1d_fused_applies(4, F32) == 1
+    assert lib.dfft_stft1d_scratch_bytes(1024, 2 ** 22 + 1, 1, F32, 0) == 0
+    monkeypatch.setenv("DFFT_STFT_FUSED", "0")
+    assert lib.dfft_stft1d_fused_applies(1024, F32) == 0 and lib.dfft_stft1d_scratch_bytes(1024, 2 ** 22 + 1, 1, F32, 0) == 256 << 20
+    monkeypatch.delenv("DFFT_STFT_FUSED")
+    assert lib.dfft_istft1d_scratch_bytes(1024, 2 ** 22, 1, F32) == 256 << 20 == lib.dfft_istft1d_scratch_bytes(1024, 4093, 2049, F32)
+    # dfft_rconv1d_long
+    assert lib.dfft_rconv1d_long_fused_applies(16384, F32) == 1 and lib.dfft_rconv1d_long_scratch_bytes(16000, 16384, 61, 4401, F32) == 256 << 20
+    monkeypatch.setenv("DFFT_RCONV_LONG_FUSED", "0")
+    assert lib.dfft_rconv1d_long_fused_applies(16384, F32) == 0
+    monkeypatch.delenv("DFFT_RCONV_LONG_FUSED")
+    # the refusals: 2^31 rows (R2 runs 2^31 - 1), 2^31 blocks (O2 runs 2^31 - 1), 2^31 frames (S3 runs 2^31 - 1)
+    buf = np.zeros(64, dtype=np.float32)
+    p, q = buf.ctypes.data, buf.ctypes.data + 128
+    h = np.zeros(8, dtype=np.float32).ctypes.data
+    for channels, batch in ((P31, 1), (1, P31), (2 ** 16, 2 ** 15), (3, 715827883)):
+        assert lib.dfft_rconv1d(p, p, h, 2, 4, channels, batch, F32, 1, None) == _lib.EUNSUPPORTED and b"2^31 or more rows" in lib.dfft_last_error()
+        assert lib.dfft_rconv1d_long(p, p, h, 16000, 16384, channels, batch, F32, 1, None) == _lib.EUNSUPPORTED
+        assert lib.dfft_rconv1d_scratch_bytes(2, 4, channels, batch, F32) == 0 == lib.dfft_rconv1d_long_scratch_bytes(16000, 16384, channels, batch, F32)
+    assert lib.dfft_rconv1d_os(p, q, h, 3 * P31, 3 * P31, 4, 1, 1, 1, F32, 0, None) == _lib.EUNSUPPORTED
+    assert b"2^31 or more items" in lib.dfft_last_error()
+    assert lib.dfft_rconv1d_os(p, q, h, 3 * P31 - 2, 3 * P31 - 2, 4, 1, 1, 1, F32, 0, None) == _lib.EUNSUPPORTED       # a ragged last block counts
+    assert lib.dfft_rconv1d_os(p, q, h, 768 * 2 ** 20, 768 * 2 ** 20, 1024, 256, 2 ** 6, 2 ** 5, F32, 0, None) == _lib.EUNSUPPORTED
+    assert lib.dfft_stft1d(p, q, h, 2 * P31 + 2, 4, 2, 0, P31, 1, F32, 0, 1, 1.0, None) == _lib.EUNSUPPORTED
+    assert b"2^31 or more items" in lib.dfft_last_error()
+    assert lib.dfft_stft1d(p, q, h, 2 ** 20, 1024, 256, 0, 4093, 524689, F32, 0, 0, 1.0, None) == _lib.EUNSUPPORTED   # 4093 * 524 689 = 2^31 + 429
+    assert lib.dfft_istft1d(q, p, h, h + 16, 2 * P31 + 2, 4, 2, 0, P31, 1, F32, None) == _lib.EUNSUPPORTED
+    assert lib.dfft_stft1d_scratch_bytes(4, P31, 1, F32, 1) == 0 == lib.dfft_istft1d_scratch_bytes(4, P31, 1, F32)
+    assert not buf.any()
+    if lib.dfft_device_count() == 0:
+        # just under each guard the call is accepted: made-up, disjoint addresses, which only a machine without a device may be handed
+        a, b, c = 1 << 44, 1 << 46, 1 << 42
+        assert lib.dfft_rconv1d(a, a, c, 2, 4, P31 - 1, 1, F32, 1, None) == _lib.ENOGPU
+        assert lib.dfft_rconv1d_os(a, b, c, 3 * (P31 - 1), 3 * (P31 - 1), 4, 1, 1, 1, F32, 0, None) == _lib.ENOGPU
+        assert lib.dfft_stft1d(a, b, c, 2 * P31, 4, 2, 0, P31 - 1, 1, F32, 0, 1, 1.0, None) == _lib.ENOGPU
+        assert lib.dfft_istft1d(b, a, c, c + 4096, 2 * P31, 4, 2, 0, P31 - 1, 1, F32, None) == _lib.ENOGPU
