@@ -354,6 +354,8 @@ int dfft_plan_destroy(dfft_plan_t plan);
  * (out == in) or out of place; byte ranges that overlap only partly: DFFT_EINVAL, checked before the device is queried; with out != in,
  * `in` is never written (the four-step and Bluestein forms work through scratch); nothing outside the batch * n (* width) elements of
  * `out` is written; batch == 0 writes nothing and returns DFFT_OK.
+ * Lines are independent in all four: no row, column or plane shares arithmetic with another, so a line of NaN, of zeros or of any
+ * magnitude leaves every other line of the batch bit-identical, and nothing outside `in` that is read reaches a result.
  * In-place or out-of-place length-n C2C FFT of `batch` contiguous rows (stride n). */
 int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
 /* Length-n FFT down the columns of a [n][width] row-major matrix, `batch` matrices back to back.
@@ -407,7 +409,9 @@ unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, lo
  * bin n/2 are ignored).  Unnormalised, out of place (the byte ranges of in and out must not overlap: DFFT_EINVAL), `in` is never
  * written.  Form 1 runs the half-length kernels of the r2c plans; forms 2 and 3 pair rows 2p and 2p + 1 in one n-point complex
  * transform (an odd last row is paired with a zero row, or its partner's output dropped), so each row's rounding error is bounded
- * relative to its pair's combined magnitude.  Scratch and Bluestein tables come from the caches dfft_trim frees. */
+ * relative to its pair's combined magnitude.  Nothing else is shared: form 1 rows are independent, and in forms 2 and 3 a row of NaN
+ * or of any magnitude reaches its partner and no other row (every row outside the pair stays bit-identical).  Scratch and Bluestein
+ * tables come from the caches dfft_trim frees. */
 int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream);
 
 /* Real transforms along the middle axis of [batch][n][s] (s = 1: dfft_rfft1d, bit-identical), for ANY n of dfft_length_kind 1, 2 or 3.
@@ -415,7 +419,8 @@ int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, in
  * axis=1) for ANY input (the imaginary parts of bin 0 and, n even, bin n/2 are ignored).  Unnormalised, out of place (overlapping byte
  * ranges of in and out: DFFT_EINVAL), `in` is never written; any s >= 1 and any element-aligned pointers.  Real columns 2c and 2c + 1 share
  * one n-point complex transform down the column pair (an odd last column is paired with a zero column), so each column's rounding error
- * is bounded relative to its pair's combined magnitude.  Tuned single-pass n (n * s < 2^31) run as one launch; every other n in batch
+ * is bounded relative to its pair's combined magnitude.  Pairs never span two [n][s] items, and a column of NaN or of any magnitude
+ * reaches its partner and no other column.  Tuned single-pass n (n * s < 2^31) run as one launch; every other n in batch
  * chunks on the four-step / Bluestein / run-time-scheduled transforms with scratch from the caches dfft_trim frees.  Arguments are checked
  * before the device is queried. */
 int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long batch, int dtype, int direction, void* stream);
@@ -425,7 +430,14 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
  * numpy.fft.irfft2(X, s=(n1, n2)) for ANY input (inverse C2C along n1, then C2R along n2 with numpy's rule for the imaginary parts).
  * Unnormalised, out of place (overlap: DFFT_EINVAL), `in` is never written.  Planes are processed in groups sized for the 256 MiB
  * Infinity Cache: R2C rows (dfft_rfft1d) then the n1-point columns in place on `out` (dfft_fft1d_any); backward the inverse columns
- * into a scratch group, then C2R rows into `out`.  Arguments are checked before the device is queried. */
+ * into a scratch group, then C2R rows into `out`.  Arguments are checked before the device is queried.
+ * WHICH PLANES SHARE ARITHMETIC: the rows of a plane group -- all `batch` planes while their bins fit 256 MiB, else the evened chunk of
+ * planes dfft_fft2d_batch takes -- go through dfft_rfft1d's row transform as ONE batch of planes_in_group * n1 rows.  n2 of real form 1,
+ * or even n1: planes are independent.  n2 of form 2 or 3 with odd n1: rows 2p and 2p + 1 of that flattened batch pair up, so the last
+ * row of the group's plane 2q shares a transform with the first row of its plane 2q + 1 (the last row of an odd last plane goes with
+ * zeros), and each of the two planes' rounding error is bounded relative to their combined magnitude.  Forward the column pass spreads
+ * what crosses over the whole neighbouring plane (a NaN plane makes its partner plane NaN throughout); backward only over that one row.
+ * No other plane is reached, in either direction. */
 int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long batch, int dtype, int direction, void* stream);
 
 /* Real-to-real transforms along the middle axis of reals [batch][n][s] (s = 1: contiguous rows), for ANY n of dfft_length_kind 1, 2 or 3
@@ -437,7 +449,8 @@ int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long
  * so type III of type II is 2n x.  Types I and IV are NOT built.  dtype DFFT_F64 (double) or DFFT_F32 (float).  Out of place or exactly
  * in place (out == in); byte ranges that overlap only partly: DFFT_EINVAL; with out != in, `in` is never written.  Any s >= 1 and any
  * element-aligned pointers.  Adjacent columns 2c, 2c + 1 (s > 1) or rows 2p, 2p + 1 (s = 1) share one n-point complex transform (an odd
- * last one is paired with zeros), so each one's rounding error is bounded relative to its pair's combined magnitude.  Tuned single-pass
+ * last one is paired with zeros), so each one's rounding error is bounded relative to its pair's combined magnitude; column pairs never
+ * span two [n][s] items, and nothing reaches a line outside the pair.  Tuned single-pass
  * n (for s > 1: n * s < 2^31) run as ONE launch that moves the field once in and once out (csrc/dfft_r2r.hip); every other n, and every n
  * under DFFT_R2R_FUSED=0 (read per call), runs pre kernel -> n-point transform -> post kernel in batch chunks.  Scratch, the quarter-wave
  * tables and the Bluestein tables come from the caches dfft_trim frees; a call allocates nothing once they are warm.  Arguments are
@@ -460,7 +473,8 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
  * Longer sequences run block by block through dfft_rconv1d_os below (overlap-save); four-step and Bluestein halves are NOT built.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the
  * batch); NULL pointers, sizes below 1, m < n, a bad dtype or filter kind, in and out overlapping partly, h overlapping out:
  * DFFT_EINVAL -- all decided before the device is queried.  out == in (exactly) is allowed; with out != in, `in` is never written; h is
- * never written; nothing outside the batch * channels * n reals of out is written.
+ * never written; nothing outside the batch * channels * n reals of out is written.  Rows are independent (no pairing, on either route): a
+ * row of NaN or of any magnitude leaves every other row bit-identical, and filter row c reaches exactly the rows of channel c.
  * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_rconv.hip) that loads the n reals of a row, runs the forward m/2-point
  * transform, splits, multiplies, merges and runs the inverse in registers and LDS, and stores n reals: the row is read once and written
  * once, the zero padding and the spectrum never exist in memory.  Every other accepted m, the few (m/2, dtype) whose kernels would spill
@@ -487,7 +501,8 @@ long long dfft_rconv1d_length(long long at_least);
  * < 2^31 block items (element offsets are 64-bit); any element-aligned pointers.  NULL pointers, sizes out of range, a bad dtype or
  * filter kind, in and out overlapping AT ALL (blocks read what their neighbours write: there is no in-place form), h overlapping out:
  * DFFT_EINVAL; every other m, and 2^31 or more items: DFFT_EUNSUPPORTED -- all decided before the device is queried.  in and h are never
- * written; nothing outside the batch * channels * n_out reals of out is written.
+ * written; nothing outside the batch * channels * n_out reals of out is written.  Rows are independent; inside a row a sample reaches
+ * the results of the blocks that read it (a NaN at in[r, j] makes at least out[r, j ... j + discard] NaN, and may spread over those blocks).
  * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_osconv.hip): the kernel of dfft_rconv1d run per (row, block) item with the
  * load base, the store window and the filter row taken from the item -- the padded blocks, the dropped samples and the spectrum never
  * exist in memory; two reals per access where n, n_out and discard are even and both pointers are aligned to two reals.  Every other
@@ -515,7 +530,10 @@ int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long*
  * element-aligned pointers.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the batch); NULL pointers, sizes below 1,
  * m < n, a bad dtype or filter kind, in and out overlapping partly, hp overlapping out: DFFT_EINVAL -- all decided before the device is
  * queried.  out == in (exactly) is allowed; with out != in, `in` is never written; hp is never written; nothing outside the
- * batch * channels * n reals of out is written.  Bluestein halves, strided rows and autograd are NOT built.
+ * batch * channels * n reals of out is written.  On the three-launch route rows are independent (its per-pair step pairs scratch rows
+ * of ONE input row); on the composed route below rows 2p and 2p + 1 of the batch * channels rows share their transforms, as in
+ * dfft_rfft1d's real form 3, and each row's rounding error is bounded relative to its pair's combined magnitude.
+ * Bluestein halves, strided rows and autograd are NOT built.
  * The call is THREE launches per chunk of rows (csrc/dfft_lconv.hip), the fused kernel of dfft_rconv1d cut along the four-step
  * decomposition: N1-point columns read straight from the reals (times the four-step twiddle) into M complex of scratch per row; per pair
  * of scratch rows the N2-point transform, the split / multiply / merge step and the N2-point inverse, in place; the inverse N1-point columns
@@ -547,6 +565,8 @@ unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, lon
  * rows * frames < 2^31 items (element offsets are 64-bit); any element-aligned pointers.  NULL pointers, sizes out of range, a bad
  * dtype, pad mode or out kind, reflect padding with pad >= n, in, out and win overlapping: DFFT_EINVAL; every other m, and 2^31 or more
  * items: DFFT_EUNSUPPORTED -- all decided before the device is queried.  in and win are never written; nothing outside out is written.
+ * Every (row, frame) is computed on its own: a sample reaches exactly the frames whose support (mirror images included) holds it, and
+ * every other frame of every row stays bit-identical; the inverse likewise -- a frame reaches exactly the samples under its support.
  * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_stft.hip): the thread group of an item reads its frame straight from the
  * row -- two reals per access for whole frames where n, hop and pad are even and `in` is aligned to two reals, else real by real with
  * the zero or mirrored index --, applies the window in registers, transforms, and stores the bins or their squared moduli: the framed
