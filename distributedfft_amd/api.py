@@ -735,11 +735,8 @@ def rconv1d_length(at_least: int) -> int:
     return int(L.load().dfft_rconv1d_length(int(at_least)))
 
 
-def rconv1d(x, H, m: Optional[int] = None, out=None):
-    """y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c], m)[:n] for every row of a contiguous float64 / float32
-    device tensor (..., channels, n) (dfft_rconv1d).  H is (channels, m//2 + 1) of the matching complex dtype, or of x's own dtype (a
-    real filter: half the filter bytes); m defaults to 2 * (H.shape[-1] - 1) and must be a length rconv1d_length returns.  m == n is
-    the circular convolution, m >= n + taps - 1 the head of the linear one.  Normalised: H == 1 gives y == x.  out=x runs in place."""
+def _rconv1d_args(x, H, m):
+    """The argument checks of rconv1d -> (m, channels, n, batch)"""
     import math
 
     import torch
@@ -750,29 +747,156 @@ def rconv1d(x, H, m: Optional[int] = None, out=None):
         f"H must be a contiguous {cdt} or {x.dtype} tensor (channels, m//2 + 1) on {x.device}"
     m = 2 * (int(H.shape[-1]) - 1) if m is None else int(m)
     assert tuple(H.shape) == (channels, m // 2 + 1), f"H must have shape {(channels, m // 2 + 1)}, got {tuple(H.shape)}"
+    return m, channels, n, math.prod(int(v) for v in x.shape[:-2])
+
+
+def _rconv1d_run(x, H, m, out):
+    """rconv1d without autograd: one dfft_rconv1d call"""
+    import torch
+    m, channels, n, batch = _rconv1d_args(x, H, m)
     out = _check_out(x, out)
-    batch = math.prod(int(v) for v in x.shape[:-2])
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_rconv1d(x.data_ptr(), out.data_ptr(), H.data_ptr(), n, m, channels, batch, F64 if x.dtype == torch.float64 else F32,
-                                      FILTER_COMPLEX if H.dtype == cdt else FILTER_REAL, None), "dfft_rconv1d")
+                                      FILTER_REAL if H.dtype == x.dtype else FILTER_COMPLEX, None), "dfft_rconv1d")
         torch.cuda.synchronize()
     return out
+
+
+def _fftconv1d_filter(k, m):
+    """rfft1d of the taps k (channels, taps) zero-padded to m"""
+    import torch
+    kp = torch.zeros((int(k.shape[0]), m), dtype=k.dtype, device=k.device)
+    kp[:, :int(k.shape[-1])] = k
+    return rfft1d(kp)
+
+
+_AUTOGRAD = []
+
+
+def _autograd_functions():
+    """(rconv1d, fftconv1d) as torch.autograd.Function subclasses, defined on first use: this module imports torch inside functions only.
+        grad_x = rconv1d(g, conj(H), m)
+        grad_H = w / m * rxspec1d(x, g, m),  w = 1 at bins 0 and m/2, 2 elsewhere (its real part for a real H)
+        grad_k = irfft1d(rxspec1d(x, g, m), m)[:, :taps] / m
+    (g: the gradient of the output).  Backward is once_differentiable and launches nothing for an input that needs no gradient."""
+    if _AUTOGRAD:
+        return _AUTOGRAD[0]
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def grad_x(g, H, m):
+        return _rconv1d_run(g, H.conj().resolve_conj().contiguous() if H.is_complex() else H, m, None)
+
+    class Rconv1dFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, H, m):
+            ctx.save_for_backward(x, H)
+            ctx.m = m
+            return _rconv1d_run(x, H, m, None)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            x, H = ctx.saved_tensors
+            g = g.contiguous()
+            gx = grad_x(g, H, ctx.m) if ctx.needs_input_grad[0] else None
+            gH = None
+            if ctx.needs_input_grad[1]:
+                gH = rxspec1d(x, g, ctx.m)
+                w = torch.full((ctx.m // 2 + 1,), 2.0 / ctx.m, dtype=x.dtype, device=x.device)
+                w[0] = w[-1] = 1.0 / ctx.m
+                gH = gH * w if H.is_complex() else (gH.real * w).contiguous()
+            return gx, gH, None
+
+    class Fftconv1dFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, k, m):
+            H = _fftconv1d_filter(k, m)
+            ctx.save_for_backward(x, H)
+            ctx.m, ctx.taps = m, int(k.shape[-1])
+            return _rconv1d_run(x, H, m, None)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            x, H = ctx.saved_tensors
+            g = g.contiguous()
+            gx = grad_x(g, H, ctx.m) if ctx.needs_input_grad[0] else None
+            gk = None
+            if ctx.needs_input_grad[1]:
+                gk = (irfft1d(rxspec1d(x, g, ctx.m), ctx.m)[:, :ctx.taps] / ctx.m).contiguous()
+            return gx, gk, None
+
+    _AUTOGRAD.append((Rconv1dFn, Fftconv1dFn))
+    return _AUTOGRAD[0]
+
+
+def _wants_grad(*tensors):
+    import torch
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def rxspec1d(x, g, m: int, out=None):
+    """S[c, k] = sum over the batch of conj(numpy.fft.rfft(x[..., c, :], m)[k]) * numpy.fft.rfft(g[..., c, :], m)[k], k = 0 ... m//2, for two
+    contiguous float64 / float32 device tensors (..., channels, n) of one shape (dfft_rxspec1d) -> (channels, m//2 + 1) of the matching
+    complex dtype, unnormalised.  m must be a length rconv1d_length returns.  g is x gives the auto-spectrum sum |X|^2 with exact-zero
+    imaginary parts.  The result is the same bits from call to call.  A windowed (Welch) form and autograd of rxspec1d itself are not
+    built."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    assert g.is_cuda and g.device == x.device and g.is_contiguous() and g.dtype == x.dtype and g.shape == x.shape, \
+        f"g must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}"
+    m = int(m)
+    channels, n = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    shape = (channels, m // 2 + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=cdt, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == cdt and out.device == x.device and out.is_contiguous(), \
+        f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rxspec1d(x.data_ptr(), g.data_ptr(), out.data_ptr(), n, m, channels, batch, F64 if x.dtype == torch.float64 else F32, None),
+                "dfft_rxspec1d")
+        torch.cuda.synchronize()
+    return out
+
+
+def rconv1d(x, H, m: Optional[int] = None, out=None):
+    """y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c], m)[:n] for every row of a contiguous float64 / float32
+    device tensor (..., channels, n) (dfft_rconv1d).  H is (channels, m//2 + 1) of the matching complex dtype, or of x's own dtype (a
+    real filter: half the filter bytes); m defaults to 2 * (H.shape[-1] - 1) and must be a length rconv1d_length returns.  m == n is
+    the circular convolution, m >= n + taps - 1 the head of the linear one.  Normalised: H == 1 gives y == x.  out=x runs in place.
+    Differentiable in x and H (grad mode on and either requires grad; out= is then a ValueError): the input gradient is rconv1d with the
+    conjugated filter, the filter gradient rxspec1d.  Double backward is not built, and rconv1d_os / fftfilt1d and rconv1d_long /
+    fftconv1d_long are not differentiable."""
+    if _wants_grad(x, H):
+        if out is not None:
+            raise ValueError("rconv1d: out= cannot be combined with a tensor that requires grad")
+        m = _rconv1d_args(x, H, m)[0]
+        return _autograd_functions()[0].apply(x, H, m)
+    return _rconv1d_run(x, H, m, out)
 
 
 def fftconv1d(x, k, out=None):
     """numpy.convolve(x[..., c, :], k[c])[:n] for every row of a contiguous float64 / float32 device tensor (..., channels, n): the
     causal "long convolution" with the real taps k (channels, taps), through rconv1d on m = rconv1d_length(n + taps - 1) with the
-    filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 8192."""
-    import torch
+    filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 8192.  Differentiable in x and k (grad mode on and
+    either requires grad; out= is then a ValueError); double backward is not built."""
     assert x.is_cuda and x.dim() >= 2 and k.is_cuda and k.dim() == 2 and k.dtype == x.dtype and k.device == x.device
     channels, n, taps = int(x.shape[-2]), int(x.shape[-1]), int(k.shape[-1])
     assert int(k.shape[0]) == channels, f"k must hold one row of taps per channel: ({channels}, taps), got {tuple(k.shape)}"
     m = rconv1d_length(n + taps - 1)
     if m == 0:
         raise ValueError(f"fftconv1d: n + taps - 1 = {n + taps - 1} is beyond the longest padded length (8192)")
-    kp = torch.zeros((channels, m), dtype=k.dtype, device=k.device)
-    kp[:, :taps] = k
-    return rconv1d(x, rfft1d(kp), m, out=out)
+    if _wants_grad(x, k):
+        if out is not None:
+            raise ValueError("fftconv1d: out= cannot be combined with a tensor that requires grad")
+        assert x.is_contiguous() and x.dtype.is_floating_point and x.numel() > 0
+        return _autograd_functions()[1].apply(x, k, m)
+    return rconv1d(x, _fftconv1d_filter(k, m), m, out=out)
 
 
 def rconv1d_long_length(at_least: int) -> int:

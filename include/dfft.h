@@ -489,6 +489,37 @@ int dfft_rconv1d_fused_applies(long long n, long long m, int dtype, int filter_k
 unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
 long long dfft_rconv1d_length(long long at_least);
 
+/* Batched 1-D real cross-spectrum, summed over the batch: x and g are rows of reals [batch][channels][n] as in dfft_rconv1d,
+ *     out[c, k] = sum_b conj(numpy.fft.rfft(x[b, c, :], m)[k]) * numpy.fft.rfft(g[b, c, :], m)[k],     k = 0 ... m/2,
+ * out [channels][m/2 + 1] of the complex type, unnormalised.  It is the filter gradient of dfft_rconv1d (g the gradient of its output;
+ * the input gradient is dfft_rconv1d itself with the conjugated filter), and the Welch / cross-spectral-density / matched-filter
+ * accumulation; g == x (exactly) is allowed and gives the auto-spectrum sum_b |X|^2.  The imaginary parts of out[c][0] and out[c][m/2]
+ * are stored as exact zeros (and every imaginary part of the auto-spectrum).  dtype DFFT_F64 (double) or DFFT_F32 (float).
+ * Accepted: the sizes of dfft_rconv1d -- 1 <= n <= m, dfft_real_form(m) == 1 (so m <= 8192), channels >= 1, batch >= 1,
+ * batch * channels < 2^31 rows; any element-aligned pointers.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the
+ * batch and add the results); NULL pointers, sizes below 1, m < n, a bad dtype, out overlapping x or g: DFFT_EINVAL -- all decided
+ * before the device is queried.  x and g are never written; nothing outside the channels * (m/2 + 1) elements of out is written.  A row
+ * (b, c) reaches every bin of out[c] and nothing of any other channel.
+ * The result is the same bits from call to call: no floating-point atomics.  The batch is cut into dfft_rxspec1d_slices contiguous
+ * ranges, the first batch % slices of them one row longer -- host arithmetic on fixed constants, never on the device that is present:
+ * slices = max(1, min(target / channels, batch / 8)), target = 512 * min(G, 8) items with G the thread groups per workgroup of the
+ * m/2-point kernel (about the resident thread groups of a 256-CU part; G = 1 where m/2 has no tuned plan), so a slice holds at least 8
+ * rows -- each slice is summed in row order and the slices are added in slice order, all in the working precision.
+ * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_xspec.hip), plus a small one that adds the slices where there are
+ * several: a thread group per (slice, channel) loads the n reals of a row of x, runs the forward m/2-point transform and forms the
+ * row's bins in registers, does the same for g, and accumulates the products in registers -- each row of either field is read once
+ * and nothing is written per row.  Every other accepted m, the few (m/2, dtype) whose kernels would spill or measured slower, and every
+ * m under DFFT_RXSPEC_FUSED=0 (read per call) run pad -> R2C rows on both fields -> a multiply-accumulate in row order, in chunks of
+ * rows of at most max(256 MiB, one row's) scratch from the per-(device, stream) buffer dfft_trim frees; a call allocates nothing once
+ * that is warm.  dfft_rxspec1d_fused_applies tells the route (vec: n even and both fields aligned to two reals; the route does not
+ * depend on it), dfft_rxspec1d_scratch_bytes the lease (the partial sums of the slices, 0 for one slice; the chunk on the composed
+ * route; 0 for a call that is refused), dfft_rxspec1d_slices the slice count (0 for sizes that are refused).  All three are host
+ * arithmetic. */
+int dfft_rxspec1d(const void* x, const void* g, void* out, long long n, long long m, long long channels, long long batch, int dtype, void* stream);
+int dfft_rxspec1d_fused_applies(long long n, long long m, int dtype, int vec);
+unsigned long long dfft_rxspec1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
+long long dfft_rxspec1d_slices(long long m, long long channels, long long batch, int dtype);
+
 /* Overlap-save form of dfft_rconv1d for rows of ANY length: in [batch][channels][n], out [batch][channels][n_out], h [channels][m/2 + 1]
  * as above.  m is the block length and `discard` (d) the samples dropped per block; with S = m - d and nb = ceil(n_out / S), block b of
  * row r is
