@@ -116,6 +116,10 @@ SIGNATURES = {
     "dfft_rconv1d_long": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_rconv1d_long_fused_applies": (C.c_int, [_LL, C.c_int]),
     "dfft_rconv1d_long_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, C.c_int]),
+    "dfft_rxspec1d_long": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
+    "dfft_rxspec1d_long_fused_applies": (C.c_int, [_LL, C.c_int]),
+    "dfft_rxspec1d_long_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, C.c_int]),
+    "dfft_rxspec1d_long_slices": (_LL, [_LL, _LL, _LL, C.c_int]),
     "dfft_stft1d": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, _LL, C.c_int, C.c_int, C.c_int, C.c_double, _VP]),
     "dfft_istft1d": (C.c_int, [_VP, _VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, _LL, C.c_int, _VP]),
     "dfft_stft1d_frames": (_LL, [_LL, _LL, _LL, _LL]),

@@ -870,8 +870,8 @@ def rconv1d(x, H, m: Optional[int] = None, out=None):
     real filter: half the filter bytes); m defaults to 2 * (H.shape[-1] - 1) and must be a length rconv1d_length returns.  m == n is
     the circular convolution, m >= n + taps - 1 the head of the linear one.  Normalised: H == 1 gives y == x.  out=x runs in place.
     Differentiable in x and H (grad mode on and either requires grad; out= is then a ValueError): the input gradient is rconv1d with the
-    conjugated filter, the filter gradient rxspec1d.  Double backward is not built, and rconv1d_os / fftfilt1d and rconv1d_long /
-    fftconv1d_long are not differentiable."""
+    conjugated filter, the filter gradient rxspec1d.  Double backward is not built, and rconv1d_os / fftfilt1d are not differentiable
+    (rconv1d_long / fftconv1d_long are)."""
     if _wants_grad(x, H):
         if out is not None:
             raise ValueError("rconv1d: out= cannot be combined with a tensor that requires grad")
@@ -923,11 +923,8 @@ def rconv1d_long_filter(H, m: Optional[int] = None):
     return Hp
 
 
-def rconv1d_long(x, Hp, m: Optional[int] = None, out=None):
-    """rconv1d for padded lengths beyond 8192 (dfft_rconv1d_long): y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c],
-    m)[:n] for every row of a contiguous float64 / float32 device tensor (..., channels, n), with Hp = rconv1d_long_filter(H).  m
-    defaults to 2 * (Hp.shape[-1] - 1) and must be a length rconv1d_long_length returns.  Normalised: H == 1 gives y == x.  out=x runs
-    in place."""
+def _rconv1d_long_args(x, Hp, m):
+    """The argument checks of rconv1d_long -> (m, channels, n, batch)"""
     import math
 
     import torch
@@ -938,8 +935,15 @@ def rconv1d_long(x, Hp, m: Optional[int] = None, out=None):
         f"Hp must be a contiguous {cdt} or {x.dtype} tensor (channels, m//2 + 1) on {x.device}"
     m = 2 * (int(Hp.shape[-1]) - 1) if m is None else int(m)
     assert tuple(Hp.shape) == (channels, m // 2 + 1), f"Hp must have shape {(channels, m // 2 + 1)}, got {tuple(Hp.shape)}"
+    return m, channels, n, math.prod(int(v) for v in x.shape[:-2])
+
+
+def _rconv1d_long_run(x, Hp, m, out):
+    """rconv1d_long without autograd: one dfft_rconv1d_long call"""
+    import torch
+    m, channels, n, batch = _rconv1d_long_args(x, Hp, m)
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
     out = _check_out(x, out)
-    batch = math.prod(int(v) for v in x.shape[:-2])
     with torch.cuda.device(x.device):
         L.check(L.load().dfft_rconv1d_long(x.data_ptr(), out.data_ptr(), Hp.data_ptr(), n, m, channels, batch,
                                            F64 if x.dtype == torch.float64 else F32, FILTER_COMPLEX if Hp.dtype == cdt else FILTER_REAL, None),
@@ -948,11 +952,125 @@ def rconv1d_long(x, Hp, m: Optional[int] = None, out=None):
     return out
 
 
+def _fftconv1d_long_filter(k, m):
+    """rfft1d of the taps k (channels, taps) zero-padded to m, in the order rconv1d_long reads it"""
+    import torch
+    kp = torch.zeros((int(k.shape[0]), m), dtype=k.dtype, device=k.device)
+    kp[:, :int(k.shape[-1])] = k
+    return rconv1d_long_filter(rfft1d(kp))
+
+
+_AUTOGRAD_LONG = []
+
+
+def _autograd_functions_long():
+    """(rconv1d_long, fftconv1d_long) as torch.autograd.Function subclasses, defined on first use (see _autograd_functions):
+        grad_x  = rconv1d_long(g, conj(Hp), m)          (conjugation commutes with the permutation of rconv1d_long_filter)
+        grad_Hp = w / m * rxspec1d_long(x, g, m, filter_order=True),  w = 1 at bins 0 and m/2 -- positions 0 and m/2 of the permuted
+                  order as well -- and 2 elsewhere (its real part for a real Hp)
+        grad_k  = irfft1d(rxspec1d_long(x, g, m), m)[:, :taps] / m
+    (g: the gradient of the output).  Backward is once_differentiable and launches nothing for an input that needs no gradient."""
+    if _AUTOGRAD_LONG:
+        return _AUTOGRAD_LONG[0]
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def grad_x(g, Hp, m):
+        return _rconv1d_long_run(g, Hp.conj().resolve_conj().contiguous() if Hp.is_complex() else Hp, m, None)
+
+    class Rconv1dLongFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, Hp, m):
+            ctx.save_for_backward(x, Hp)
+            ctx.m = m
+            return _rconv1d_long_run(x, Hp, m, None)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            x, Hp = ctx.saved_tensors
+            g = g.contiguous()
+            gx = grad_x(g, Hp, ctx.m) if ctx.needs_input_grad[0] else None
+            gH = None
+            if ctx.needs_input_grad[1]:
+                gH = rxspec1d_long(x, g, ctx.m, filter_order=True)
+                w = torch.full((ctx.m // 2 + 1,), 2.0 / ctx.m, dtype=x.dtype, device=x.device)
+                w[0] = w[-1] = 1.0 / ctx.m
+                gH = gH * w if Hp.is_complex() else (gH.real * w).contiguous()
+            return gx, gH, None
+
+    class Fftconv1dLongFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, k, m):
+            Hp = _fftconv1d_long_filter(k, m)
+            ctx.save_for_backward(x, Hp)
+            ctx.m, ctx.taps = m, int(k.shape[-1])
+            return _rconv1d_long_run(x, Hp, m, None)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            x, Hp = ctx.saved_tensors
+            g = g.contiguous()
+            gx = grad_x(g, Hp, ctx.m) if ctx.needs_input_grad[0] else None
+            gk = None
+            if ctx.needs_input_grad[1]:
+                gk = (irfft1d(rxspec1d_long(x, g, ctx.m), ctx.m)[:, :ctx.taps] / ctx.m).contiguous()
+            return gx, gk, None
+
+    _AUTOGRAD_LONG.append((Rconv1dLongFn, Fftconv1dLongFn))
+    return _AUTOGRAD_LONG[0]
+
+
+def rxspec1d_long(x, g, m: int, out=None, filter_order: bool = False):
+    """rxspec1d for padded lengths beyond 8192 (dfft_rxspec1d_long): S[c, k] = sum over the batch of conj(numpy.fft.rfft(x[..., c, :], m)[k])
+    * numpy.fft.rfft(g[..., c, :], m)[k], k = 0 ... m//2, for two contiguous float64 / float32 device tensors (..., channels, n) of one
+    shape -> (channels, m//2 + 1) of the matching complex dtype, unnormalised.  m must be a length rconv1d_long_length returns.
+    filter_order=True returns the layout of rconv1d_long_filter (S[c, k1 + N1 * k2] at position k1 * N2 + k2).  g is x gives the
+    auto-spectrum sum |X|^2 with exact-zero imaginary parts.  The result is the same bits from call to call.  A windowed (Welch) form
+    and autograd of rxspec1d_long itself are not built."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 2 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    assert g.is_cuda and g.device == x.device and g.is_contiguous() and g.dtype == x.dtype and g.shape == x.shape, \
+        f"g must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}"
+    m = int(m)
+    channels, n = int(x.shape[-2]), int(x.shape[-1])
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    shape = (channels, m // 2 + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=cdt, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == cdt and out.device == x.device and out.is_contiguous(), \
+        f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
+    batch = math.prod(int(v) for v in x.shape[:-2])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rxspec1d_long(x.data_ptr(), g.data_ptr(), out.data_ptr(), n, m, channels, batch,
+                                            F64 if x.dtype == torch.float64 else F32, 1 if filter_order else 0, None), "dfft_rxspec1d_long")
+        torch.cuda.synchronize()
+    return out
+
+
+def rconv1d_long(x, Hp, m: Optional[int] = None, out=None):
+    """rconv1d for padded lengths beyond 8192 (dfft_rconv1d_long): y[..., c, :] = numpy.fft.irfft(numpy.fft.rfft(x[..., c, :], m) * H[c],
+    m)[:n] for every row of a contiguous float64 / float32 device tensor (..., channels, n), with Hp = rconv1d_long_filter(H).  m
+    defaults to 2 * (Hp.shape[-1] - 1) and must be a length rconv1d_long_length returns.  Normalised: H == 1 gives y == x.  out=x runs
+    in place.  Differentiable in x and Hp, complex or real (grad mode on and either requires grad; out= is then a ValueError): the
+    input gradient is rconv1d_long with the conjugated filter, the filter gradient rxspec1d_long in the filter's order.  Double
+    backward is not built."""
+    if _wants_grad(x, Hp):
+        if out is not None:
+            raise ValueError("rconv1d_long: out= cannot be combined with a tensor that requires grad")
+        m = _rconv1d_long_args(x, Hp, m)[0]
+        return _autograd_functions_long()[0].apply(x, Hp, m)
+    return _rconv1d_long_run(x, Hp, m, out)
+
+
 def fftconv1d_long(x, k, out=None):
     """fftconv1d for n + taps - 1 > 8192: numpy.convolve(x[..., c, :], k[c])[:n] for every row of a contiguous float64 / float32 device
     tensor (..., channels, n) with the real taps k (channels, taps), through rconv1d_long on m = rconv1d_long_length(n + taps - 1) with
-    the filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 2^23."""
-    import torch
+    the filter spectrum rfft1d of the zero-padded taps.  n + taps - 1 must not exceed 2^23.  Differentiable in x and k (grad mode on
+    and either requires grad; out= is then a ValueError); double backward is not built."""
     assert x.is_cuda and x.dim() >= 2 and k.is_cuda and k.dim() == 2 and k.dtype == x.dtype and k.device == x.device
     channels, n, taps = int(x.shape[-2]), int(x.shape[-1]), int(k.shape[-1])
     assert int(k.shape[0]) == channels, f"k must hold one row of taps per channel: ({channels}, taps), got {tuple(k.shape)}"
@@ -961,9 +1079,12 @@ def fftconv1d_long(x, k, out=None):
     m = rconv1d_long_length(n + taps - 1)
     if m == 0:
         raise ValueError(f"fftconv1d_long: n + taps - 1 = {n + taps - 1} is beyond the longest padded length (2^23)")
-    kp = torch.zeros((channels, m), dtype=k.dtype, device=k.device)
-    kp[:, :taps] = k
-    return rconv1d_long(x, rconv1d_long_filter(rfft1d(kp)), m, out=out)
+    if _wants_grad(x, k):
+        if out is not None:
+            raise ValueError("fftconv1d_long: out= cannot be combined with a tensor that requires grad")
+        assert x.is_contiguous() and x.dtype.is_floating_point and x.numel() > 0
+        return _autograd_functions_long()[1].apply(x, k, m)
+    return rconv1d_long(x, _fftconv1d_long_filter(k, m), m, out=out)
 
 
 def rconv1d_os_block(taps: int, n_out: int, dtype) -> tuple:

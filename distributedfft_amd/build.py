@@ -122,6 +122,10 @@ def units():
     # plus the dispatcher, the slice reduction and the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_xspec.hip", OBJ / f"dfft_xspec_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # long 1-D real cross-spectrum (the filter gradient of the long convolution): pass A and the accumulating row-pair kernels of the factor
+    # lengths of each group, plus the dispatcher, the slice reduction and the kernels of the composed form
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_lxspec.hip", OBJ / f"dfft_lxspec_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))

@@ -1,10 +1,12 @@
 // dfft_batch.cpp -- the plan-less batched entry points: complex and real 1-D transforms along rows or a strided axis, batched 2-D
-// transforms, real-to-real transforms, the 1-D real FFT convolution with its overlap-save and long forms, dfft_scale and dfft_trim.
+// transforms, real-to-real transforms, the 1-D real FFT convolution with its overlap-save and long forms, the long cross-spectrum,
+// dfft_scale and dfft_trim.
 #include <map>
 #include <mutex>
 #include <tuple>
 
 #include "dfft_lconv.h"
+#include "dfft_lxspec.h"
 #include "dfft_osconv.h"
 #include "dfft_plan_impl.h"
 #include "dfft_r2r.h"
@@ -638,6 +640,79 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
         if (int rc = lconv_mul(bins, hp, m, r0, channels, k, dtype, filter_kind, st)) return rc;
         if (int rc = real_rows_run(Rb, bins, pad, k, inner, st)) return rc;
         if (int rc = lconv_trunc(pad, (char*)out + (size_t)r0 * n * rs, n, m, k, dtype, st)) return rc;
+    }
+    return DFFT_OK;
+}
+
+// Long 1-D real cross-spectrum (dfft_lxspec.hip): dfft_rxspec1d at the padded lengths of dfft_rconv1d_long
+static bool lxspec_rows_ok(long long channels, long long batch) {
+    return channels < (1ll << 31) && batch < (1ll << 31) && batch * channels < (1ll << 31);
+}
+
+int dfft_rxspec1d_long_fused_applies(long long m, int dtype) { return valid_dtype(dtype) && lxspec_fused_env() && lxspec_fused(m, dtype); }
+
+long long dfft_rxspec1d_long_slices(long long m, long long channels, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || m < 1 || channels < 1 || batch < 1 || !lxspec_rows_ok(channels, batch) || !lconv_split(m, nullptr, nullptr)) return 0;
+    return lxspec_slices(m, channels, lxspec_chunk_rows(m, dtype, batch * channels));
+}
+
+unsigned long long dfft_rxspec1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || !lxspec_rows_ok(channels, batch)) return 0;
+    return lxspec_scratch_bytes(m, dtype, channels, batch * channels);
+}
+
+int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, long long m, long long channels, long long batch, int dtype, int order,
+                       void* stream) {
+    if (!x || !g || !out || n < 1 || m < 1 || channels < 1 || batch < 1 || m < n || !valid_dtype(dtype) || (order != 0 && order != 1))
+        return fail(DFFT_EINVAL, "dfft_rxspec1d_long: bad arguments");
+    if (!lconv_split(m, nullptr, nullptr)) return fail(DFFT_EUNSUPPORTED, lconv_length_message("dfft_rxspec1d_long", m));
+    if (!lxspec_rows_ok(channels, batch)) return fail(DFFT_EUNSUPPORTED, "dfft_rxspec1d_long: batch * channels = 2^31 or more rows: split the batch");
+    const size_t    cs = elem_bytes(dtype), rs = cs / 2;
+    const long long rows = batch * channels, nh = m / 2 + 1;
+    const uintptr_t ibytes = (uintptr_t)rows * n * rs, obytes = (uintptr_t)channels * nh * cs;
+    if (ranges_overlap(x, ibytes, out, obytes) || ranges_overlap(g, ibytes, out, obytes))
+        return fail(DFFT_EINVAL, "dfft_rxspec1d_long: out overlaps x or g");
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rxspec1d_long: no HIP device visible (no CPU fallback)");
+    const hipStream_t st = (hipStream_t)stream;
+    ScratchLease      lease;
+    if (lxspec_fused_env() && lxspec_fused(m, dtype)) {
+        LxspecLaunch L;
+        std::memset(&L, 0, sizeof(L));
+        L.dtype = dtype;
+        L.order = order;
+        L.n = n;
+        L.m = m;
+        L.channels = channels;
+        L.batch = batch;
+        L.x = x;
+        L.g = g;
+        L.out = out;
+        const size_t need = lxspec_scratch_bytes(m, dtype, channels, rows);
+        if (!lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rxspec1d_long: cannot allocate the scratch buffer");
+        return lxspec_run(L, lease.get(), need, st);
+    }
+    // composed route, per chunk of rows of at most max(256 MiB, one row's) bins of both fields and padded rows: pad, the real rows of
+    // length m as dfft_rfft1d runs them, on both fields, and the kernel that adds each channel's rows to out in row order -- on ONE lease
+    const bool      autos = x == g;
+    const size_t    rb = 2 * (size_t)nh * cs + (size_t)m * rs;
+    const long long nr = std::max(1ll, std::min(rows, (long long)(std::max((size_t)(256ull << 20), rb) / rb)));
+    RealRowsPass    Rf;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
+    const size_t data_b = ((size_t)nr * rb + 255) / 256 * 256;
+    if (!lease.acquire(data_b + Rf.need, st)) return fail(DFFT_EHIP, "dfft_rxspec1d_long: cannot allocate the scratch buffer");
+    char* xb = (char*)lease.get();           // [nr][nh] complex
+    char* gb = xb + (size_t)nr * nh * cs;    // [nr][nh] complex
+    char* pad = gb + (size_t)nr * nh * cs;   // [nr][m] reals, shared by the two fields
+    void* inner = xb + data_b;
+    for (long long r0 = 0; r0 < rows; r0 += nr) {
+        const long long k = std::min(nr, rows - r0);
+        if (int rc = lxspec_pad((const char*)x + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+        if (int rc = real_rows_run(Rf, pad, xb, k, inner, st)) return rc;
+        if (!autos) {
+            if (int rc = lxspec_pad((const char*)g + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+            if (int rc = real_rows_run(Rf, pad, gb, k, inner, st)) return rc;
+        }
+        if (int rc = lxspec_mac(xb, autos ? xb : gb, out, m, r0, k, channels, dtype, order, st)) return rc;
     }
     return DFFT_OK;
 }

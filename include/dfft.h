@@ -564,7 +564,8 @@ int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long*
  * batch * channels * n reals of out is written.  On the three-launch route rows are independent (its per-pair step pairs scratch rows
  * of ONE input row); on the composed route below rows 2p and 2p + 1 of the batch * channels rows share their transforms, as in
  * dfft_rfft1d's real form 3, and each row's rounding error is bounded relative to its pair's combined magnitude.
- * Bluestein halves, strided rows and autograd are NOT built.
+ * Bluestein halves and strided rows are NOT built.  Gradients: the input gradient is this call with the conjugated filter, the filter
+ * gradient dfft_rxspec1d_long below.
  * The call is THREE launches per chunk of rows (csrc/dfft_lconv.hip), the fused kernel of dfft_rconv1d cut along the four-step
  * decomposition: N1-point columns read straight from the reals (times the four-step twiddle) into M complex of scratch per row; per pair
  * of scratch rows the N2-point transform, the split / multiply / merge step and the N2-point inverse, in place; the inverse N1-point columns
@@ -582,6 +583,39 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
                       void* stream);
 int dfft_rconv1d_long_fused_applies(long long m, int dtype);
 unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
+
+/* dfft_rxspec1d for the padded lengths of dfft_rconv1d_long (the filter gradient of that convolution): the same definition,
+ *     out[c, k] = sum_b conj(numpy.fft.rfft(x[b, c, :], m)[k]) * numpy.fft.rfft(g[b, c, :], m)[k],        out [channels][m/2 + 1] complex,
+ * unnormalised, the imaginary parts of bins 0 and m/2 exact zeros, g == x (exactly) the auto-spectrum with exact-zero imaginary parts
+ * throughout.  order 0 stores the bins in natural order; order 1 in the order of dfft_rconv1d_long_filter (out[c][k1 * N2 + k2] =
+ * S[c][k1 + N1 * k2], out[c][M] = S[c][M]).  Accepted m: exactly those of dfft_rconv1d_long_split; 1 <= n <= m, channels >= 1, batch >= 1,
+ * batch * channels < 2^31 rows.  Every other m: DFFT_EUNSUPPORTED (and 2^31 or more rows: split the batch); NULL pointers, sizes below 1,
+ * m < n, a bad dtype or order, out overlapping x or g: DFFT_EINVAL -- all decided before the device is queried.  x and g are never written.
+ * Fused route (csrc/dfft_lxspec.hip), per chunk of rows: pass A of dfft_rconv1d_long on both fields (one for the auto-spectrum) into
+ * M = m/2 complex of scratch per row and field; an accumulating kernel with one item per (slice, channel, pair of scratch rows) that, for
+ * every row of its channel and slice in order, runs the N2-point transforms of x and g, forms 2 X[k] and 2 G[k] of its own bins and adds
+ * conj(X[k]) G[k] to running sums in registers (nothing is written per row); a reduction over the slices that writes `out` in the requested
+ * order -- 2 n + 4 m reals of traffic per row pair.  NO floating-point atomics, and the cuts are host arithmetic on (m, channels, batch,
+ * dtype) and fixed constants, never the device:
+ *   chunks  the batch * channels rows, in order, in chunks of max(1, min(rows, max(256 MiB, rb) / rb)) rows, rb = 2 * M complex (both
+ *           fields; counted so also for the auto-spectrum);
+ *   slices  a channel has at most steps = ceil(chunk rows / channels) rows in a chunk; they are cut into
+ *           max(1, min(2048 / (channels * ceil(N1 / 2)), steps / 8)) contiguous ranges, the first steps % slices one step longer
+ *           (channels * ceil(N1 / 2) items exist with one slice already);
+ *   order   rows of a slice in order, then the slices in order (their sum), then the chunks in order (out += the chunk's sum).
+ * So every bit of the result is the same from call to call.  A call of one chunk and one slice in order 1 stores straight to out.
+ * The splits whose accumulating kernel would keep values in scratch memory (csrc/dfft_lxspec.hip: lxspec_fused_ok), and every m under
+ * DFFT_RXSPEC_LONG_FUSED=0 (read per call), run the composed route: pad -> the real rows of length m as dfft_rfft1d runs them, on both
+ * fields -> a kernel that adds each channel's rows to out in row order; deterministic as well, in chunks of at most max(256 MiB, one
+ * row's) bins and padded rows.  dfft_rxspec1d_long_fused_applies tells the route; dfft_rxspec1d_long_slices the slice count of the first
+ * (the largest) chunk; dfft_rxspec1d_long_scratch_bytes the lease of the fused route: (chunk rows * 2 * M + slices * channels * (M + 1))
+ * complex (0 for sizes that are refused; the composed route leases its bins, padded rows and the transforms' own scratch instead).  All
+ * three are host arithmetic.  A windowed (Welch) form, Bluestein halves and strided rows are NOT built. */
+int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, long long m, long long channels, long long batch, int dtype, int order,
+                       void* stream);
+int dfft_rxspec1d_long_fused_applies(long long m, int dtype);
+unsigned long long dfft_rxspec1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype);
+long long dfft_rxspec1d_long_slices(long long m, long long channels, long long batch, int dtype);
 
 /* Batched short-time Fourier transform and its inverse (unnormalised, numpy conventions).  Rows of reals in [rows][n], a window win [m]
  * of reals, frames of m reals that advance by hop >= 1, 0 <= pad < m samples of padding in front of every row.  Frame f of row r is
