@@ -106,6 +106,10 @@ SIGNATURES = {
     "dfft_rxspec1d_fused_applies": (C.c_int, [_LL, _LL, C.c_int, C.c_int]),
     "dfft_rxspec1d_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, C.c_int]),
     "dfft_rxspec1d_slices": (_LL, [_LL, _LL, _LL, C.c_int]),
+    "dfft_rcsd1d": (C.c_int, [_VP, _VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, C.c_double, C.c_int, _VP]),
+    "dfft_rcsd1d_fused_applies": (C.c_int, [_LL, C.c_int, C.c_int]),
+    "dfft_rcsd1d_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int, C.c_int]),
+    "dfft_rcsd1d_slices": (_LL, [_LL, _LL, _LL, C.c_int]),
     "dfft_rconv1d_os": (C.c_int, [_VP, _VP, _VP, _LL, _LL, _LL, _LL, _LL, _LL, C.c_int, C.c_int, _VP]),
     "dfft_rconv1d_os_fused_applies": (C.c_int, [_LL, C.c_int]),
     "dfft_rconv1d_os_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, _LL, _LL, C.c_int]),

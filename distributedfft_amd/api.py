@@ -840,8 +840,8 @@ def rxspec1d(x, g, m: int, out=None):
     """S[c, k] = sum over the batch of conj(numpy.fft.rfft(x[..., c, :], m)[k]) * numpy.fft.rfft(g[..., c, :], m)[k], k = 0 ... m//2, for two
     contiguous float64 / float32 device tensors (..., channels, n) of one shape (dfft_rxspec1d) -> (channels, m//2 + 1) of the matching
     complex dtype, unnormalised.  m must be a length rconv1d_length returns.  g is x gives the auto-spectrum sum |X|^2 with exact-zero
-    imaginary parts.  The result is the same bits from call to call.  A windowed (Welch) form and autograd of rxspec1d itself are not
-    built."""
+    imaginary parts.  The result is the same bits from call to call.  The framed, windowed (Welch) sum is rcsd1d.  Autograd of rxspec1d
+    itself is not built."""
     import math
 
     import torch
@@ -1027,8 +1027,8 @@ def rxspec1d_long(x, g, m: int, out=None, filter_order: bool = False):
     * numpy.fft.rfft(g[..., c, :], m)[k], k = 0 ... m//2, for two contiguous float64 / float32 device tensors (..., channels, n) of one
     shape -> (channels, m//2 + 1) of the matching complex dtype, unnormalised.  m must be a length rconv1d_long_length returns.
     filter_order=True returns the layout of rconv1d_long_filter (S[c, k1 + N1 * k2] at position k1 * N2 + k2).  g is x gives the
-    auto-spectrum sum |X|^2 with exact-zero imaginary parts.  The result is the same bits from call to call.  A windowed (Welch) form
-    and autograd of rxspec1d_long itself are not built."""
+    auto-spectrum sum |X|^2 with exact-zero imaginary parts.  The result is the same bits from call to call.  The framed,
+    windowed (Welch) sum is rcsd1d, for frames of at most 8192 samples.  Autograd of rxspec1d_long itself is not built."""
     import math
 
     import torch
@@ -1288,6 +1288,100 @@ def istft(X, n_fft: int, hop_length: Optional[int] = None, window=None, center: 
         out[..., :have] = dst
         out[..., have:] = 0
     return out
+
+
+def rcsd1d(x, g, n_fft: int, hop_length: int, window=None, scale: float = 1.0, out=None, win_length: Optional[int] = None):
+    """scale * sum over the frames f of conj(numpy.fft.rfft(w * x[..., f hop : f hop + n_fft])) * numpy.fft.rfft(w * g[..., f hop : f hop + n_fft])
+    for two contiguous float64 / float32 device tensors (..., n) of one shape (dfft_rcsd1d) -> (..., n_fft // 2 + 1) of the matching
+    complex dtype: the raw sum that welch / csd / coherence average.  Frames are whole and start at sample 0 (no padding, no centring):
+    1 + (n - n_fft) // hop_length of them, and the samples behind the last one are not read.  `window`: None (rectangular) or a 1-D
+    tensor of win_length (default n_fft) values, centred and zero-padded as in stft.  n_fft must be of real form 1 (even, n_fft // 2 a
+    single-pass length, at most 8192).  g is x gives the auto-spectrum with exact-zero imaginary parts.  The result is the same bits
+    from call to call.  No autograd."""
+    import math
+
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1 and x.dtype in (torch.float64, torch.float32) and x.numel() > 0
+    assert g.is_cuda and g.device == x.device and g.is_contiguous() and g.dtype == x.dtype and g.shape == x.shape, \
+        f"g must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}"
+    n_fft, hop, n = int(n_fft), int(hop_length), int(x.shape[-1])
+    if hop < 1:
+        raise ValueError(f"hop_length must be at least 1, got {hop}")
+    frames = stft_frames(n, n_fft, hop, 0)
+    if frames < 1:
+        raise ValueError(f"rows of {n} samples are shorter than one frame of n_fft = {n_fft}")
+    w = _stft_window(window, n_fft, win_length, x.dtype, x.device)
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    shape = tuple(x.shape[:-1]) + (n_fft // 2 + 1,)
+    if out is None:
+        out = torch.empty(shape, dtype=cdt, device=x.device)
+    assert out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == cdt and tuple(out.shape) == shape, \
+        f"out must be a contiguous {cdt} tensor of shape {shape} on {x.device}"
+    rows = math.prod(int(v) for v in x.shape[:-1])
+    with torch.cuda.device(x.device):
+        L.check(L.load().dfft_rcsd1d(x.data_ptr(), g.data_ptr(), out.data_ptr(), w.data_ptr(), n, n_fft, hop, frames, rows, float(scale),
+                                     F64 if x.dtype == torch.float64 else F32, None), "dfft_rcsd1d")
+        torch.cuda.synchronize()
+    return out
+
+
+def _csd_setup(x, n_fft, hop_length, window, fs, scaling, win_length):
+    """hop, window tensor (win_length values) and the scale 1 / (fs sum w^2) ("density") or 1 / (sum w)^2 ("spectrum"), over frames"""
+    import torch
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    n_fft = int(n_fft)
+    hop = n_fft // 2 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    if window is None:
+        window = torch.hann_window(wl, periodic=True, dtype=torch.float64, device=x.device)
+    w64 = window.to(device=x.device, dtype=x.dtype).to(torch.float64)   # the values the frames are multiplied by
+    norm = 1.0 / (float(fs) * float((w64 * w64).sum())) if scaling == "density" else 1.0 / float(w64.sum()) ** 2
+    return hop, window, norm
+
+
+def _one_sided(P, n_fft, norm, frames):
+    """the mean over frames, the normalisation, and every bin but 0 and n_fft / 2 doubled -- on the small result"""
+    P = P * (norm / frames)
+    P[..., 1:n_fft // 2] *= 2.0
+    return P
+
+
+def csd(x, y, n_fft: int, hop_length: Optional[int] = None, window=None, fs: float = 1.0, scaling: str = "density", win_length: Optional[int] = None):
+    """scipy.signal.csd(x, y, fs, window, nperseg=n_fft, noverlap=n_fft - hop_length, detrend=False, scaling=scaling) of two contiguous
+    float64 / float32 device tensors (..., n) of one shape: the one-sided cross-spectral density (or spectrum) mean_f conj(X_f) Y_f ->
+    (..., n_fft // 2 + 1) complex, from one launch of rcsd1d that reads each row once and writes no spectrogram.  hop_length defaults
+    to n_fft // 2, window to the periodic Hann window (a 1-D tensor of win_length values otherwise, centred and zero-padded to n_fft).
+    Normalisation 1 / (fs sum w^2) for "density", 1 / (sum w)^2 for "spectrum"; every bin but 0 and n_fft / 2 is doubled.
+    Not built: per-segment detrending, average="median", two-sided output, padding / boundary extension, frames longer than 8192, and
+    autograd."""
+    n_fft = int(n_fft)
+    hop, window, norm = _csd_setup(x, n_fft, hop_length, window, fs, scaling, win_length)
+    P = rcsd1d(x, y, n_fft, hop, window, win_length=win_length)
+    return _one_sided(P, n_fft, norm, stft_frames(int(x.shape[-1]), n_fft, hop, 0))
+
+
+def welch(x, n_fft: int, hop_length: Optional[int] = None, window=None, fs: float = 1.0, scaling: str = "density", win_length: Optional[int] = None):
+    """scipy.signal.welch(x, fs, window, nperseg=n_fft, noverlap=n_fft - hop_length, detrend=False, scaling=scaling): the one-sided power
+    spectral density (or spectrum) mean_f |X_f|^2 of a contiguous float64 / float32 device tensor (..., n) -> (..., n_fft // 2 + 1) real
+    (csd with y is x: the second transform is skipped).  Arguments, and what is not built, as in csd.  No autograd."""
+    n_fft = int(n_fft)
+    hop, window, norm = _csd_setup(x, n_fft, hop_length, window, fs, scaling, win_length)
+    P = rcsd1d(x, x, n_fft, hop, window, win_length=win_length)
+    return _one_sided(P.real.contiguous(), n_fft, norm, stft_frames(int(x.shape[-1]), n_fft, hop, 0))
+
+
+def coherence(x, y, n_fft: int, hop_length: Optional[int] = None, window=None, win_length: Optional[int] = None):
+    """scipy.signal.coherence(x, y, window=window, nperseg=n_fft, noverlap=n_fft - hop_length, detrend=False): the magnitude-squared
+    coherence |Pxy|^2 / (Pxx Pyy) of two contiguous float64 / float32 device tensors (..., n) of one shape -> (..., n_fft // 2 + 1) real,
+    from three launches of rcsd1d (the normalisation cancels).  One frame gives 1.  Arguments, and what is not built, as in csd.  No
+    autograd."""
+    n_fft = int(n_fft)
+    hop, window, _ = _csd_setup(x, n_fft, hop_length, window, 1.0, "density", win_length)
+    pxy = rcsd1d(x, y, n_fft, hop, window, win_length=win_length)
+    pxx = rcsd1d(x, x, n_fft, hop, window, win_length=win_length).real
+    pyy = rcsd1d(y, y, n_fft, hop, window, win_length=win_length).real
+    return (pxy.real * pxy.real + pxy.imag * pxy.imag) / (pxx * pyy)
 
 
 def rfft2d_batch(x, out=None):

@@ -24,7 +24,7 @@ ARCH = "gfx950"
 NUM_INST_GROUPS = 12  # keep in sync with csrc/dfft_plans.h
 # host-side units (csrc/<name>.cpp).  All of them are compiled as HIP: the plan units take the launch structs from the kernel headers (dfft_zy.h and friends)
 HOST_UNITS = ["dfft_core", "dfft_passes", "dfft_plan", "dfft_plan_tune", "dfft_plan_r2c", "dfft_plan_conv", "dfft_batch",
-              "dfft_stft_api", "dfft_xspec_api", "dfft_exchange", "dfft_bootstrap", "dfft_alloc", "dfft_trace"]
+              "dfft_stft_api", "dfft_xspec_api", "dfft_csd_api", "dfft_exchange", "dfft_bootstrap", "dfft_alloc", "dfft_trace"]
 
 # --offload-compress: the gfx950 code objects are stored zstd-compressed and unpacked by the HIP runtime when the library is loaded
 # (65 MB -> 18.5 MB per .so; process start and the benchmark unchanged, profiles/r05/experiments/compress_smoke.log)
@@ -126,6 +126,10 @@ def units():
     # lengths of each group, plus the dispatcher, the slice reduction and the kernels of the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_lxspec.hip", OBJ / f"dfft_lxspec_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # framed (Welch) 1-D real cross-spectrum: the frame kernels of the tuned half-lengths of each group, plus the dispatcher, the slice
+    # reduction and the composed form
+    for g in range(NUM_INST_GROUPS + 1):
+        out.append((CSRC / "dfft_csd.hip", OBJ / f"dfft_csd_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))

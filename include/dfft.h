@@ -610,7 +610,7 @@ unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, lon
  * row's) bins and padded rows.  dfft_rxspec1d_long_fused_applies tells the route; dfft_rxspec1d_long_slices the slice count of the first
  * (the largest) chunk; dfft_rxspec1d_long_scratch_bytes the lease of the fused route: (chunk rows * 2 * M + slices * channels * (M + 1))
  * complex (0 for sizes that are refused; the composed route leases its bins, padded rows and the transforms' own scratch instead).  All
- * three are host arithmetic.  A windowed (Welch) form, Bluestein halves and strided rows are NOT built. */
+ * three are host arithmetic.  Bluestein halves and strided rows are NOT built (the framed, windowed form is dfft_rcsd1d, m <= 8192). */
 int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, long long m, long long channels, long long batch, int dtype, int order,
                        void* stream);
 int dfft_rxspec1d_long_fused_applies(long long m, int dtype);
@@ -663,6 +663,43 @@ long long dfft_stft1d_frames(long long n, long long m, long long hop, long long 
 int dfft_stft1d_fused_applies(long long m, int dtype);
 unsigned long long dfft_stft1d_scratch_bytes(long long m, long long frames, long long rows, int dtype, int out_kind);
 unsigned long long dfft_istft1d_scratch_bytes(long long m, long long frames, long long rows, int dtype);
+
+/* Framed (Welch) 1-D real cross-spectrum: x and g are rows of reals [rows][n], win [m] a window of reals, frames of m reals that advance
+ * by hop >= 1 with no padding and no centring -- frame f of a row is its samples [f hop, f hop + m) --
+ *     out[r, k] = scale * sum_f conj(numpy.fft.rfft(win * x[r, f hop : f hop + m])[k]) * numpy.fft.rfft(win * g[r, f hop : f hop + m])[k],
+ * k = 0 ... m/2, out [rows][m/2 + 1] of the complex type: the sum that scipy.signal.welch / csd / coherence average (detrend=False).
+ * frames must be dfft_stft1d_frames(n, m, hop, 0) = 1 + (n - m) / hop >= 1; the samples behind the last whole frame, and for hop > m the
+ * samples between frames, are never read.  g == x (exactly) gives the auto-spectrum sum_f |X_f|^2 with every imaginary part an exact
+ * zero; the imaginary parts of out[r][0] and out[r][m/2] are exact zeros always.  dtype DFFT_F64 (double) or DFFT_F32 (float).
+ * Accepted: dfft_real_form(m) == 1 (m even, m/2 a single-pass length, so m <= 8192), n >= m, rows >= 1, rows (and so rows * slices)
+ * and frames below 2^31 each; any element-aligned pointers.  NULL pointers, sizes out of range, a frame count other than the one above, a
+ * bad dtype, out overlapping x, g or win: DFFT_EINVAL; every other m, and 2^31 or more rows or frames (split the rows; split a row at a
+ * multiple of hop and add the results): DFFT_EUNSUPPORTED -- all decided before the device is queried.  x, g and win are never written;
+ * nothing outside the rows * (m/2 + 1) elements of out is written.  A row reaches its own line of out and no other.
+ * The result is the same bits from call to call: no floating-point atomics.  The frames of a row are cut into dfft_rcsd1d_slices
+ * contiguous ranges, the first frames % slices of them one frame longer -- host arithmetic on fixed constants, never on the device that
+ * is present: slices = max(1, min(target / rows, frames / 8)), target = 512 * min(G, 32) items with G the thread groups per workgroup of
+ * the m/2-point kernel (G = 1 where m/2 has no tuned plan) -- each slice is summed in frame order and the slices are added in slice
+ * order, all in the working precision.
+ * Where m/2 has a tuned plan the call is ONE launch (csrc/dfft_csd.hip), plus a small one that adds the slices where there are several:
+ * a thread group per (slice, row) reads a frame of x straight from the row -- two reals per access where n and hop are even and both
+ * fields are aligned to two reals, else real by real --, applies the window in registers, transforms and forms the frame's bins in
+ * registers, does the same for g (g == x has a lighter kernel of its own: one transform, real sums), and accumulates the products in
+ * registers.  A row comes from memory once (its overlapping frames are consecutive trips of one thread group) and m/2 + 1 bins are
+ * written per row: neither a spectrogram nor a framed copy exists.  Every other accepted m, the (m/2, dtype, auto or cross) whose
+ * kernels would spill or measured no faster, and every m under DFFT_RCSD_FUSED=0 (read per call) run, in chunks of frames of at most
+ * max(256 MiB, one frame's) scratch (DFFT_RCSD_CHUNK_BYTES, read per call, lowers the cap; the result does not depend on the chunking)
+ * from the per-(device, stream) buffer dfft_trim frees: the bins (auto: squared moduli) of the chunk's frames by the frame kernel of
+ * dfft_stft1d where that is built, else gather-and-window -> R2C rows, then a multiply-accumulate in frame order.
+ * dfft_rcsd1d_fused_applies tells the route (autos: g == x), dfft_rcsd1d_scratch_bytes the lease (the
+ * partial sums of the slices, 0 for one slice; the chunk on the composed route; 0 for sizes that are refused), dfft_rcsd1d_slices the
+ * slice count (0 for sizes that are refused).  All three are host arithmetic.
+ * NOT built: per-frame detrending, median averaging, two-sided output, padding / centring, frames longer than 8192 and a backward form. */
+int dfft_rcsd1d(const void* x, const void* g, void* out, const void* win, long long n, long long m, long long hop, long long frames, long long rows,
+                double scale, int dtype, void* stream);
+int dfft_rcsd1d_fused_applies(long long m, int dtype, int autos);
+unsigned long long dfft_rcsd1d_scratch_bytes(long long m, long long frames, long long rows, int dtype, int autos);
+long long dfft_rcsd1d_slices(long long m, long long rows, long long frames, int dtype);
 
 /* ---- batched 2D transform (templateFFT's FFTDim = 2 application: initializeFFT, templateFFT.cpp:5767, launched by fftZY,
  * fft_mpi_3d_api.cpp:466-522; component benchmark templateFFT/batchTest/Test_2D.cpp:29-198) ---------------------------------
