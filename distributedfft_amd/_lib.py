@@ -132,6 +132,12 @@ SIGNATURES = {
     "dfft_istft1d_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int]),
     "dfft_scale": (C.c_int, [_VP, _LL, C.c_int, C.c_double, _VP]),
     "dfft_trim": (C.c_int, []),
+    "dfft_rfft1d_scratch_bytes": (C.c_ulonglong, [_LL, _LL, C.c_int, C.c_int]),
+    "dfft_rfft2d_batch_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int, C.c_int]),
+    "dfft_fft2d_batch_scratch_bytes": (C.c_ulonglong, [_LL, _LL, _LL, C.c_int]),
+    "dfft_debug_scratch_fill": (C.c_int, [C.c_ulonglong, C.c_int, _VP]),
+    "dfft_debug_scratch_capacity": (C.c_ulonglong, [_VP]),
+    "dfft_debug_scratch_count": (_LL, [C.c_int, _VP]),
     "dfft_boot_init": (C.c_int, []),
     "dfft_boot_rank": (C.c_int, []),
     "dfft_boot_size": (C.c_int, []),

@@ -76,7 +76,9 @@ struct RealRowsPass {
     bool               bs_fused;
     size_t             need;      // scratch bytes
 };
-static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, RealRowsPass* R) {
+// sizes_only: tables that carry n, M and the dtype alone stand in for the cached ones -- the lease queries, which touch no device
+static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, RealRowsPass* R,
+                             const BluesteinTables* sizes_only = nullptr) {
     const size_t    cs = elem_bytes(dtype);
     const long long nh = n / 2 + 1;
     // rows as one plane: real pitch n, complex pitch nh; at most 2^30 rows per launch (an even count: pairs never straddle two calls)
@@ -101,10 +103,10 @@ static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bo
         return DFFT_OK;
     }
     // two-for-one pairs: the cached Bluestein tables of (n, dtype, direction) for Bluestein lengths
-    if (length_kind(n) == 3)
+    if (length_kind(n) == 3 && !sizes_only)
         if (int rc = bluestein_tables(n, dtype, dir, &R->t)) return rc;
     R->bs_fused = bluestein_fused_env();
-    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), R->t.get(), R->bs_fused);
+    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), length_kind(n) == 3 && sizes_only ? sizes_only : R->t.get(), R->bs_fused);
     return DFFT_OK;
 }
 static int real_rows_run(const RealRowsPass& R, const void* in, void* out, long long rows, void* scr, hipStream_t st) {
@@ -166,7 +168,7 @@ struct AnyPass {
     bool               bs_fused;
     size_t             need;
 };
-static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, AnyPass* A) {
+static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, AnyPass* A, const BluesteinTables* sizes_only = nullptr) {
     A->n = n;
     A->s = s;
     A->dtype = dtype;
@@ -176,8 +178,9 @@ static int any_prepare(long long n, long long s, long long batch, int dtype, int
     A->bs_fused = bluestein_fused_env();
     A->need = A->kind == 2 ? (size_t)batch * n * s * elem_bytes(dtype) : 0;
     if (A->kind == 3) {
-        if (int rc = bluestein_tables(n, dtype, dir, &A->t)) return rc;
-        A->need = bluestein_scratch_bytes(*A->t, s, batch, A->bs_fused);
+        if (!sizes_only)
+            if (int rc = bluestein_tables(n, dtype, dir, &A->t)) return rc;
+        A->need = bluestein_scratch_bytes(sizes_only ? *sizes_only : *A->t, s, batch, A->bs_fused);
     }
     return DFFT_OK;
 }
@@ -187,7 +190,60 @@ static int any_run(const AnyPass& A, const void* in, void* out, long long batch,
     return A.s == 1 ? dfft_fft1d_rows((void*)in, out, A.n, batch, A.dtype, A.dir, st) : dfft_fft1d_cols((void*)in, out, A.n, A.s, batch, A.dtype, A.dir, st);
 }
 
+static void sizes_only_tables(BluesteinTables* T, long long n, int dtype, int dir) {
+    T->n = n;
+    T->M = bluestein_padded_length(n);
+    T->dtype = dtype;
+    T->dir = dir;
+}
+
 extern "C" {
+
+// ---- test hooks: the per-(device, stream) scratch buffer as earlier calls left it (dfft_long.hip).  Without a device they touch none.
+int dfft_debug_scratch_fill(unsigned long long at_least_bytes, int byte, void* stream) {
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_debug_scratch_fill: no HIP device visible");
+    return long_scratch_debug_fill((size_t)at_least_bytes, byte, (hipStream_t)stream);
+}
+unsigned long long dfft_debug_scratch_capacity(void* stream) {
+    if (dfft_device_count() < 1) return 0;
+    return long_scratch_debug_capacity((hipStream_t)stream);
+}
+long long dfft_debug_scratch_count(int byte, void* stream) {
+    if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_debug_scratch_count: no HIP device visible");
+    return long_scratch_debug_count(byte, (hipStream_t)stream);
+}
+
+// ---- the leases of dfft_rfft1d, dfft_rfft2d_batch and dfft_fft2d_batch by the routines' own rules (host arithmetic, no device): the
+// largest single lease of the call, which is what the grow-only buffer holds afterwards; 0: none, or sizes that are refused
+unsigned long long dfft_rfft1d_scratch_bytes(long long n, long long batch, int dtype, int direction) {
+    if (!valid_dtype(dtype) || !valid_direction(direction) || batch < 1 || real_form(n) == 0) return 0;
+    BluesteinTables T;
+    sizes_only_tables(&T, n, dtype, direction);
+    RealRowsPass R;
+    if (real_rows_prepare(n, batch, dtype, direction, false, &R, &T)) return 0;
+    return R.need;
+}
+unsigned long long dfft_rfft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype, int direction) {
+    if (!valid_dtype(dtype) || !valid_direction(direction) || n1 < 1 || n2 < 1 || batch < 1 || real_form(n2) == 0 || length_kind(n1) == 0) return 0;
+    const bool      fwd = direction == DFFT_FORWARD;
+    const long long nh = n2 / 2 + 1;
+    const uintptr_t cplane_b = (uintptr_t)n1 * nh * elem_bytes(dtype);
+    const long long cp = cache_plane_group(batch, (long long)cplane_b);
+    BluesteinTables T2, T1;
+    sizes_only_tables(&T2, n2, dtype, direction);
+    sizes_only_tables(&T1, n1, dtype, direction);
+    RealRowsPass R;
+    if (real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, &R, &T2)) return 0;
+    if (fwd) return std::max<unsigned long long>(R.need, dfft_fft1d_any_scratch_bytes(n1, nh, cp, dtype));  // two leases, one after the other
+    AnyPass A;
+    if (any_prepare(n1, nh, cp, dtype, direction, &A, &T1)) return 0;
+    return (unsigned long long)cp * cplane_b + std::max(R.need, A.need);
+}
+unsigned long long dfft_fft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype) {
+    if (!valid_dtype(dtype) || n1 < 1 || n2 < 1 || batch < 1 || !dfft_length_supported(n1) || !dfft_length_supported(n2)) return 0;
+    if (n1 <= 4096 && n2 <= 4096) return 0;  // single-pass axes, the one-launch stage included: no scratch
+    return (unsigned long long)batch * n1 * n2 * elem_bytes(dtype);  // the four-step axis on dfft_fft1d_rows / dfft_fft1d_cols: as much as the data
+}
 
 int dfft_fft1d_rows(void* in, void* out, long long n, long long batch, int dtype, int direction, void* stream) {
     if (!in || !out || batch < 0 || !valid_dtype(dtype) || !valid_direction(direction))

@@ -17,5 +17,11 @@ typedef void* LongScratchLease;
 void* long_scratch(size_t bytes, hipStream_t stream, LongScratchLease* lease);
 void  long_scratch_release(LongScratchLease lease);
 void  long_scratch_trim();  // frees every cached buffer that is not leased (dfft_trim); drains the owning devices first
+// Test hooks behind dfft_debug_scratch_* (include/dfft.h), all on the buffer of (current device, stream) and under its lease:
+// fill grows it to at least `at_least_bytes` by long_scratch's rule and enqueues a memset of the whole cached buffer; capacity is the
+// bytes cached (0: none); count waits for the stream and counts the bytes equal to `byte` on the host (negative: a DFFT_E* code).
+int       long_scratch_debug_fill(size_t at_least_bytes, int byte, hipStream_t stream);
+size_t    long_scratch_debug_capacity(hipStream_t stream);
+long long long_scratch_debug_count(int byte, hipStream_t stream);
 
 }  // namespace dfft

@@ -270,6 +270,49 @@ void long_scratch_trim() {
     if (have_cur) (void)hipSetDevice(cur);
 }
 
+// ---- test hooks (dfft_debug_scratch_*): what an earlier call left in the cached buffer of (current device, stream), made visible and
+// settable.  They go through the same lease as every caller; none of them creates an entry that is not there, except the fill.
+static ScratchEntry* scratch_entry_if_any(hipStream_t stream) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(g_mutex);
+    auto                        it = g_scratch.find(std::make_pair(dev, stream));
+    return it == g_scratch.end() ? nullptr : it->second.get();
+}
+
+int long_scratch_debug_fill(size_t at_least_bytes, int byte, hipStream_t stream) {
+    LongScratchLease lease = nullptr;
+    void*            p = long_scratch(at_least_bytes, stream, &lease);
+    if (!lease) return fail(DFFT_EHIP, "dfft_debug_scratch_fill: cannot allocate the scratch buffer");
+    hipError_t e = hipSuccess;
+    if (p) e = hipMemsetAsync(p, byte & 0xff, static_cast<ScratchEntry*>(lease)->bytes, stream);  // the WHOLE cached buffer
+    long_scratch_release(lease);
+    if (e != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_debug_scratch_fill: ") + hipGetErrorString(e));
+    return DFFT_OK;
+}
+
+size_t long_scratch_debug_capacity(hipStream_t stream) {
+    ScratchEntry* e = scratch_entry_if_any(stream);
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->m);
+    return e->p ? e->bytes : 0;
+}
+
+long long long_scratch_debug_count(int byte, hipStream_t stream) {
+    ScratchEntry* e = scratch_entry_if_any(stream);
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->m);  // the lease: no call enqueues on this buffer while it is read
+    if (!e->p || !e->bytes) return 0;
+    hipError_t err = hipStreamSynchronize(stream);
+    std::vector<unsigned char> h(e->bytes);
+    if (err == hipSuccess) err = hipMemcpy(h.data(), e->p, e->bytes, hipMemcpyDeviceToHost);
+    if (err != hipSuccess) return fail(DFFT_EHIP, std::string("dfft_debug_scratch_count: ") + hipGetErrorString(err));
+    return (long long)std::count(h.begin(), h.end(), (unsigned char)(byte & 0xff));
+}
+
 int long_fft(const void* in, void* out, long long n, long long s, long long batch, int dtype, int dir, double scale, void* scratch,
              hipStream_t stream) {
     int N1 = 0, N2 = 0;

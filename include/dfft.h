@@ -723,6 +723,29 @@ int dfft_fft2d_batch_status(void* stream);
  * Buffers in use by a call in progress are left alone.  No counterpart in the reference. */
 int dfft_trim(void);
 
+/* The leases of dfft_rfft1d, dfft_rfft2d_batch and dfft_fft2d_batch from that buffer, by the routines' own rules (host arithmetic, no
+ * device is queried): the largest single lease of the call -- what the grow-only buffer holds after it -- and 0 for none or for sizes
+ * that are refused.  dfft_rfft1d: 0 for real form 1 (forward, and backward with a tuned n/2; else the copy of a chunk's bins), the
+ * paired transforms' scratch for forms 2 and 3.  dfft_rfft2d_batch: forward the larger of the row pass's and dfft_fft1d_any's, backward
+ * the bins of a plane group plus the larger of the two passes' own.  dfft_fft2d_batch: nothing for single-pass axes (the one-launch
+ * stage included), as much as the data where an axis runs four-step. */
+unsigned long long dfft_rfft1d_scratch_bytes(long long n, long long batch, int dtype, int direction);
+unsigned long long dfft_rfft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype, int direction);
+unsigned long long dfft_fft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype);
+
+/* TEST HOOKS, not part of the transform interface: the scratch buffer of (current device, stream) as earlier calls left it.  They take the
+ * same lease as every plan-less call.  tests/test_gpu_call_mix.py fills the buffer with NaN bit patterns (byte 0xFF: every fp32 and fp64
+ * word a NaN) or zeros before a call and shows that the call's result does not depend on it.
+ *   dfft_debug_scratch_fill      grows the buffer to at least_bytes by the usual rule (a smaller one is freed behind a stream wait), then
+ *                                enqueues a memset of the WHOLE cached buffer with `byte` on `stream`.  DFFT_OK or a DFFT_E* code.
+ *   dfft_debug_scratch_capacity  the bytes cached for (current device, stream); 0 when there are none.
+ *   dfft_debug_scratch_count     waits for `stream`, copies the buffer to the host and returns how many of its bytes equal `byte`
+ *                                (0 with no buffer; a negative DFFT_E* code on failure).
+ * Without a device: DFFT_ENOGPU, 0 and DFFT_ENOGPU; none is touched. */
+int dfft_debug_scratch_fill(unsigned long long at_least_bytes, int byte, void* stream);
+unsigned long long dfft_debug_scratch_capacity(void* stream);
+long long dfft_debug_scratch_count(int byte, void* stream);
+
 /* data[i] *= s for `count` complex elements on the device (the 1/N normalisation both transforms leave to the caller;
  * the reference's scale_element kernel, kernel_func.cpp:102-157, used only by 3dmpifft_roc). */
 int dfft_scale(void* data, long long count, int dtype, double s, void* stream);
