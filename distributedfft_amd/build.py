@@ -119,17 +119,19 @@ def units():
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_stft.hip", OBJ / f"dfft_stft_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # batched 1-D real cross-spectrum (the filter gradient of the convolution): the fused kernels of the tuned half-lengths of each group,
-    # plus the dispatcher, the slice reduction and the composed form
+    # plus the dispatcher and the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_xspec.hip", OBJ / f"dfft_xspec_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
     # long 1-D real cross-spectrum (the filter gradient of the long convolution): pass A and the accumulating row-pair kernels of the factor
     # lengths of each group, plus the dispatcher, the slice reduction and the kernels of the composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_lxspec.hip", OBJ / f"dfft_lxspec_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
-    # framed (Welch) 1-D real cross-spectrum: the frame kernels of the tuned half-lengths of each group, plus the dispatcher, the slice
-    # reduction and the composed form
+    # framed (Welch) 1-D real cross-spectrum: the frame kernels of the tuned half-lengths of each group, plus the dispatcher and the
+    # composed form
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_csd.hip", OBJ / f"dfft_csd_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))
+    # the element-wise kernels those families share: zero-padded rows, truncated rows, the slice reduction
+    out.append((CSRC / "dfft_rows_common.hip", OBJ / "dfft_rows_common.o", []))
     # X stage of the spectral-filter plans: the fused kernels of the fused lengths of each group, plus the dispatcher
     for g in range(NUM_INST_GROUPS + 1):
         out.append((CSRC / "dfft_conv.hip", OBJ / f"dfft_conv_{g}.o", [f"-DDFFT_INST_GROUP={g}"]))

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "dfft_fused_host.h"
 #include "dfft_lconv.h"
 #include "dfft_lxspec.h"
 #include "dfft_osconv.h"
@@ -14,6 +15,7 @@
 #include "dfft_real.h"
 #include "dfft_real_cols.h"
 #include "dfft_real_pair.h"
+#include "dfft_rows_common.h"
 
 using namespace dfft;
 
@@ -680,7 +682,7 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
     // composed route, per chunk of rows of at most max(256 MiB, one row's) bins and padded rows: pad, the real rows of length m as
     // dfft_rfft1d runs them, multiply by H / m, the inverse rows, truncate -- on ONE lease (bins, padded rows, the transforms' own scratch)
     const size_t    rb = (size_t)nh * cs + (size_t)m * rs;
-    const long long nr = std::max(1ll, std::min(rows, (long long)(std::max((size_t)(256ull << 20), rb) / rb)));
+    const long long nr = chunk_units(rb, rows);
     RealRowsPass    Rf, Rb;
     if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
     if (int rc = real_rows_prepare(m, nr, dtype, DFFT_BACKWARD, true, &Rb)) return rc;
@@ -691,11 +693,11 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
     void* inner = bins + data_b;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);
-        if (int rc = lconv_pad((const char*)in + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+        if (int rc = pad_rows((const char*)in + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
         if (int rc = real_rows_run(Rf, pad, bins, k, inner, st)) return rc;
         if (int rc = lconv_mul(bins, hp, m, r0, channels, k, dtype, filter_kind, st)) return rc;
         if (int rc = real_rows_run(Rb, bins, pad, k, inner, st)) return rc;
-        if (int rc = lconv_trunc(pad, (char*)out + (size_t)r0 * n * rs, n, m, k, dtype, st)) return rc;
+        if (int rc = trunc_rows(pad, (char*)out + (size_t)r0 * n * rs, n, m, k, dtype, st)) return rc;
     }
     return DFFT_OK;
 }
@@ -751,7 +753,7 @@ int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, lon
     // length m as dfft_rfft1d runs them, on both fields, and the kernel that adds each channel's rows to out in row order -- on ONE lease
     const bool      autos = x == g;
     const size_t    rb = 2 * (size_t)nh * cs + (size_t)m * rs;
-    const long long nr = std::max(1ll, std::min(rows, (long long)(std::max((size_t)(256ull << 20), rb) / rb)));
+    const long long nr = chunk_units(rb, rows);
     RealRowsPass    Rf;
     if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
     const size_t data_b = ((size_t)nr * rb + 255) / 256 * 256;
@@ -762,10 +764,10 @@ int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, lon
     void* inner = xb + data_b;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);
-        if (int rc = lxspec_pad((const char*)x + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+        if (int rc = pad_rows((const char*)x + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
         if (int rc = real_rows_run(Rf, pad, xb, k, inner, st)) return rc;
         if (!autos) {
-            if (int rc = lxspec_pad((const char*)g + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
+            if (int rc = pad_rows((const char*)g + (size_t)r0 * n * rs, pad, n, m, k, dtype, st)) return rc;
             if (int rc = real_rows_run(Rf, pad, gb, k, inner, st)) return rc;
         }
         if (int rc = lxspec_mac(xb, autos ? xb : gb, out, m, r0, k, channels, dtype, order, st)) return rc;

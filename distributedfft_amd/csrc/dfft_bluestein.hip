@@ -24,9 +24,7 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the multi-pass kernels and the tables).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_bluestein.h"
 #include "dfft_long.h"
 
@@ -200,7 +198,6 @@ DFFT_PLAN_TABLE(DFFT_BS_INST)
 
 namespace {
 
-constexpr size_t kScratchCap = 256ull << 20;
 
 template <class V> __device__ __forceinline__ V cmulb(V a, V b) { return V{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
@@ -235,10 +232,6 @@ __global__ void __launch_bounds__(256) bluestein_finish_kernel(const V* src, V* 
         const V         v = cmulb(src[(b * M + k) * s + c], chirp[k]);
         out[e] = V{v.x * scale, v.y * scale};
     }
-}
-
-unsigned elementwise_grid(long long total) {
-    return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16));
 }
 
 // M-point transforms of data[batch][M][s] on the single-pass kernels (M a tuned length <= 4096), in place
@@ -397,10 +390,7 @@ long long bluestein_padded_length(long long n) {
     return it == v.end() ? 0 : *it;
 }
 
-bool bluestein_fused_env() {
-    const char* e = getenv("DFFT_BLUESTEIN_FUSED");
-    return !(e && *e == '0');
-}
+bool bluestein_fused_env() { return env_switch_on("DFFT_BLUESTEIN_FUSED"); }
 
 int bluestein_tables(long long n, int dtype, int dir, BluesteinTablesPtr* out) {
     int dev = 0;

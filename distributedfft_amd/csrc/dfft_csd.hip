@@ -15,7 +15,7 @@
 // in the working precision -- E accumulators per thread, plus the Nyquist accumulator in the thread of bin 0.  Overlapping frames of a
 // row are consecutive trips of one thread group: a row comes from HBM once and its other m / hop - 1 readings are L2 hits.  After
 // its frames the group stores its M + 1 sums times scale / 4, the imaginary parts of bins 0 and M as exact zeros: straight to `out` for
-// one slice, else to partial[slice][row][.] in the scratch buffer, which rcsd_reduce_kernel sums in slice order.  No atomics: the
+// one slice, else to partial[slice][row][.] in the scratch buffer, which slice_reduce (dfft_rows_common.hip) sums in slice order.  No atomics: the
 // result is the same bits from call to call.  No spectrogram and no framed copy ever exists in memory.
 //
 // Thread groups of one workgroup take consecutive items; all of them run the trip count of the longest slice (the exchanges of a
@@ -30,11 +30,8 @@
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the reduction and the kernels of the composed form).
 #include "dfft_csd.h"
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
-#include "dfft_rconv_impl.h"
-#include "dfft_real.h"
+#include "dfft_fused_host.h"
+#include "dfft_rows_common.h"
 #include "dfft_stft.h"
 
 #include <algorithm>
@@ -63,7 +60,7 @@ struct RcsdFusedLaunch {
     const void* twh;   // e^{-2 pi i k / m}
 };
 
-// (M, dtype) whose instantiations would keep values in scratch memory (tools/rcsd_resources.py, profiles/2026-10-20_rcsd1d/
+// (M, dtype) whose instantiations would keep values in scratch memory (tools/fused_resources.py rcsd, profiles/2026-10-20_rcsd1d/
 // kernel_resources.txt) are not built: they run the composed form.  The kernel reads or holds the window pairs of a thread next to
 // everything rxspec_rows_kernel holds, so the list is longer than rxspec_fused_ok's.
 constexpr bool rcsd_fused_ok(int M, bool f64, bool autos) {
@@ -85,10 +82,11 @@ constexpr bool rcsd_fused_ok(int M, bool f64, bool autos) {
     return true;
 }
 
-// entry point of the tuned half-length M: defined (and explicitly instantiated) in the translation unit of M's group only
-template <bool ON, int M> struct RcsdInst {};
-template <int M> struct RcsdInst<true, M> {
-    static hipError_t run(const RcsdFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<M>: defined in the translation unit of M's group only
+struct RcsdTag {
+    using Launch = RcsdFusedLaunch;
+    static constexpr bool ok(int M, bool f64, bool autos) { return rcsd_fused_ok(M, f64, autos); }
+    template <int M> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -103,7 +101,7 @@ __device__ __forceinline__ void rcsd_load(V (&v)[P::E], const typename real_of<V
     // fp64 with the window read per use: the window comes in behind the frame, four values at a time -- the compiler would otherwise hold
     // the 2 E window values next to the E loaded ones, and the 16-point kernels of 1024 and 2048 points went 28 ... 124 bytes per lane
     // into scratch.  This rests on how the compiler schedules, and the kernels have no registers to spare: after any change of the
-    // toolchain run tools/rcsd_resources.py again (tests/test_rcsd1d_host.py holds the inventory to zero scratch) and route what spills.
+    // toolchain run tools/fused_resources.py rcsd again (tests/test_rcsd1d_host.py holds the inventory to zero scratch) and route what spills.
     constexpr bool STAGED = !WIN_REG && sizeof(V) == 16;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
@@ -129,38 +127,6 @@ __device__ __forceinline__ void rcsd_load(V (&v)[P::E], const typename real_of<V
             if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
         }
     }
-}
-
-// v: the frame's M complex values -> 2 X[k] of the thread's bins k = j + T * (0 ... E-1); returns 2 X[M] in the thread of bin 0.
-// Ends behind a group barrier: every partner is read before the next transform's exchanges reuse the tile.
-template <class V, class P, class RG>
-__device__ __forceinline__ typename real_of<V>::type rcsd_bins(V (&v)[P::E], const typename VecTraits<V>::W* twr, V* lds,
-                                                                const typename VecTraits<V>::W (&wh)[RG::TWH_REG ? P::E : 1],
-                                                                const typename VecTraits<V>::W* __restrict__ twh, int j) {
-    using KG = typename RG::KG;
-    using W = typename VecTraits<V>::W;
-    using RT = typename real_of<V>::type;
-    constexpr int  E = P::E, T = P::T, M = P::N;
-    constexpr bool TWPOW = KG::TWMODE == TW_REG;
-    run_stages<V, P, 0, +1, 1, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, 1, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, 0);
-    group_sync<KG::WAVE_LOCAL>();
-#pragma unroll
-    for (int k = 0; k < E; ++k) lds[lds_index<1, KG::PAD>(j + T * k, 0)] = v[k];
-    group_sync<KG::WAVE_LOCAL>();
-    RT nyq = (RT)0;
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-        const int kk = j + T * k;
-        const V   zm = lds[lds_index<1, KG::PAD>(kk == 0 ? 0 : M - kk, 0)];
-        const W   w = RG::TWH_REG ? wh[RG::TWH_REG ? k : 0] : twh[kk];
-        const V   xe{v[k].x + zm.x, v[k].y - zm.y};  // 2 Xe[k]
-        const V   xo{v[k].y + zm.y, zm.x - v[k].x};  // 2 Xo[k]
-        const V   t = cmul(xo, w);
-        if (kk == 0) nyq = xe.x - xo.x;              // 2 X[M] = 2 (Re Z[0] - Im Z[0])
-        v[k] = V{xe.x + t.x, xe.y + t.y};
-    }
-    group_sync<KG::WAVE_LOCAL>();
-    return nyq;
 }
 
 // AUTO: g is x.  One transform per frame, no copy of the first field's bins and real accumulators only: about a third fewer live
@@ -211,7 +177,7 @@ rcsd_frames_kernel(const typename real_of<V>::type* x, const typename real_of<V>
             const long long base = live ? (long long)row * n + (long long)(f0 + i) * hop : 0ll;  // 64-bit bases
             V               v[E];
             rcsd_load<V, P, VEC, WIN_REG>(v, x + base, live, wn, win, j);
-            const RT xn = rcsd_bins<V, P, RG>(v, twr, lds, wh, twh, j);
+            const RT xn = rrow_bins<V, P, RG>(v, twr, lds, wh, twh, j);
             if constexpr (AUTO) {  // |2 X|^2: the imaginary parts are never formed
 #pragma unroll
                 for (int k = 0; k < E; ++k) acc[k] += v[k].x * v[k].x + v[k].y * v[k].y;
@@ -224,7 +190,7 @@ rcsd_frames_kernel(const typename real_of<V>::type* x, const typename real_of<V>
                 if (cross) {  // always: a branch the compiler cannot see through keeps the second field's loads and transform behind the
                               // first one's (merged, the 16- to 24-point kernels go 120 ... 468 bytes per lane into scratch)
                     rcsd_load<V, P, VEC, WIN_REG>(v, g + base, live, wn, win, j);
-                    gn = rcsd_bins<V, P, RG>(v, twr, lds, wh, twh, j);
+                    gn = rrow_bins<V, P, RG>(v, twr, lds, wh, twh, j);
                 }
 #pragma unroll
                 for (int k = 0; k < E; ++k) {  // conj(X) G
@@ -276,30 +242,15 @@ template <class V, int M> hipError_t rcsd_run_typed(const RcsdFusedLaunch& F, hi
     }
     return hipErrorInvalidValue;  // not built (rcsd_fused_ok): the dispatcher does not come here
 }
-template <int M> hipError_t RcsdInst<true, M>::run(const RcsdFusedLaunch& F, hipStream_t stream) {
+template <int M> hipError_t RcsdTag::run(const RcsdFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return rcsd_run_typed<double2, M>(F, stream);
     if (F.dtype == F32) return rcsd_run_typed<float2, M>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_RCSD_INST(N, GRP, E, ...) template struct RcsdInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_RCSD_INST)
-#undef DFFT_RCSD_INST
+DFFT_FUSED_INSTANTIATE(RcsdTag)
 
-#else  // the dispatcher, the reduction and the kernels of the composed form
+#else  // the dispatcher and the kernels of the composed form
 
-// out[e] = partial[0][e] + partial[1][e] + ... in slice order, e < re = rows * (M + 1)
-template <class V>
-__global__ void __launch_bounds__(256) rcsd_reduce_kernel(const V* __restrict__ partial, V* __restrict__ out, long long re, unsigned slices) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < re; e += (long long)gridDim.x * 256) {
-        V acc = partial[e];
-        for (unsigned s = 1; s < slices; ++s) {
-            const V p = partial[(long long)s * re + e];
-            acc.x += p.x;
-            acc.y += p.y;
-        }
-        out[e] = acc;
-    }
-}
 // item it0 + t = (row, f): row = item / frames, f = item % frames.  Windowed frames: p[t][i] = in[row n + f hop + i] win[i]
 template <class RT>
 __global__ void __launch_bounds__(256) rcsd_gather_kernel(const RT* __restrict__ in, RT* __restrict__ p, const RT* __restrict__ win, long long n, long long m,
@@ -344,42 +295,10 @@ __global__ void __launch_bounds__(256) rcsd_mac_kernel(const V* xb, const V* gb,
 }
 namespace {
 
-constexpr size_t    kRcsdScratchCap = 256ull << 20;
-constexpr long long kRcsdGroupsPerPart = 512;  // resident workgroups of a 256-CU part at two per CU ... (2048 measured: DESIGN 7s)
-constexpr long long kRcsdMaxGroupFactor = 32;  // ... times the thread groups of a workgroup, at most 32: the target item count
-constexpr long long kRcsdMinFrames = 8;        // frames of a slice, at least (a slice costs M + 1 stored and re-read bins)
-
-// the cap on a chunk's scratch: 256 MiB, or DFFT_RCSD_CHUNK_BYTES (read per call; the tests' way to make several chunks of a small problem)
-size_t chunk_cap() {
-    const char* e = getenv("DFFT_RCSD_CHUNK_BYTES");
-    if (e && *e) {
-        const long long v = atoll(e);
-        if (v > 0) return (size_t)v;
-    }
-    return kRcsdScratchCap;
-}
-
-unsigned rcsd_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-// thread groups per workgroup of the fused kernel of half-length M (RconvGeom::G; 1 for an untuned M)
-int groups_per_workgroup(long long M) {
-    switch (M) {
-#define DFFT_RCSD_G(N, GRP, E, ...) \
-    case N: return RconvGeom<double2, PlanFor<N>::type>::G;
-        DFFT_PLAN_TABLE(DFFT_RCSD_G)
-#undef DFFT_RCSD_G
-        default: return 1;
-    }
-}
-bool tuned_half(long long M, int dtype, bool autos) {
-    switch (M) {
-#define DFFT_RCSD_TUNED(N, GRP, E, ...) \
-    case N: return rcsd_fused_ok(N, dtype == F64, autos);
-        DFFT_PLAN_TABLE(DFFT_RCSD_TUNED)
-#undef DFFT_RCSD_TUNED
-        default: return false;
-    }
-}
+// the cut into slices (slice_count; 512 workgroups per part: 2048 measured): the target item count takes at most 32 thread
+// groups of a workgroup, and a slice holds at least 8 frames (it costs M + 1 stored and re-read bins)
+constexpr long long kRcsdMaxGroupFactor = 32;
+constexpr long long kRcsdMinFrames = 8;
 
 bool shape_ok(const RcsdLaunch& L) {
     return (L.dtype == F64 || L.dtype == F32) && L.n >= 1 && L.m >= 2 && L.m <= L.n && L.hop >= 1 && L.rows >= 1 && L.frames >= 1 &&
@@ -387,36 +306,19 @@ bool shape_ok(const RcsdLaunch& L) {
 }
 
 // one item (frame of a row) of the composed form: its m/2 + 1 bins of either field and its m windowed reals (shared by the two fields)
-size_t    item_bytes(long long m, int dtype) { return 2 * (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
-long long chunk_items(long long m, int dtype, long long items) {
-    const size_t ib = item_bytes(m, dtype);
-    return std::max(1ll, std::min(items, (long long)(std::max(chunk_cap(), ib) / ib)));
-}
+size_t item_bytes(long long m, int dtype) { return 2 * (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
+// items of a chunk: what fits 256 MiB, or DFFT_RCSD_CHUNK_BYTES
+long long chunk_items(long long m, int dtype, long long items) { return chunk_units(item_bytes(m, dtype), items, chunk_cap_env("DFFT_RCSD_CHUNK_BYTES")); }
 
 template <class V>
 hipError_t gather_and_transform(const RcsdLaunch& L, const void* field, long long it0, long long ni, void* fr, V* bins, hipStream_t stream) {
     using RT = typename real_of<V>::type;
-    const long long nb = L.m / 2 + 1;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(rcsd_gather_kernel<RT>, dim3(rcsd_grid(ni * L.m)), dim3(256), 0, stream, (const RT*)field, (RT*)fr, (const RT*)L.win, L.n, L.m, L.hop,
-                       L.frames, it0, ni * L.m);
+    hipLaunchKernelGGL(rcsd_gather_kernel<RT>, dim3(elementwise_grid(ni * L.m)), dim3(256), 0, stream, (const RT*)field, (RT*)fr, (const RT*)L.win, L.n, L.m,
+                       L.hop, L.frames, it0, ni * L.m);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = L.dtype;
-    R.n2 = (int)L.m;
-    R.rows = ni;
-    R.rows_per_plane = ni;
-    R.rpitch = L.m;
-    R.rplane = ni * L.m;
-    R.cpitch = nb;
-    R.cplane = ni * nb;
-    R.scale = 1.0;
-    R.dir = +1;
-    R.in = fr;
-    R.out = bins;
-    return launch_real_rows(R, stream);
+    return launch_real_rows(contiguous_real_rows(L.dtype, L.m, ni, +1, 1.0, fr, bins), stream);
 }
 
 // The bins (auto-spectrum: their squared moduli) of the items [it0, it0 + ni) of one field through the one-launch frame kernel of the
@@ -459,7 +361,7 @@ template <class V> int rcsd_chunk(const RcsdLaunch& L, long long it0, long long 
         if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rcsd (gather, R2C rows): ") + hipGetErrorString(e));
     }
     const long long r0 = it0 / L.frames, nr = (it0 + ni - 1) / L.frames - r0 + 1;
-    hipLaunchKernelGGL(rcsd_mac_kernel<V>, dim3(rcsd_grid(nr * nb)), dim3(256), 0, stream, (const V*)xb, (const V*)(autos ? xb : gb), (V*)L.out, nb, L.frames,
+    hipLaunchKernelGGL(rcsd_mac_kernel<V>, dim3(elementwise_grid(nr * nb)), dim3(256), 0, stream, (const V*)xb, (const V*)(autos ? xb : gb), (V*)L.out, nb, L.frames,
                        it0, ni, r0, nr, L.scale, autos ? 1 : 0, power ? 1 : 0);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
@@ -467,10 +369,7 @@ template <class V> int rcsd_chunk(const RcsdLaunch& L, long long it0, long long 
 
 }  // namespace
 
-bool rcsd_fused_env() {
-    const char* e = getenv("DFFT_RCSD_FUSED");
-    return !(e && *e == '0');
-}
+bool rcsd_fused_env() { return env_switch_on("DFFT_RCSD_FUSED"); }
 
 bool rcsd_vec(const void* x, const void* g, long long n, long long hop, int dtype) {
     return n % 2 == 0 && hop % 2 == 0 && (uintptr_t)x % elem_bytes(dtype) == 0 && (uintptr_t)g % elem_bytes(dtype) == 0;
@@ -478,13 +377,12 @@ bool rcsd_vec(const void* x, const void* g, long long n, long long hop, int dtyp
 
 bool rcsd_fused(long long m, int dtype, bool autos) {
     if ((dtype != F64 && dtype != F32) || m < 4 || m % 2 || !real_length_supported(m)) return false;
-    return tuned_half(m / 2, dtype, autos);
+    return tuned_built<RcsdTag>(m / 2, dtype == F64, autos);
 }
 
 long long rcsd_slices(long long m, long long rows, long long frames, int dtype) {
     if (m < 2 || !real_length_supported(m) || rows < 1 || frames < 1 || (dtype != F64 && dtype != F32) || !rcsd_items_ok(rows, frames)) return 0;
-    const long long target = kRcsdGroupsPerPart * std::min<long long>(groups_per_workgroup(m / 2), kRcsdMaxGroupFactor);
-    return std::max(1ll, std::min(target / rows, frames / kRcsdMinFrames));
+    return slice_count(groups_per_workgroup(m / 2), kRcsdMaxGroupFactor, rows, frames, kRcsdMinFrames);
 }
 
 size_t rcsd_scratch_bytes(const RcsdLaunch& L, bool fused_on) {
@@ -522,34 +420,16 @@ int rcsd(const RcsdLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes
         F.win = L.win;
         if (int rc = get_twiddles((int)(L.m / 2), L.dtype, &F.tw)) return rc;
         if (int rc = get_twiddles((int)L.m, L.dtype, &F.twh)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.m / 2) {
-#define DFFT_RCSD_CASE(N, GRP, E, ...) \
-    case N: e = RcsdInst<true, N>::run(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_RCSD_CASE)
-#undef DFFT_RCSD_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<RcsdTag>(L.m / 2, F, stream);
         if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rcsd (fused): ") + hipGetErrorString(e));
-        if (slices > 1) {
-            const long long re = L.rows * nb;
-            if (L.dtype == F64)
-                hipLaunchKernelGGL(rcsd_reduce_kernel<double2>, dim3(rcsd_grid(re)), dim3(256), 0, stream, (const double2*)scratch, (double2*)L.out, re,
-                                   (unsigned)slices);
-            else
-                hipLaunchKernelGGL(rcsd_reduce_kernel<float2>, dim3(rcsd_grid(re)), dim3(256), 0, stream, (const float2*)scratch, (float2*)L.out, re,
-                                   (unsigned)slices);
-            DFFT_HIP_TRY(hipGetLastError());
-        }
-        return DFFT_OK;
+        return slices > 1 ? slice_reduce(scratch, L.out, L.rows * nb, slices, L.dtype, stream) : DFFT_OK;
     }
     // chunks of consecutive (row, frame) items whose windowed frames and bins fit the scratch buffer: the frames of a row are added in
     // ascending order whatever the cut
     const size_t    ib = item_bytes(L.m, L.dtype);
     const long long items = L.rows * L.frames;
-    long long       ni = chunk_items(L.m, L.dtype, items);
-    if (scratch_bytes / ib < (size_t)ni) ni = (long long)(scratch_bytes / ib);
-    if (!scratch || ni < 1) return fail(DFFT_EINVAL, "rcsd: scratch buffer too small");
+    long long       ni = fit_chunk_to_lease("rcsd", chunk_items(L.m, L.dtype, items), ib, scratch, scratch_bytes);
+    if (ni < 1) return DFFT_EINVAL;
     // Where the STFT's one-launch frame kernel is built for (m/2, dtype) it forms the chunk's bins straight from the rows; the chunks
     // are then whole rows, or -- a row with more frames than a chunk holds -- runs of frames of one row.  No windowed frames are kept
     // then (and the auto-spectrum keeps squared moduli, not bins), so the same lease holds more items.

@@ -51,10 +51,8 @@ int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStre
 // or complex type of F64; 4 or 8 of F32)
 int lconv_filter(const void* h, void* hp, long long m, long long channels, int esize, hipStream_t stream);
 
-// The kernels of the composed route around the real transforms of length m (dfft_batch.cpp runs those): rows [nr][n] -> padded rows
-// [nr][m]; bins [nr][m/2 + 1] *= H / m with H read from hp (rows row0 ... of the call); padded rows -> rows [nr][n].
-int lconv_pad(const void* in, void* pad, long long n, long long m, long long nr, int dtype, hipStream_t stream);
+// The multiply of the composed route between the real transforms of length m (dfft_batch.cpp runs those, and pad_rows / trunc_rows of
+// dfft_rows_common.h around them): bins [nr][m/2 + 1] *= H / m with H read from hp (rows row0 ... of the call).
 int lconv_mul(void* bins, const void* hp, long long m, long long row0, long long channels, long long nr, int dtype, int filter_kind, hipStream_t stream);
-int lconv_trunc(const void* pad, void* out, long long n, long long m, long long nr, int dtype, hipStream_t stream);
 
 }  // namespace dfft

@@ -23,11 +23,8 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the kernels of the factor lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the tables, the filter permutation and the kernels of the composed route).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_lconv.h"
-#include "dfft_rconv_impl.h"
 
 #include <algorithm>
 #include <atomic>
@@ -67,7 +64,7 @@ struct LconvPass {
     const void* colt;  // e^{-2 pi i k2 / (2 N2)}, k2 < N2
 };
 
-// (N, dtype) whose instantiations would keep values in scratch memory (tools/lconv_resources.py, profiles/2026-10-20_rconv1d_long/
+// (N, dtype) whose instantiations would keep values in scratch memory (tools/fused_resources.py lconv, profiles/2026-10-20_rconv1d_long/
 // kernel_resources.txt) are not built: a split with such a factor runs the composed route.  All kernels of an (N, dtype) go together.
 constexpr bool lconv_fused_ok(int N, bool f64) {
     (void)N;
@@ -75,10 +72,11 @@ constexpr bool lconv_fused_ok(int N, bool f64) {
     return true;
 }
 
-// entry point of the factor length N: defined (and explicitly instantiated) in the translation unit of N's group only
-template <bool ON, int N> struct LconvInst {};
-template <int N> struct LconvInst<true, N> {
-    static hipError_t run(const LconvPass& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<N>, one pass of the factor length N: defined in the translation unit of N's group only
+struct LconvTag {
+    using Launch = LconvPass;
+    static constexpr bool ok(int N, bool f64) { return lconv_factor(N) && lconv_fused_ok(N, f64); }
+    template <int N> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -368,16 +366,14 @@ template <class V, int N> hipError_t lconv_run_typed(const LconvPass& F, hipStre
     }
     return hipErrorInvalidValue;  // not built (lconv_factor, lconv_fused_ok): the dispatcher does not come here
 }
-template <int N> hipError_t LconvInst<true, N>::run(const LconvPass& F, hipStream_t stream) {
+template <int N> hipError_t LconvTag::run(const LconvPass& F, hipStream_t stream) {
     if (F.dtype == F64) return lconv_run_typed<double2, N>(F, stream);
     if (F.dtype == F32) return lconv_run_typed<float2, N>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_LCONV_INST(N, GRP, E, ...) template struct LconvInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_LCONV_INST)
-#undef DFFT_LCONV_INST
+DFFT_FUSED_INSTANTIATE(LconvTag)
 
-#else  // the dispatcher, the tables, the filter permutation and the kernels of the composed route
+#else  // the dispatcher, the tables, the filter permutation and the multiply kernel of the composed route
 
 // hp[c][k1 N2 + k2] = h[c][k1 + N1 k2], hp[c][M] = h[c][M]
 template <class T>
@@ -387,22 +383,6 @@ __global__ void __launch_bounds__(256) lconv_filter_kernel(const T* __restrict__
         const long long c = e / nb, i = e - c * nb;
         const long long k1 = i / N2, k2 = i - k1 * N2;
         hp[e] = h[c * nb + (i == nb - 1 ? i : k1 + N1 * k2)];
-    }
-}
-// padded rows: p[r][i] = x[r][i] (i < n), 0 (n <= i < m)
-template <class RT>
-__global__ void __launch_bounds__(256) lconv_pad_kernel(const RT* __restrict__ in, RT* __restrict__ p, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / m, i = e - r * m;
-        p[e] = i < n ? in[r * n + i] : (RT)0;
-    }
-}
-// y[r][i] = p[r][i], i < n.  `out` may be the buffer the chunk was padded from: p is the scratch.
-template <class RT>
-__global__ void __launch_bounds__(256) lconv_trunc_kernel(const RT* __restrict__ p, RT* __restrict__ out, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / n, i = e - r * n;
-        out[e] = p[r * m + i];
     }
 }
 // bins[r][k] *= H[(row0 + r) % channels][k] / m, k <= M, with H[k] at hp[(k % N1) N2 + k / N1] (k < M), hp[M]
@@ -424,10 +404,6 @@ __global__ void __launch_bounds__(256) lconv_mul_kernel(V* __restrict__ bins, co
 
 namespace {
 
-constexpr size_t kLconvScratchCap = 256ull << 20;
-
-unsigned lconv_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
 // every accepted m in ascending order: twice the products of two factor lengths, 8192 < m <= 2^23
 const std::vector<long long>& accepted_lengths() {
     static const std::vector<long long> v = [] {
@@ -442,26 +418,6 @@ const std::vector<long long>& accepted_lengths() {
         return out;
     }();
     return v;
-}
-
-bool factor_fused(int N, int dtype) {
-    switch (N) {
-#define DFFT_LCONV_TUNED(N, GRP, E, ...) \
-    case N: return lconv_factor(N) && lconv_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_LCONV_TUNED)
-#undef DFFT_LCONV_TUNED
-        default: return false;
-    }
-}
-
-hipError_t run_pass(int N, const LconvPass& F, hipStream_t stream) {
-    switch (N) {
-#define DFFT_LCONV_CASE(N, GRP, E, ...) \
-    case N: return LconvInst<true, N>::run(F, stream);
-        DFFT_PLAN_TABLE(DFFT_LCONV_CASE)
-#undef DFFT_LCONV_CASE
-        default: return hipErrorInvalidValue;
-    }
 }
 
 // the tables of one (device, m, dtype): built once, kept for the life of the process (about 100 KiB)
@@ -539,21 +495,15 @@ long long lconv_length(long long at_least) {
     return it == v.end() ? 0 : *it;
 }
 
-bool lconv_fused_env() {
-    const char* e = getenv("DFFT_RCONV_LONG_FUSED");
-    return !(e && *e == '0');
-}
+bool lconv_fused_env() { return env_switch_on("DFFT_RCONV_LONG_FUSED"); }
 
 bool lconv_fused(long long m, int dtype) {
     int n1 = 0, n2 = 0;
     if ((dtype != F64 && dtype != F32) || !lconv_split(m, &n1, &n2)) return false;
-    return factor_fused(n1, dtype) && factor_fused(n2, dtype);
+    return tuned_built<LconvTag>(n1, dtype == F64) && tuned_built<LconvTag>(n2, dtype == F64);
 }
 
-long long lconv_chunk_rows(long long m, int dtype, long long rows) {
-    const size_t rb = (size_t)(m / 2) * elem_bytes(dtype);
-    return std::max(1ll, std::min(rows, (long long)(std::max(kLconvScratchCap, rb) / rb)));
-}
+long long lconv_chunk_rows(long long m, int dtype, long long rows) { return chunk_units((size_t)(m / 2) * elem_bytes(dtype), rows); }
 size_t lconv_scratch_bytes(long long m, int dtype, long long rows) {
     if (rows < 1 || !lconv_split(m, nullptr, nullptr)) return 0;
     return (size_t)lconv_chunk_rows(m, dtype, rows) * (size_t)(m / 2) * elem_bytes(dtype);
@@ -568,9 +518,8 @@ int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStre
     const long long rows = L.batch * L.channels;
     if (rows >= (1ll << 31)) return fail(DFFT_EINVAL, "lconv: 2^31 or more rows");
     const size_t rb = (size_t)(L.m / 2) * elem_bytes(L.dtype), rs = elem_bytes(L.dtype) / 2;
-    long long    nr = lconv_chunk_rows(L.m, L.dtype, rows);
-    if (scratch_bytes / rb < (size_t)nr) nr = (long long)(scratch_bytes / rb);
-    if (!scratch || nr < 1) return fail(DFFT_EINVAL, "lconv: scratch buffer too small");
+    const long long nr = fit_chunk_to_lease("lconv", lconv_chunk_rows(L.m, L.dtype, rows), rb, scratch, scratch_bytes);
+    if (nr < 1) return DFFT_EINVAL;
     LconvTables T;
     if (int rc = lconv_tables(L.m, n1, n2, L.dtype, &T)) return rc;
     LconvPass F;
@@ -601,7 +550,7 @@ int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStre
         for (int pass = 0; pass < 3; ++pass) {
             F.pass = pass;
             F.tw = pass == LCONV_PASS_MID ? tw2 : tw1;
-            const hipError_t e = run_pass(pass == LCONV_PASS_MID ? n2 : n1, F, stream);
+            const hipError_t e = run_tuned<LconvTag>(pass == LCONV_PASS_MID ? n2 : n1, F, stream);
             if (e != hipSuccess) return fail(DFFT_EHIP, std::string(names[pass]) + hipGetErrorString(e));
         }
     }
@@ -613,26 +562,10 @@ int lconv_filter(const void* h, void* hp, long long m, long long channels, int e
     if (!h || !hp || channels < 1 || !lconv_split(m, &n1, &n2)) return fail(DFFT_EINVAL, "lconv_filter: bad arguments");
     const long long total = channels * (m / 2 + 1);
     (void)hipGetLastError();
-    if (esize == 16) hipLaunchKernelGGL(lconv_filter_kernel<double2>, dim3(lconv_grid(total)), dim3(256), 0, stream, (const double2*)h, (double2*)hp, n1, n2, total);
-    else if (esize == 8) hipLaunchKernelGGL(lconv_filter_kernel<double>, dim3(lconv_grid(total)), dim3(256), 0, stream, (const double*)h, (double*)hp, n1, n2, total);
-    else if (esize == 4) hipLaunchKernelGGL(lconv_filter_kernel<float>, dim3(lconv_grid(total)), dim3(256), 0, stream, (const float*)h, (float*)hp, n1, n2, total);
+    if (esize == 16) hipLaunchKernelGGL(lconv_filter_kernel<double2>, dim3(elementwise_grid(total)), dim3(256), 0, stream, (const double2*)h, (double2*)hp, n1, n2, total);
+    else if (esize == 8) hipLaunchKernelGGL(lconv_filter_kernel<double>, dim3(elementwise_grid(total)), dim3(256), 0, stream, (const double*)h, (double*)hp, n1, n2, total);
+    else if (esize == 4) hipLaunchKernelGGL(lconv_filter_kernel<float>, dim3(elementwise_grid(total)), dim3(256), 0, stream, (const float*)h, (float*)hp, n1, n2, total);
     else return fail(DFFT_EINVAL, "lconv_filter: bad element size");
-    DFFT_HIP_TRY(hipGetLastError());
-    return DFFT_OK;
-}
-
-int lconv_pad(const void* in, void* pad, long long n, long long m, long long nr, int dtype, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (dtype == F64) hipLaunchKernelGGL(lconv_pad_kernel<double>, dim3(lconv_grid(nr * m)), dim3(256), 0, stream, (const double*)in, (double*)pad, n, m, nr * m);
-    else hipLaunchKernelGGL(lconv_pad_kernel<float>, dim3(lconv_grid(nr * m)), dim3(256), 0, stream, (const float*)in, (float*)pad, n, m, nr * m);
-    DFFT_HIP_TRY(hipGetLastError());
-    return DFFT_OK;
-}
-
-int lconv_trunc(const void* pad, void* out, long long n, long long m, long long nr, int dtype, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (dtype == F64) hipLaunchKernelGGL(lconv_trunc_kernel<double>, dim3(lconv_grid(nr * n)), dim3(256), 0, stream, (const double*)pad, (double*)out, n, m, nr * n);
-    else hipLaunchKernelGGL(lconv_trunc_kernel<float>, dim3(lconv_grid(nr * n)), dim3(256), 0, stream, (const float*)pad, (float*)out, n, m, nr * n);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
 }
@@ -641,7 +574,7 @@ int lconv_mul(void* bins, const void* hp, long long m, long long row0, long long
     int n1 = 0, n2 = 0;
     if (!lconv_split(m, &n1, &n2)) return fail(DFFT_EINVAL, "lconv_mul: bad arguments");
     const long long total = nr * (m / 2 + 1);
-    const dim3      grid(lconv_grid(total));
+    const dim3      grid(elementwise_grid(total));
     const double    sc = 1.0 / (double)m;
     (void)hipGetLastError();
     if (dtype == F64 && filter_kind == RCONV_FILTER_REAL)

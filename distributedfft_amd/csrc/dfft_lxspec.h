@@ -21,8 +21,7 @@ struct LxspecLaunch {
     void*       out;
 };
 
-// Fixed constants of the cuts (never the device): see lxspec_chunk_rows, lxspec_slices
-constexpr size_t    kLxspecScratchCap = 256ull << 20;
+// Fixed constants of the cuts (never the device): see lxspec_slices (lxspec_chunk_rows: kScratchCap of dfft_fused_host.h)
 constexpr long long kLxspecTargetItems = 2048;  // (slice, channel, row pair) items worth cutting the batch for
 constexpr long long kLxspecMinSteps = 8;        // rows of a channel in a slice, at least
 
@@ -45,10 +44,9 @@ size_t lxspec_scratch_bytes(long long m, int dtype, long long channels, long lon
 // Sums rows of a slice in order, slices in order, chunks in order: no atomics.  Enqueues on `stream` only.
 int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
-// The kernels of the composed route around the real transforms of length m (dfft_batch.cpp runs those): rows [nr][n] -> padded rows
-// [nr][m]; out[c][.] (+)= the sum over the chunk's rows of channel c, in row order, of conj(xb) gb (row r of the chunk is row row0 + r of
+// The accumulation of the composed route behind the real transforms of length m (dfft_batch.cpp runs those, behind pad_rows of
+// dfft_rows_common.h): out[c][.] (+)= the sum over the chunk's rows of channel c, in row order, of conj(xb) gb (row r of the chunk is row row0 + r of
 // the call; row0 == 0 starts the sum; gb == xb: the auto-spectrum), bins [nr][m/2 + 1] in natural order, out in `order`.
-int lxspec_pad(const void* in, void* pad, long long n, long long m, long long nr, int dtype, hipStream_t stream);
 int lxspec_mac(const void* xb, const void* gb, void* out, long long m, long long row0, long long nr, long long channels, int dtype, int order,
                hipStream_t stream);
 

@@ -26,12 +26,9 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the kernels of the factor lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the tables, the reduction and the kernels of the composed route).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
+#include "dfft_fused_host.h"
 #include "dfft_lconv.h"
 #include "dfft_lxspec.h"
-#include "dfft_plans.h"
-#include "dfft_rconv_impl.h"
 
 #include <algorithm>
 #include <atomic>
@@ -73,21 +70,23 @@ struct LxspecPass {
     const void* colt;  // e^{-2 pi i k2 / (2 N2)}, k2 < N2
 };
 
-// (N2, dtype) whose accumulating Mid kernel would keep values in scratch memory (tools/lxspec_resources.py, profiles/2026-10-20_rxspec1d_long/
+// (N2, dtype) whose accumulating Mid kernel would keep values in scratch memory (tools/fused_resources.py lxspec, profiles/2026-10-20_rxspec1d_long/
 // kernel_resources.txt) are not built: a split with such a longer factor runs the composed route.  Pass A of every factor length is built.
 constexpr bool lxspec_fused_ok(int N, bool f64) {
-#ifdef DFFT_LXSPEC_BUILD_ALL  // tools/lxspec_resources.py --all: every Mid kernel, to find the ones that spill
+#ifdef DFFT_LXSPEC_BUILD_ALL  // tools/fused_resources.py lxspec --build-all: every Mid kernel, to find the ones that spill
     return N > 0 || f64;
 #endif
-    // 24 and 20 points per thread in fp64, three live arrays: 208, 108, 164 and 288 bytes per lane (tools/lxspec_resources.py --all)
+    // 24 and 20 points per thread in fp64, three live arrays: 208, 108, 164 and 288 bytes per lane (tools/fused_resources.py lxspec --build-all)
     if (f64 && (N == 384 || N == 640 || N == 1280 || N == 1536)) return false;
     return true;
 }
 
-// entry point of the factor length N: defined (and explicitly instantiated) in the translation unit of N's group only
-template <bool ON, int N> struct LxspecInst {};
-template <int N> struct LxspecInst<true, N> {
-    static hipError_t run(const LxspecPass& F, hipStream_t stream);
+// the family (dfft_fused_host.h); ok: the Mid kernel of N2 = N is built; run<N>, one pass of the factor length N: defined in the
+// translation unit of N's group only
+struct LxspecTag {
+    using Launch = LxspecPass;
+    static constexpr bool ok(int N, bool f64) { return lconv_factor(N) && N > 64 && lxspec_fused_ok(N, f64); }
+    template <int N> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -349,14 +348,12 @@ template <class V, int N> hipError_t lxspec_run_typed(const LxspecPass& F, hipSt
     }
     return hipErrorInvalidValue;  // not built (lconv_factor, lxspec_fused_ok): the dispatcher does not come here
 }
-template <int N> hipError_t LxspecInst<true, N>::run(const LxspecPass& F, hipStream_t stream) {
+template <int N> hipError_t LxspecTag::run(const LxspecPass& F, hipStream_t stream) {
     if (F.dtype == F64) return lxspec_run_typed<double2, N>(F, stream);
     if (F.dtype == F32) return lxspec_run_typed<float2, N>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_LXSPEC_INST(N, GRP, E, ...) template struct LxspecInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_LXSPEC_INST)
-#undef DFFT_LXSPEC_INST
+DFFT_FUSED_INSTANTIATE(LxspecTag)
 
 #else  // the dispatcher, the tables, the reduction and the kernels of the composed route
 
@@ -388,14 +385,6 @@ __global__ void __launch_bounds__(256) lxspec_reduce_kernel(const V* __restrict_
         }
     }
 }
-// padded rows: p[r][i] = x[r][i] (i < n), 0 (n <= i < m)
-template <class RT>
-__global__ void __launch_bounds__(256) lxspec_pad_kernel(const RT* __restrict__ in, RT* __restrict__ p, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / m, i = e - r * m;
-        p[e] = i < n ? in[r * n + i] : (RT)0;
-    }
-}
 // rxspec_mac_kernel of dfft_xspec.hip with the store order: out[c][i] (+)= sum over the chunk's rows r of channel c, in row order, of
 // conj(xb[r][k]) gb[r][k], k the natural bin of position i.  `first`: the chunk starts the sum.  autos: gb is xb, the sum is of |xb|^2.
 template <class V>
@@ -423,28 +412,6 @@ __global__ void __launch_bounds__(256) lxspec_mac_kernel(const V* xb, const V* g
 }
 
 namespace {
-
-unsigned lxspec_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-bool mid_fused(int N, int dtype) {
-    switch (N) {
-#define DFFT_LXSPEC_TUNED(N, GRP, E, ...) \
-    case N: return lconv_factor(N) && N > 64 && lxspec_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_LXSPEC_TUNED)
-#undef DFFT_LXSPEC_TUNED
-        default: return false;
-    }
-}
-
-hipError_t run_pass(int N, const LxspecPass& F, hipStream_t stream) {
-    switch (N) {
-#define DFFT_LXSPEC_CASE(N, GRP, E, ...) \
-    case N: return LxspecInst<true, N>::run(F, stream);
-        DFFT_PLAN_TABLE(DFFT_LXSPEC_CASE)
-#undef DFFT_LXSPEC_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
 
 // the tables of one (device, m, dtype): built once, kept for the life of the process (about 100 KiB)
 struct LxspecTables {
@@ -502,21 +469,15 @@ bool rows_ok(long long channels, long long rows) { return channels >= 1 && rows 
 
 }  // namespace
 
-bool lxspec_fused_env() {
-    const char* e = getenv("DFFT_RXSPEC_LONG_FUSED");
-    return !(e && *e == '0');
-}
+bool lxspec_fused_env() { return env_switch_on("DFFT_RXSPEC_LONG_FUSED"); }
 
 bool lxspec_fused(long long m, int dtype) {
     int n1 = 0, n2 = 0;
     if ((dtype != F64 && dtype != F32) || !lconv_split(m, &n1, &n2)) return false;
-    return mid_fused(n2, dtype);
+    return tuned_built<LxspecTag>(n2, dtype == F64);
 }
 
-long long lxspec_chunk_rows(long long m, int dtype, long long rows) {
-    const size_t rb = 2 * (size_t)(m / 2) * elem_bytes(dtype);
-    return std::max(1ll, std::min(rows, (long long)(std::max(kLxspecScratchCap, rb) / rb)));
-}
+long long lxspec_chunk_rows(long long m, int dtype, long long rows) { return chunk_units(2 * (size_t)(m / 2) * elem_bytes(dtype), rows); }
 
 long long lxspec_slices(long long m, long long channels, long long rows) {
     int n1 = 0, n2 = 0;
@@ -580,15 +541,15 @@ int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipSt
         for (int field = 0; field < (autos ? 1 : 2); ++field) {
             F.in = (const char*)(field ? L.g : L.x) + (size_t)r0 * L.n * rs;
             F.scr = field ? sg : sx;
-            const hipError_t e = run_pass(n1, F, stream);
+            const hipError_t e = run_tuned<LxspecTag>(n1, F, stream);
             if (e != hipSuccess) return fail(DFFT_EHIP, std::string("lxspec (pass A): ") + hipGetErrorString(e));
         }
         F.pass = LXSPEC_PASS_MID;
         F.tw = tw2;
-        const hipError_t e = run_pass(n2, F, stream);
+        const hipError_t e = run_tuned<LxspecTag>(n2, F, stream);
         if (e != hipSuccess) return fail(DFFT_EHIP, std::string("lxspec (mid): ") + hipGetErrorString(e));
         if (!direct) {
-            const dim3 grid(lxspec_grid(L.channels * (M + 1)));
+            const dim3 grid(elementwise_grid(L.channels * (M + 1)));
             (void)hipGetLastError();
             if (L.dtype == F64)
                 hipLaunchKernelGGL(lxspec_reduce_kernel<double2>, grid, dim3(256), 0, stream, (const double2*)partial, (double2*)L.out, L.channels, n1, n2,
@@ -602,19 +563,11 @@ int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipSt
     return DFFT_OK;
 }
 
-int lxspec_pad(const void* in, void* pad, long long n, long long m, long long nr, int dtype, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (dtype == F64) hipLaunchKernelGGL(lxspec_pad_kernel<double>, dim3(lxspec_grid(nr * m)), dim3(256), 0, stream, (const double*)in, (double*)pad, n, m, nr * m);
-    else hipLaunchKernelGGL(lxspec_pad_kernel<float>, dim3(lxspec_grid(nr * m)), dim3(256), 0, stream, (const float*)in, (float*)pad, n, m, nr * m);
-    DFFT_HIP_TRY(hipGetLastError());
-    return DFFT_OK;
-}
-
 int lxspec_mac(const void* xb, const void* gb, void* out, long long m, long long row0, long long nr, long long channels, int dtype, int order,
                hipStream_t stream) {
     int n1 = 0, n2 = 0;
     if (!lconv_split(m, &n1, &n2)) return fail(DFFT_EINVAL, "lxspec_mac: bad arguments");
-    const dim3 grid(lxspec_grid(channels * (m / 2 + 1)));
+    const dim3 grid(elementwise_grid(channels * (m / 2 + 1)));
     const int  autos = xb == gb ? 1 : 0, first = row0 == 0 ? 1 : 0;
     (void)hipGetLastError();
     if (dtype == F64)

@@ -27,13 +27,9 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the block chooser and the kernels of the composed form).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
+#include "dfft_fused_host.h"
 #include "dfft_osconv.h"
-#include "dfft_plans.h"
 #include "dfft_rconv.h"
-#include "dfft_rconv_impl.h"
-#include "dfft_real.h"
 
 #include <algorithm>
 #include <atomic>
@@ -58,7 +54,7 @@ struct OsconvFusedLaunch {
     const void* twh;  // e^{-2 pi i k / m}
 };
 
-// (M, dtype) whose block kernels would keep values in scratch memory (tools/osconv_resources.py, profiles/2026-10-20_rconv1d_os/
+// (M, dtype) whose block kernels would keep values in scratch memory (tools/fused_resources.py osconv, profiles/2026-10-20_rconv1d_os/
 // kernel_resources.txt) are not built: they run the composed form.  The first two lines are rconv_fused_ok's (dfft_rconv.hip), whose
 // rule the dispatcher applies through rconv_fused as well.
 constexpr bool osconv_fused_ok(int M, bool f64) {
@@ -68,10 +64,11 @@ constexpr bool osconv_fused_ok(int M, bool f64) {
     return true;
 }
 
-// entry point of the tuned half-length M: defined (and explicitly instantiated) in the translation unit of M's group only
-template <bool ON, int M> struct OsconvInst {};
-template <int M> struct OsconvInst<true, M> {
-    static hipError_t run(const OsconvFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<M>: defined in the translation unit of M's group only
+struct OsconvTag {
+    using Launch = OsconvFusedLaunch;
+    static constexpr bool ok(int M, bool f64) { return osconv_fused_ok(M, f64); }
+    template <int M> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -209,14 +206,12 @@ template <class V, int M> hipError_t osconv_run_typed(const OsconvFusedLaunch& F
     }
     return hipErrorInvalidValue;  // not built (osconv_fused_ok): the dispatcher does not come here
 }
-template <int M> hipError_t OsconvInst<true, M>::run(const OsconvFusedLaunch& F, hipStream_t stream) {
+template <int M> hipError_t OsconvTag::run(const OsconvFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return osconv_run_typed<double2, M>(F, stream);
     if (F.dtype == F32) return osconv_run_typed<float2, M>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_OSCONV_INST(N, GRP, E, ...) template struct OsconvInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_OSCONV_INST)
-#undef DFFT_OSCONV_INST
+DFFT_FUSED_INSTANTIATE(OsconvTag)
 
 #else  // the dispatcher, the block chooser and the kernels of the composed form
 
@@ -260,16 +255,8 @@ __global__ void __launch_bounds__(256) osconv_mul_kernel(V* __restrict__ bins, c
 
 namespace {
 
-constexpr size_t kOsconvScratchCap = 256ull << 20;
-
-unsigned osconv_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
 // one item of the composed form: its m/2 + 1 bins and its m gathered reals
 size_t item_bytes(long long m, int dtype) { return (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
-long long chunk_items(long long m, int dtype, long long items) {
-    const size_t ib = item_bytes(m, dtype);
-    return std::max(1ll, std::min(items, (long long)(std::max(kOsconvScratchCap, ib) / ib)));
-}
 
 bool sizes_ok(const OsconvLaunch& L) {
     if (L.n < 1 || L.n_out < 1 || L.discard < 0 || L.m <= L.discard || L.n_out - L.discard > L.n || !real_length_supported(L.m) || L.channels < 1 ||
@@ -284,37 +271,21 @@ template <class V> int osconv_chunk(const OsconvLaunch& L, long long nb, long lo
     V*              bins = (V*)scratch;              // [ni][nbins]; a multiple of sizeof(V) bytes, so the blocks behind it stay aligned to V
     RT*             pad = (RT*)(bins + ni * nbins);  // [ni][m]
     (void)hipGetLastError();
-    hipLaunchKernelGGL(osconv_gather_kernel<RT>, dim3(osconv_grid(ni * m)), dim3(256), 0, stream, (const RT*)L.in, pad, L.n, m, S, d, nb, it0, ni * m);
+    hipLaunchKernelGGL(osconv_gather_kernel<RT>, dim3(elementwise_grid(ni * m)), dim3(256), 0, stream, (const RT*)L.in, pad, L.n, m, S, d, nb, it0, ni * m);
     DFFT_HIP_TRY(hipGetLastError());
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = L.dtype;
-    R.n2 = (int)m;
-    R.rows = ni;
-    R.rows_per_plane = ni;
-    R.rpitch = m;
-    R.rplane = ni * m;
-    R.cpitch = nbins;
-    R.cplane = ni * nbins;
-    R.scale = 1.0;
-    R.dir = +1;
-    R.in = pad;
-    R.out = bins;
-    hipError_t e = launch_real_rows(R, stream);
+    hipError_t e = launch_real_rows(contiguous_real_rows(L.dtype, m, ni, +1, 1.0, pad, bins), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rconv_os (R2C rows): ") + hipGetErrorString(e));
     if (L.filter_kind == RCONV_FILTER_REAL)
-        hipLaunchKernelGGL((osconv_mul_kernel<V, RT>), dim3(osconv_grid(ni * nbins)), dim3(256), 0, stream, bins, (const RT*)L.h, nbins, nb, it0, L.channels,
+        hipLaunchKernelGGL((osconv_mul_kernel<V, RT>), dim3(elementwise_grid(ni * nbins)), dim3(256), 0, stream, bins, (const RT*)L.h, nbins, nb, it0, L.channels,
                            ni * nbins, 1.0 / (double)m);
     else
-        hipLaunchKernelGGL((osconv_mul_kernel<V, V>), dim3(osconv_grid(ni * nbins)), dim3(256), 0, stream, bins, (const V*)L.h, nbins, nb, it0, L.channels,
+        hipLaunchKernelGGL((osconv_mul_kernel<V, V>), dim3(elementwise_grid(ni * nbins)), dim3(256), 0, stream, bins, (const V*)L.h, nbins, nb, it0, L.channels,
                            ni * nbins, 1.0 / (double)m);
     DFFT_HIP_TRY(hipGetLastError());
-    R.dir = -1;  // (the two-launch form of an untuned m/2 merges in place on its input: the bins are scratch)
-    R.in = bins;
-    R.out = pad;
-    e = launch_real_rows(R, stream);
+    // (the two-launch form of an untuned m/2 merges in place on its input: the bins are scratch)
+    e = launch_real_rows(contiguous_real_rows(L.dtype, m, ni, -1, 1.0, bins, pad), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rconv_os (C2R rows): ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(osconv_scatter_kernel<RT>, dim3(osconv_grid(ni * S)), dim3(256), 0, stream, (const RT*)pad, (RT*)L.out, L.n_out, m, S, d, nb, it0,
+    hipLaunchKernelGGL(osconv_scatter_kernel<RT>, dim3(elementwise_grid(ni * S)), dim3(256), 0, stream, (const RT*)pad, (RT*)L.out, L.n_out, m, S, d, nb, it0,
                        ni * S);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
@@ -365,19 +336,13 @@ bool osconv_vec(const void* in, const void* out, long long n, long long n_out, l
 
 bool osconv_fused(long long m, int dtype) {
     if ((dtype != F64 && dtype != F32) || !rconv_fused(1, m, dtype, RCONV_FILTER_COMPLEX, false)) return false;
-    switch (m / 2) {
-#define DFFT_OSCONV_TUNED(N, GRP, E, ...) \
-    case N: return osconv_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_OSCONV_TUNED)
-#undef DFFT_OSCONV_TUNED
-        default: return false;
-    }
+    return tuned_built<OsconvTag>(m / 2, dtype == F64);
 }
 
 size_t osconv_scratch_bytes(const OsconvLaunch& L, bool fused_on) {
     if ((L.dtype != F64 && L.dtype != F32) || !sizes_ok(L)) return 0;
     if (fused_on && osconv_fused(L.m, L.dtype)) return 0;
-    return (size_t)chunk_items(L.m, L.dtype, L.batch * L.channels * osconv_blocks(L.n_out, L.m, L.discard)) * item_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(item_bytes(L.m, L.dtype), L.batch * L.channels * osconv_blocks(L.n_out, L.m, L.discard)) * item_bytes(L.m, L.dtype);
 }
 
 int osconv(const OsconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
@@ -403,22 +368,14 @@ int osconv(const OsconvLaunch& L, bool fused_on, void* scratch, size_t scratch_b
         F.h = L.h;
         if (int rc = get_twiddles((int)(L.m / 2), L.dtype, &F.tw)) return rc;
         if (int rc = get_twiddles((int)L.m, L.dtype, &F.twh)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.m / 2) {
-#define DFFT_OSCONV_CASE(N, GRP, E, ...) \
-    case N: e = OsconvInst<true, N>::run(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_OSCONV_CASE)
-#undef DFFT_OSCONV_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<OsconvTag>(L.m / 2, F, stream);
         if (e == hipSuccess) return DFFT_OK;
         return fail(DFFT_EHIP, std::string("rconv_os (fused): ") + hipGetErrorString(e));
     }
     // chunks of items whose gathered blocks and bins fit the scratch buffer
-    const size_t ib = item_bytes(L.m, L.dtype);
-    long long    ni = chunk_items(L.m, L.dtype, items);
-    if (scratch_bytes / ib < (size_t)ni) ni = (long long)(scratch_bytes / ib);
-    if (!scratch || ni < 1) return fail(DFFT_EINVAL, "rconv_os: scratch buffer too small");
+    const size_t    ib = item_bytes(L.m, L.dtype);
+    const long long ni = fit_chunk_to_lease("rconv_os", chunk_units(ib, items), ib, scratch, scratch_bytes);
+    if (ni < 1) return DFFT_EINVAL;
     for (long long i0 = 0; i0 < items; i0 += ni) {
         const long long k = std::min(ni, items - i0);
         const int       rc = L.dtype == F64 ? osconv_chunk<double2>(L, nb, i0, k, scratch, stream) : osconv_chunk<float2>(L, nb, i0, k, scratch, stream);

@@ -36,9 +36,7 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the table cache and the pre / post kernels).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_bluestein.h"
 #include "dfft_long.h"
 #include "dfft_r2r.h"
@@ -88,10 +86,11 @@ constexpr bool r2r_fused_ok(int n, bool f64, bool three, int form) {
     return true;
 }
 
-// entry point of the tuned length N: defined (and explicitly instantiated) in the translation unit of N's group only
-template <bool ON, int N> struct R2rInst {};
-template <int N> struct R2rInst<true, N> {
-    static hipError_t run(const R2rFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<N>: defined in the translation unit of N's group only
+struct R2rTag {
+    using Launch = R2rFusedLaunch;
+    static constexpr bool ok(int n, bool f64, bool three, int form) { return r2r_fused_ok(n, f64, three, form); }
+    template <int N> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -362,19 +361,15 @@ template <class V, int N, bool THREE> hipError_t r2r_run_typed(const R2rFusedLau
     }
     return hipErrorInvalidValue;  // not built (r2r_fused_ok): the dispatcher does not come here
 }
-template <int N> hipError_t R2rInst<true, N>::run(const R2rFusedLaunch& F, hipStream_t stream) {
+template <int N> hipError_t R2rTag::run(const R2rFusedLaunch& F, hipStream_t stream) {
     const bool three = F.kind == R2R_DCT3 || F.kind == R2R_DST3;
     if (F.dtype == F64) return three ? r2r_run_typed<double2, N, true>(F, stream) : r2r_run_typed<double2, N, false>(F, stream);
     if (F.dtype == F32) return three ? r2r_run_typed<float2, N, true>(F, stream) : r2r_run_typed<float2, N, false>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_R2R_INST(N, GRP, E, ...) template struct R2rInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_R2R_INST)
-#undef DFFT_R2R_INST
+DFFT_FUSED_INSTANTIATE(R2rTag)
 
 #else  // the dispatcher, the table cache, and the kernels of the composed route
-
-template <int N> hipError_t r2r_fused_run(const R2rFusedLaunch& F, hipStream_t stream) { return R2rInst<true, N>::run(F, stream); }
 
 // Address map of the composed route's kernels: packed pair (u, k, pc) of z [units][n][sp] <-> reals in[u * istep + 2 pc + row * rs]
 // (+ bd for sequence b), u = batch item (columns) or row pair (rows, sp = 1); lim = s (columns) or the number of rows of the chunk.
@@ -447,28 +442,16 @@ __global__ void __launch_bounds__(256) r2r_post_kernel(const V* __restrict__ z, 
 
 namespace {
 
-constexpr size_t kR2rScratchCap = 256ull << 20;
-
-unsigned r2r_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-bool tuned_length(long long n, int dtype, bool three, int form) {
-    switch (n) {
-#define DFFT_R2R_TUNED(N, GRP, E, ...) \
-    case N: return r2r_fused_ok(N, dtype == F64, three, form);
-        DFFT_PLAN_TABLE(DFFT_R2R_TUNED)
-#undef DFFT_R2R_TUNED
-        default: return false;
-    }
-}
+bool tuned_length(long long n, int dtype, bool three, int form) { return tuned_built<R2rTag>(n, dtype == F64, three, form); }
 
 // units (batch items, or row pairs at s = 1) and packed pairs per row of a unit
 long long r2r_units(long long s, long long batch) { return s == 1 ? (batch + 1) / 2 : batch; }
 long long r2r_sp(long long s) { return s == 1 ? 1 : (s + 1) / 2; }
 
 // units per chunk of the composed route (their packed pairs within max(256 MiB, one unit's)), and the scratch such a chunk needs
-long long chunk_units(long long n, long long sp, int dtype, long long units) {
+long long r2r_chunk_units(long long n, long long sp, int dtype, long long units) {
     const size_t zb = (size_t)n * sp * elem_bytes(dtype);
-    return std::max(1ll, std::min(units, (long long)(std::max(kR2rScratchCap, zb) / zb)));
+    return chunk_units(zb, units);
 }
 size_t chunk_bytes(long long n, long long sp, int dtype, long long nu, const BluesteinTables* T, bool bs_fused) {
     const size_t zb = (size_t)nu * n * sp * elem_bytes(dtype);
@@ -506,10 +489,10 @@ int r2r_chunk(const R2rLaunch& L, const R2rTable& Wt, long long u0, long long nu
     const RT* in = (const RT*)L.in + u0 * M.istep;
     RT*       out = (RT*)L.out + u0 * M.istep;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(r2r_pre_kernel<V>, dim3(r2r_grid(M.total)), dim3(256), 0, stream, in, (V*)z, (const V*)Wt.w, M);
+    hipLaunchKernelGGL(r2r_pre_kernel<V>, dim3(elementwise_grid(M.total)), dim3(256), 0, stream, in, (V*)z, (const V*)Wt.w, M);
     DFFT_HIP_TRY(hipGetLastError());
     if (int rc = r2r_fft(z, L.n, M.sp, nu, L.dtype, M.three ? -1 : +1, T, bs_fused, inner, inner_bytes, stream)) return rc;
-    hipLaunchKernelGGL(r2r_post_kernel<V>, dim3(r2r_grid(M.total)), dim3(256), 0, stream, (const V*)z, out, (const V*)Wt.w, M);
+    hipLaunchKernelGGL(r2r_post_kernel<V>, dim3(elementwise_grid(M.total)), dim3(256), 0, stream, (const V*)z, out, (const V*)Wt.w, M);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
 }
@@ -586,10 +569,7 @@ void r2r_trim() {
     if (have_cur) (void)hipSetDevice(cur);
 }
 
-bool r2r_fused_env() {
-    const char* e = getenv("DFFT_R2R_FUSED");
-    return !(e && *e == '0');
-}
+bool r2r_fused_env() { return env_switch_on("DFFT_R2R_FUSED"); }
 
 // Fused lengths that run the composed route because it measured at least as fast (fused / composed time >= 1.0,
 // profiles/r15/README.md).  None recorded: not measured yet.
@@ -614,7 +594,7 @@ size_t r2r_scratch_bytes(const R2rLaunch& L, bool fused_on, const BluesteinTable
     const int       dtype = L.dtype;
     if (n < 1 || s < 1 || batch <= 0 || (fused_on && r2r_fused(n, s, dtype, L.kind, r2r_vec(L.in, L.out, s, dtype)))) return 0;
     const long long sp = r2r_sp(s);
-    return chunk_bytes(n, sp, dtype, chunk_units(n, sp, dtype, r2r_units(s, batch)), T, bluestein_fused);
+    return chunk_bytes(n, sp, dtype, r2r_chunk_units(n, sp, dtype, r2r_units(s, batch)), T, bluestein_fused);
 }
 
 int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
@@ -637,14 +617,7 @@ int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTa
         F.wq = Wt.w;
         F.vec = r2r_vec(L.in, L.out, L.s, L.dtype);
         if (int rc = get_twiddles((int)L.n, L.dtype, &F.tw)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.n) {
-#define DFFT_R2R_CASE(N, GRP, E, ...) \
-    case N: e = r2r_fused_run<N>(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_R2R_CASE)
-#undef DFFT_R2R_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<R2rTag>(L.n, F, stream);
         if (e == hipSuccess) return DFFT_OK;
         return fail(DFFT_EHIP, std::string(three ? "r2r type III (fused): " : "r2r type II (fused): ") + hipGetErrorString(e));
     }
@@ -654,7 +627,7 @@ int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTa
     }
     // batch chunks whose packed pairs and transform scratch fit the scratch buffer
     const long long sp = r2r_sp(L.s), units = r2r_units(L.s, L.batch);
-    long long       nu = chunk_units(L.n, sp, L.dtype, units);
+    long long       nu = r2r_chunk_units(L.n, sp, L.dtype, units);
     while (nu > 1 && chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused) > scratch_bytes) nu = (nu + 1) / 2;
     if (!scratch || chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused) > scratch_bytes) return fail(DFFT_EINVAL, "r2r: scratch buffer too small");
     const size_t zb = (size_t)nu * L.n * sp * elem_bytes(L.dtype);

@@ -23,17 +23,15 @@
 // groups are disjoint; for the same reason the kernel does not mark its real pointers __restrict__.
 //
 // Composed form (every other accepted M, the instantiations rconv_fused_ok leaves out, DFFT_RCONV_FUSED=0): per chunk of rows of at
-// most max(256 MiB, one row's) scratch -- rconv_pad_kernel into padded rows, launch_real_rows forward, rconv_mul_kernel (H / m, in place
-// on the bins), launch_real_rows backward, rconv_trunc_kernel into `out`.
+// most max(256 MiB, one row's) scratch -- pad_rows (dfft_rows_common.hip) into padded rows, launch_real_rows forward, rconv_mul_kernel
+// (H / m, in place on the bins), launch_real_rows backward, trunc_rows into `out`.
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the kernels of the composed form).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
-#include "dfft_real.h"
+#include "dfft_fused_host.h"
 #include "dfft_rconv.h"
 #include "dfft_rconv_impl.h"
+#include "dfft_rows_common.h"
 
 #include <algorithm>
 #include <atomic>
@@ -58,7 +56,7 @@ struct RconvFusedLaunch {
     const void* twh;  // e^{-2 pi i k / m}
 };
 
-// (M, dtype) whose instantiations would keep values in scratch memory (tools/rconv_resources.py, profiles/2026-10-19_rconv1d/
+// (M, dtype) whose instantiations would keep values in scratch memory (tools/fused_resources.py rconv, profiles/2026-10-19_rconv1d/
 // kernel_resources.txt) or measured slower than the composed form are not built: they run the composed form.
 constexpr bool rconv_fused_ok(int M, bool f64) {
     if (M == 3125) return false;         // 25 points per thread: 184 ... 684 bytes per lane in fp64 and fp32, either access width
@@ -66,10 +64,11 @@ constexpr bool rconv_fused_ok(int M, bool f64) {
     return true;
 }
 
-// entry point of the tuned half-length M: defined (and explicitly instantiated) in the translation unit of M's group only
-template <bool ON, int M> struct RconvInst {};
-template <int M> struct RconvInst<true, M> {
-    static hipError_t run(const RconvFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<M>: defined in the translation unit of M's group only
+struct RconvTag {
+    using Launch = RconvFusedLaunch;
+    static constexpr bool ok(int M, bool f64) { return rconv_fused_ok(M, f64); }
+    template <int M> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -106,6 +105,7 @@ rconv_rows_kernel(const typename real_of<V>::type* in, typename real_of<V>::type
         const bool      valid = row < rows;
         const long long base = valid ? (long long)row * n : 0ll;  // 64-bit row bases
         V               v[E];
+        // rrow_load (dfft_rconv_impl.h) written out: called as a function it changed this kernel's registers
         if constexpr (VEC) {  // n even: a two-real value lies wholly inside the row or wholly in the padding
             const V* ip = reinterpret_cast<const V*>(in + base);
 #pragma unroll
@@ -197,33 +197,15 @@ template <class V, int M> hipError_t rconv_run_typed(const RconvFusedLaunch& F, 
     }
     return hipErrorInvalidValue;  // not built (rconv_fused_ok): the dispatcher does not come here
 }
-template <int M> hipError_t RconvInst<true, M>::run(const RconvFusedLaunch& F, hipStream_t stream) {
+template <int M> hipError_t RconvTag::run(const RconvFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return rconv_run_typed<double2, M>(F, stream);
     if (F.dtype == F32) return rconv_run_typed<float2, M>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_RCONV_INST(N, GRP, E, ...) template struct RconvInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_RCONV_INST)
-#undef DFFT_RCONV_INST
+DFFT_FUSED_INSTANTIATE(RconvTag)
 
-#else  // the dispatcher and the kernels of the composed form
+#else  // the dispatcher and the multiply kernel of the composed form
 
-// padded rows: p[r][i] = x[r][i] (i < n), 0 (n <= i < m)
-template <class RT>
-__global__ void __launch_bounds__(256) rconv_pad_kernel(const RT* __restrict__ in, RT* __restrict__ p, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / m, i = e - r * m;
-        p[e] = i < n ? in[r * n + i] : (RT)0;
-    }
-}
-// y[r][i] = p[r][i], i < n.  `out` may be the buffer the chunk was padded from: p is the scratch.
-template <class RT>
-__global__ void __launch_bounds__(256) rconv_trunc_kernel(const RT* __restrict__ p, RT* __restrict__ out, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / n, i = e - r * n;
-        out[e] = p[r * m + i];
-    }
-}
 // bins[r][k] *= H[(row0 + r) % channels][k] / m, k <= M
 template <class V, class HT>
 __global__ void __launch_bounds__(256) rconv_mul_kernel(V* __restrict__ bins, const HT* __restrict__ h, long long nb, long long row0, long long channels,
@@ -241,26 +223,8 @@ __global__ void __launch_bounds__(256) rconv_mul_kernel(V* __restrict__ bins, co
 
 namespace {
 
-constexpr size_t kRconvScratchCap = 256ull << 20;
-
-unsigned rconv_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-bool tuned_half(long long M, int dtype) {
-    switch (M) {
-#define DFFT_RCONV_TUNED(N, GRP, E, ...) \
-    case N: return rconv_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_RCONV_TUNED)
-#undef DFFT_RCONV_TUNED
-        default: return false;
-    }
-}
-
 // one row of the composed form: its m/2 + 1 bins and its m padded reals
 size_t row_bytes(long long m, int dtype) { return (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
-long long chunk_rows(long long m, int dtype, long long rows) {
-    const size_t rb = row_bytes(m, dtype);
-    return std::max(1ll, std::min(rows, (long long)(std::max(kRconvScratchCap, rb) / rb)));
-}
 
 template <class V> int rconv_chunk(const RconvLaunch& L, long long row0, long long nr, void* scratch, hipStream_t stream) {
     using RT = typename real_of<V>::type;
@@ -269,40 +233,20 @@ template <class V> int rconv_chunk(const RconvLaunch& L, long long row0, long lo
     RT*             pad = (RT*)(bins + nr * nb);    // [nr][m]
     const RT*       in = (const RT*)L.in + row0 * n;
     RT*             out = (RT*)L.out + row0 * n;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rconv_pad_kernel<RT>, dim3(rconv_grid(nr * m)), dim3(256), 0, stream, in, pad, n, m, nr * m);
-    DFFT_HIP_TRY(hipGetLastError());
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = L.dtype;
-    R.n2 = (int)m;
-    R.rows = nr;
-    R.rows_per_plane = nr;
-    R.rpitch = m;
-    R.rplane = nr * m;
-    R.cpitch = nb;
-    R.cplane = nr * nb;
-    R.scale = 1.0;
-    R.dir = +1;
-    R.in = pad;
-    R.out = bins;
-    hipError_t e = launch_real_rows(R, stream);
+    if (int rc = pad_rows(in, pad, n, m, nr, L.dtype, stream)) return rc;
+    hipError_t e = launch_real_rows(contiguous_real_rows(L.dtype, m, nr, +1, 1.0, pad, bins), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rconv (R2C rows): ") + hipGetErrorString(e));
     if (L.filter_kind == RCONV_FILTER_REAL)
-        hipLaunchKernelGGL((rconv_mul_kernel<V, RT>), dim3(rconv_grid(nr * nb)), dim3(256), 0, stream, bins, (const RT*)L.h, nb, row0, L.channels, nr * nb,
-                           1.0 / (double)m);
+        hipLaunchKernelGGL((rconv_mul_kernel<V, RT>), dim3(elementwise_grid(nr * nb)), dim3(256), 0, stream, bins, (const RT*)L.h, nb, row0, L.channels,
+                           nr * nb, 1.0 / (double)m);
     else
-        hipLaunchKernelGGL((rconv_mul_kernel<V, V>), dim3(rconv_grid(nr * nb)), dim3(256), 0, stream, bins, (const V*)L.h, nb, row0, L.channels, nr * nb,
-                           1.0 / (double)m);
+        hipLaunchKernelGGL((rconv_mul_kernel<V, V>), dim3(elementwise_grid(nr * nb)), dim3(256), 0, stream, bins, (const V*)L.h, nb, row0, L.channels,
+                           nr * nb, 1.0 / (double)m);
     DFFT_HIP_TRY(hipGetLastError());
-    R.dir = -1;  // (the two-launch form of an untuned m/2 merges in place on its input: the bins are scratch)
-    R.in = bins;
-    R.out = pad;
-    e = launch_real_rows(R, stream);
+    // (the two-launch form of an untuned m/2 merges in place on its input: the bins are scratch)
+    e = launch_real_rows(contiguous_real_rows(L.dtype, m, nr, -1, 1.0, bins, pad), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rconv (C2R rows): ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(rconv_trunc_kernel<RT>, dim3(rconv_grid(nr * n)), dim3(256), 0, stream, (const RT*)pad, out, n, m, nr * n);
-    DFFT_HIP_TRY(hipGetLastError());
-    return DFFT_OK;
+    return trunc_rows(pad, out, n, m, nr, L.dtype, stream);
 }
 
 }  // namespace
@@ -313,10 +257,7 @@ long long rconv_length(long long at_least) {
     return 0;
 }
 
-bool rconv_fused_env() {
-    const char* e = getenv("DFFT_RCONV_FUSED");
-    return !(e && *e == '0');
-}
+bool rconv_fused_env() { return env_switch_on("DFFT_RCONV_FUSED"); }
 
 bool rconv_vec(const void* in, const void* out, long long n, int dtype) {
     return n % 2 == 0 && (uintptr_t)in % elem_bytes(dtype) == 0 && (uintptr_t)out % elem_bytes(dtype) == 0;
@@ -326,13 +267,13 @@ bool rconv_fused(long long n, long long m, int dtype, int filter_kind, bool vec)
     (void)vec;
     if (n < 1 || m < n || !real_length_supported(m) || (dtype != F64 && dtype != F32)) return false;
     if (filter_kind != RCONV_FILTER_COMPLEX && filter_kind != RCONV_FILTER_REAL) return false;
-    return tuned_half(m / 2, dtype);
+    return tuned_built<RconvTag>(m / 2, dtype == F64);
 }
 
 size_t rconv_scratch_bytes(const RconvLaunch& L, bool fused_on) {
     if (L.n < 1 || L.m < L.n || !real_length_supported(L.m) || L.channels < 1 || L.batch < 1) return 0;
     if (fused_on && rconv_fused(L.n, L.m, L.dtype, L.filter_kind, rconv_vec(L.in, L.out, L.n, L.dtype))) return 0;
-    return (size_t)chunk_rows(L.m, L.dtype, L.batch * L.channels) * row_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels) * row_bytes(L.m, L.dtype);
 }
 
 int rconv(const RconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
@@ -357,22 +298,14 @@ int rconv(const RconvLaunch& L, bool fused_on, void* scratch, size_t scratch_byt
         F.h = L.h;
         if (int rc = get_twiddles((int)(L.m / 2), L.dtype, &F.tw)) return rc;
         if (int rc = get_twiddles((int)L.m, L.dtype, &F.twh)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.m / 2) {
-#define DFFT_RCONV_CASE(N, GRP, E, ...) \
-    case N: e = RconvInst<true, N>::run(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_RCONV_CASE)
-#undef DFFT_RCONV_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<RconvTag>(L.m / 2, F, stream);
         if (e == hipSuccess) return DFFT_OK;
         return fail(DFFT_EHIP, std::string("rconv (fused): ") + hipGetErrorString(e));
     }
     // chunks of rows whose padded rows and bins fit the scratch buffer
-    const size_t rb = row_bytes(L.m, L.dtype);
-    long long    nr = chunk_rows(L.m, L.dtype, rows);
-    if (scratch_bytes / rb < (size_t)nr) nr = (long long)(scratch_bytes / rb);
-    if (!scratch || nr < 1) return fail(DFFT_EINVAL, "rconv: scratch buffer too small");
+    const size_t    rb = row_bytes(L.m, L.dtype);
+    const long long nr = fit_chunk_to_lease("rconv", chunk_units(rb, rows), rb, scratch, scratch_bytes);
+    if (nr < 1) return DFFT_EINVAL;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);
         const int       rc = L.dtype == F64 ? rconv_chunk<double2>(L, r0, k, scratch, stream) : rconv_chunk<float2>(L, r0, k, scratch, stream);

@@ -27,9 +27,7 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the pack / split / merge / unpack kernels).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_bluestein.h"
 #include "dfft_long.h"
 #include "dfft_real_cols.h"
@@ -54,10 +52,11 @@ struct ColsFusedLaunch {
     const void* tw;
 };
 
-// entry point of the tuned length N: defined (and explicitly instantiated) in the translation unit of N's group only
-template <bool ON, int N> struct ColsInst {};
-template <int N> struct ColsInst<true, N> {
-    static hipError_t run(const ColsFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h): every tuned length is built; run<N>: defined in the translation unit of N's group only
+struct ColsTag {
+    using Launch = ColsFusedLaunch;
+    static constexpr bool ok(int) { return true; }
+    template <int N> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
@@ -288,18 +287,14 @@ template <class V, class P> hipError_t launch_cols_plan(const ColsFusedLaunch& F
     return hipSuccess;
 }
 
-template <int N> hipError_t ColsInst<true, N>::run(const ColsFusedLaunch& F, hipStream_t stream) {
+template <int N> hipError_t ColsTag::run(const ColsFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return launch_cols_plan<double2, typename PlanFor<N>::type>(F, F.dir > 0, stream);
     if (F.dtype == F32) return launch_cols_plan<float2, typename PlanFor<N>::type>(F, F.dir > 0, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_COLS_INST(N, GRP, E, ...) template struct ColsInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_COLS_INST)
-#undef DFFT_COLS_INST
+DFFT_FUSED_INSTANTIATE(ColsTag)
 
 #else  // the dispatcher, and the kernels of the multi-pass form
-
-template <int N> hipError_t cols_fused_run(const ColsFusedLaunch& F, hipStream_t stream) { return ColsInst<true, N>::run(F, stream); }
 
 // z[b][k][pc] = a + i b for the real columns a = 2pc, b = 2pc + 1 (a zero column past s) of in[b][k][s]   (e runs over nb * n * sp)
 template <class V>
@@ -369,24 +364,12 @@ __global__ void __launch_bounds__(256) c2r_cols_unpack_kernel(const V* __restric
 
 namespace {
 
-constexpr size_t kColsScratchCap = 256ull << 20;
-
-unsigned cols_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-bool tuned_length(long long n) {
-    switch (n) {
-#define DFFT_COLS_TUNED(N, GRP, E, ...) case N:
-        DFFT_PLAN_TABLE(DFFT_COLS_TUNED)
-#undef DFFT_COLS_TUNED
-        return true;
-        default: return false;
-    }
-}
+bool tuned_length(long long n) { return tuned_built<ColsTag>(n); }
 
 // batch items per chunk of the multi-pass form (their packed pairs within max(256 MiB, one item's)), and the scratch such a chunk needs
 long long chunk_items(long long n, long long sp, int dtype, long long batch) {
     const size_t zb = (size_t)n * sp * elem_bytes(dtype);
-    return std::max(1ll, std::min(batch, (long long)(std::max(kColsScratchCap, zb) / zb)));
+    return chunk_units(zb, batch);
 }
 size_t chunk_bytes(long long n, long long sp, int dtype, long long nb, const BluesteinTables* T, bool bs_fused) {
     const size_t zb = (size_t)nb * n * sp * elem_bytes(dtype);
@@ -417,22 +400,22 @@ int cols_chunk(const RealColsLaunch& L, long long b0, long long nb, const Bluest
         if (s % 2 == 0 && (uintptr_t)L.in % sizeof(V) == 0) {  // `in` already is the packed complex matrix [nb][n][s/2]
             if (int rc = cols_fft(in, z, sp, nb, L, T, bs_fused, inner, inner_bytes, stream)) return rc;
         } else {
-            hipLaunchKernelGGL(r2c_cols_pack_kernel<V>, dim3(cols_grid(tz)), dim3(256), 0, stream, in, (V*)z, s, sp, tz);
+            hipLaunchKernelGGL(r2c_cols_pack_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, in, (V*)z, s, sp, tz);
             DFFT_HIP_TRY(hipGetLastError());
             if (int rc = cols_fft(z, z, sp, nb, L, T, bs_fused, inner, inner_bytes, stream)) return rc;
         }
-        hipLaunchKernelGGL(r2c_cols_split_kernel<V>, dim3(cols_grid(tb)), dim3(256), 0, stream, (const V*)z, out, n, s, sp, tb);
+        hipLaunchKernelGGL(r2c_cols_split_kernel<V>, dim3(elementwise_grid(tb)), dim3(256), 0, stream, (const V*)z, out, n, s, sp, tb);
         DFFT_HIP_TRY(hipGetLastError());
     } else {
         const V* in = (const V*)L.in + b0 * nh * s;
         RT*      out = (RT*)L.out + b0 * n * s;
-        hipLaunchKernelGGL(c2r_cols_merge_kernel<V>, dim3(cols_grid(tz)), dim3(256), 0, stream, in, (V*)z, n, s, sp, tz);
+        hipLaunchKernelGGL(c2r_cols_merge_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, in, (V*)z, n, s, sp, tz);
         DFFT_HIP_TRY(hipGetLastError());
         if (s % 2 == 0 && (uintptr_t)L.out % sizeof(V) == 0) {  // `out` viewed as complex [nb][n][s/2]
             if (int rc = cols_fft(z, out, sp, nb, L, T, bs_fused, inner, inner_bytes, stream)) return rc;
         } else {
             if (int rc = cols_fft(z, z, sp, nb, L, T, bs_fused, inner, inner_bytes, stream)) return rc;
-            hipLaunchKernelGGL(c2r_cols_unpack_kernel<V>, dim3(cols_grid(tz)), dim3(256), 0, stream, (const V*)z, out, s, sp, tz);
+            hipLaunchKernelGGL(c2r_cols_unpack_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, (const V*)z, out, s, sp, tz);
             DFFT_HIP_TRY(hipGetLastError());
         }
     }
@@ -479,14 +462,7 @@ int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_
         F.out = L.out;
         F.vec = L.s % 2 == 0 && (uintptr_t)(L.dir > 0 ? L.in : L.out) % elem_bytes(L.dtype) == 0;
         if (int rc = get_twiddles((int)L.n, L.dtype, &F.tw)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.n) {
-#define DFFT_COLS_CASE(N, GRP, E, ...) \
-    case N: e = cols_fused_run<N>(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_COLS_CASE)
-#undef DFFT_COLS_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<ColsTag>(L.n, F, stream);
         if (e == hipSuccess) return DFFT_OK;
         return fail(DFFT_EHIP, std::string(L.dir > 0 ? "R2C pair columns: " : "C2R pair columns: ") + hipGetErrorString(e));
     }

@@ -22,9 +22,7 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the odd tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the pack / split / merge / unpack kernels).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_bluestein.h"
 #include "dfft_long.h"
 #include "dfft_real_pair.h"
@@ -273,14 +271,10 @@ __global__ void __launch_bounds__(256) c2r_pair_unpack_kernel(const V* __restric
 
 namespace {
 
-constexpr size_t kPairScratchCap = 256ull << 20;
-
-unsigned pair_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
 // packed pairs per batch chunk (at most max(256 MiB, one pair's) of them), and the scratch such a chunk needs
 long long chunk_pairs(long long n, int dtype, long long pairs) {
     const size_t zb = (size_t)n * elem_bytes(dtype);
-    return std::max(1ll, std::min(pairs, (long long)(std::max(kPairScratchCap, zb) / zb)));
+    return chunk_units(zb, pairs);
 }
 size_t chunk_bytes(long long n, int dtype, long long np, const BluesteinTables* T, bool fused) {
     const size_t zb = (size_t)np * n * elem_bytes(dtype);
@@ -322,19 +316,19 @@ int pair_chunk(const RealPairLaunch& L, long long r0, long long nr, const Bluest
     const long long np = (nr + 1) / 2, tz = np * (long long)n, tb = np * (long long)(n / 2 + 1);
     (void)hipGetLastError();
     if (L.dir > 0) {
-        hipLaunchKernelGGL(r2c_pair_pack_kernel<V>, dim3(pair_grid(tz)), dim3(256), 0, stream, (const RT*)L.in, (V*)z, n, (unsigned)r0, (unsigned)nr,
+        hipLaunchKernelGGL(r2c_pair_pack_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, (const RT*)L.in, (V*)z, n, (unsigned)r0, (unsigned)nr,
                            rpp, L.rpitch, L.rplane, (unsigned)tz);
         DFFT_HIP_TRY(hipGetLastError());
         if (int rc = pair_fft(z, np, L, T, fused, inner, inner_bytes, stream)) return rc;
-        hipLaunchKernelGGL(r2c_pair_split_kernel<V>, dim3(pair_grid(tb)), dim3(256), 0, stream, (const V*)z, (V*)L.out, n, (unsigned)r0, (unsigned)nr,
+        hipLaunchKernelGGL(r2c_pair_split_kernel<V>, dim3(elementwise_grid(tb)), dim3(256), 0, stream, (const V*)z, (V*)L.out, n, (unsigned)r0, (unsigned)nr,
                            rpp, L.cpitch, L.cplane, (unsigned)tb);
         DFFT_HIP_TRY(hipGetLastError());
     } else {
-        hipLaunchKernelGGL(c2r_pair_merge_kernel<V>, dim3(pair_grid(tz)), dim3(256), 0, stream, (const V*)L.in, (V*)z, n, (unsigned)r0, (unsigned)nr,
+        hipLaunchKernelGGL(c2r_pair_merge_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, (const V*)L.in, (V*)z, n, (unsigned)r0, (unsigned)nr,
                            rpp, L.cpitch, L.cplane, (unsigned)tz);
         DFFT_HIP_TRY(hipGetLastError());
         if (int rc = pair_fft(z, np, L, T, fused, inner, inner_bytes, stream)) return rc;
-        hipLaunchKernelGGL(c2r_pair_unpack_kernel<V>, dim3(pair_grid(tz)), dim3(256), 0, stream, (const V*)z, (RT*)L.out, n, (unsigned)r0, (unsigned)nr,
+        hipLaunchKernelGGL(c2r_pair_unpack_kernel<V>, dim3(elementwise_grid(tz)), dim3(256), 0, stream, (const V*)z, (RT*)L.out, n, (unsigned)r0, (unsigned)nr,
                            rpp, L.rpitch, L.rplane, (unsigned)tz);
         DFFT_HIP_TRY(hipGetLastError());
     }

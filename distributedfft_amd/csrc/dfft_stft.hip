@@ -27,9 +27,7 @@
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
 // -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the kernels of the composed forms).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
+#include "dfft_fused_host.h"
 #include "dfft_rconv_impl.h"
 #include "dfft_real.h"
 #include "dfft_stft.h"
@@ -58,7 +56,7 @@ struct StftFusedLaunch {
     const void* twh;  // e^{-2 pi i k / m}
 };
 
-// (M, dtype) whose frame kernels would keep values in scratch memory (tools/stft_resources.py, profiles/2026-10-20_stft/
+// (M, dtype) whose frame kernels would keep values in scratch memory (tools/fused_resources.py stft, profiles/2026-10-20_stft/
 // kernel_resources.txt) are not built: they run the composed form.
 constexpr bool stft_fused_ok(int M, bool f64) {
     if (M == 2401 && f64) return false;  // 7 points per thread on 343 threads: 20 ... 28 bytes per lane (none in fp32)
@@ -66,10 +64,11 @@ constexpr bool stft_fused_ok(int M, bool f64) {
     return true;
 }
 
-// entry point of the tuned half-length M: defined (and explicitly instantiated) in the translation unit of M's group only
-template <bool ON, int M> struct StftInst {};
-template <int M> struct StftInst<true, M> {
-    static hipError_t run(const StftFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<M>: defined in the translation unit of M's group only
+struct StftTag {
+    using Launch = StftFusedLaunch;
+    static constexpr bool ok(int M, bool f64) { return stft_fused_ok(M, f64); }
+    template <int M> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 // sample s of a row of n, s outside [0, n): the mirrored index, held inside the row whatever the arguments
@@ -201,14 +200,12 @@ template <class V, int M> hipError_t stft_run_typed(const StftFusedLaunch& F, hi
     }
     return hipErrorInvalidValue;  // not built (stft_fused_ok): the dispatcher does not come here
 }
-template <int M> hipError_t StftInst<true, M>::run(const StftFusedLaunch& F, hipStream_t stream) {
+template <int M> hipError_t StftTag::run(const StftFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return stft_run_typed<double2, M>(F, stream);
     if (F.dtype == F32) return stft_run_typed<float2, M>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_STFT_INST(N, GRP, E, ...) template struct StftInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_STFT_INST)
-#undef DFFT_STFT_INST
+DFFT_FUSED_INSTANTIATE(StftTag)
 
 #else  // the dispatcher and the kernels of the composed forms
 
@@ -261,29 +258,7 @@ __global__ void __launch_bounds__(256) istft_ola_kernel(const RT* __restrict__ c
 
 namespace {
 
-constexpr size_t kStftScratchCap = 256ull << 20;
-
-// the cap on a chunk's scratch: 256 MiB, or DFFT_STFT_CHUNK_BYTES (read per call; the tests' way to make several chunks of a small problem)
-size_t chunk_cap() {
-    const char* e = getenv("DFFT_STFT_CHUNK_BYTES");
-    if (e && *e) {
-        const long long v = atoll(e);
-        if (v > 0) return (size_t)v;
-    }
-    return kStftScratchCap;
-}
-
-unsigned stft_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-bool tuned_half(long long M) {
-    switch (M) {
-#define DFFT_STFT_TUNED(N, GRP, E, ...) \
-    case N: return true;
-        DFFT_PLAN_TABLE(DFFT_STFT_TUNED)
-#undef DFFT_STFT_TUNED
-        default: return false;
-    }
-}
+bool tuned_half(long long M) { return tuned_built<AnyTuned>(M); }
 
 // forward: the m windowed reals of an item, and for the power form its m/2 + 1 bins
 size_t fwd_item_bytes(long long m, int dtype, int out_kind) {
@@ -293,10 +268,8 @@ size_t fwd_item_bytes(long long m, int dtype, int out_kind) {
 size_t inv_item_bytes(long long m, int dtype) {
     return (size_t)m * (elem_bytes(dtype) / 2) + (tuned_half(m / 2) ? 0 : (size_t)(m / 2 + 1) * elem_bytes(dtype));
 }
-long long chunk_items(size_t ib, long long items, long long at_least) {
-    const long long fit = (long long)(std::max(chunk_cap(), ib) / ib);
-    return std::max(1ll, std::min(items, std::max(fit, at_least)));
-}
+// items of a chunk: what fits 256 MiB, or DFFT_STFT_CHUNK_BYTES
+long long chunk_items(size_t ib, long long items, long long at_least) { return chunk_units(ib, items, chunk_cap_env("DFFT_STFT_CHUNK_BYTES"), at_least); }
 
 bool common_ok(int dtype, long long n, long long m, long long hop, long long pad, long long frames, long long rows) {
     return (dtype == F64 || dtype == F32) && n >= 1 && m >= 1 && hop >= 1 && pad >= 0 && pad < m && frames >= 1 && rows >= 1 && real_length_supported(m) &&
@@ -319,27 +292,13 @@ template <class V> int stft_chunk(const StftLaunch& L, long long it0, long long 
     V*              bins = (V*)scratch;                            // power form: [ni][nbins], in front so that the frames stay aligned to V
     RT*             fr = (RT*)(bins + (power ? ni * nbins : 0));   // [ni][m]
     (void)hipGetLastError();
-    hipLaunchKernelGGL(stft_gather_kernel<RT>, dim3(stft_grid(ni * m)), dim3(256), 0, stream, (const RT*)L.in, fr, (const RT*)L.win, L.n, m, L.hop, L.pad,
+    hipLaunchKernelGGL(stft_gather_kernel<RT>, dim3(elementwise_grid(ni * m)), dim3(256), 0, stream, (const RT*)L.in, fr, (const RT*)L.win, L.n, m, L.hop, L.pad,
                        L.frames, (int)(L.pad_mode == STFT_PAD_REFLECT), it0, ni * m);
     DFFT_HIP_TRY(hipGetLastError());
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = L.dtype;
-    R.n2 = (int)m;
-    R.rows = ni;
-    R.rows_per_plane = ni;
-    R.rpitch = m;
-    R.rplane = ni * m;
-    R.cpitch = nbins;
-    R.cplane = ni * nbins;
-    R.scale = L.scale;
-    R.dir = +1;
-    R.in = fr;
-    R.out = power ? (void*)bins : (void*)((V*)L.out + it0 * nbins);
-    const hipError_t e = launch_real_rows(R, stream);
+    const hipError_t e = launch_real_rows(contiguous_real_rows(L.dtype, m, ni, +1, L.scale, fr, power ? (void*)bins : (void*)((V*)L.out + it0 * nbins)), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("stft (R2C rows): ") + hipGetErrorString(e));
     if (power) {
-        hipLaunchKernelGGL(stft_power_kernel<V>, dim3(stft_grid(ni * nbins)), dim3(256), 0, stream, (const V*)bins, (RT*)L.out + it0 * nbins, ni * nbins);
+        hipLaunchKernelGGL(stft_power_kernel<V>, dim3(elementwise_grid(ni * nbins)), dim3(256), 0, stream, (const V*)bins, (RT*)L.out + it0 * nbins, ni * nbins);
         DFFT_HIP_TRY(hipGetLastError());
     }
     return DFFT_OK;
@@ -358,25 +317,11 @@ template <class V> int istft_chunk(const IstftLaunch& L, long long r0, long long
         DFFT_HIP_TRY(hipMemcpyAsync(bins, src, (size_t)ni * nbins * sizeof(V), hipMemcpyDeviceToDevice, stream));
         src = bins;
     }
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = L.dtype;
-    R.n2 = (int)m;
-    R.rows = ni;
-    R.rows_per_plane = ni;
-    R.rpitch = m;
-    R.rplane = ni * m;
-    R.cpitch = nbins;
-    R.cplane = ni * nbins;
-    R.scale = 1.0;
-    R.dir = -1;
-    R.in = src;
-    R.out = fr;
-    const hipError_t e = launch_real_rows(R, stream);
+    const hipError_t e = launch_real_rows(contiguous_real_rows(L.dtype, m, ni, -1, 1.0, src, fr), stream);
     if (e != hipSuccess) return fail(DFFT_EHIP, std::string("istft (C2R rows): ") + hipGetErrorString(e));
     const long long total = nr * (t1 - t0);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(istft_ola_kernel<RT>, dim3(stft_grid(total)), dim3(256), 0, stream, (const RT*)fr, (RT*)L.out, (const RT*)L.win, (const RT*)L.inv_env,
+    hipLaunchKernelGGL(istft_ola_kernel<RT>, dim3(elementwise_grid(total)), dim3(256), 0, stream, (const RT*)fr, (RT*)L.out, (const RT*)L.win, (const RT*)L.inv_env,
                        L.n, m, L.hop, L.pad, r0, f0, nf, t0, t1, total, 1.0 / (double)m);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
@@ -389,10 +334,7 @@ long long stft_frames(long long n, long long m, long long hop, long long pad) {
     return 1 + (n + 2 * pad - m) / hop;
 }
 
-bool stft_fused_env() {
-    const char* e = getenv("DFFT_STFT_FUSED");
-    return !(e && *e == '0');
-}
+bool stft_fused_env() { return env_switch_on("DFFT_STFT_FUSED"); }
 
 bool stft_vec(const void* in, long long n, long long hop, long long pad, int dtype) {
     return n % 2 == 0 && hop % 2 == 0 && pad % 2 == 0 && (uintptr_t)in % elem_bytes(dtype) == 0;
@@ -400,13 +342,7 @@ bool stft_vec(const void* in, long long n, long long hop, long long pad, int dty
 
 bool stft_fused(long long m, int dtype) {
     if ((dtype != F64 && dtype != F32) || m < 4 || m % 2 || !real_length_supported(m)) return false;
-    switch (m / 2) {
-#define DFFT_STFT_FUSED_CASE(N, GRP, E, ...) \
-    case N: return stft_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_STFT_FUSED_CASE)
-#undef DFFT_STFT_FUSED_CASE
-        default: return false;
-    }
+    return tuned_built<StftTag>(m / 2, dtype == F64);
 }
 
 size_t stft_scratch_bytes(const StftLaunch& L, bool fused_on) {
@@ -444,22 +380,14 @@ int stft(const StftLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes
         F.win = L.win;
         if (int rc = get_twiddles((int)(L.m / 2), L.dtype, &F.tw)) return rc;
         if (int rc = get_twiddles((int)L.m, L.dtype, &F.twh)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.m / 2) {
-#define DFFT_STFT_CASE(N, GRP, E, ...) \
-    case N: e = StftInst<true, N>::run(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_STFT_CASE)
-#undef DFFT_STFT_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<StftTag>(L.m / 2, F, stream);
         if (e == hipSuccess) return DFFT_OK;
         return fail(DFFT_EHIP, std::string("stft (fused): ") + hipGetErrorString(e));
     }
     // chunks of items whose windowed frames (and bins) fit the scratch buffer
     const size_t ib = fwd_item_bytes(L.m, L.dtype, L.out_kind);
-    long long    ni = chunk_items(ib, items, 1);
-    if (scratch_bytes / ib < (size_t)ni) ni = (long long)(scratch_bytes / ib);
-    if (!scratch || ni < 1) return fail(DFFT_EINVAL, "stft: scratch buffer too small");
+    const long long ni = fit_chunk_to_lease("stft", chunk_items(ib, items, 1), ib, scratch, scratch_bytes);
+    if (ni < 1) return DFFT_EINVAL;
     for (long long i0 = 0; i0 < items; i0 += ni) {
         const long long k = std::min(ni, items - i0);
         const int       rc = L.dtype == F64 ? stft_chunk<double2>(L, i0, k, scratch, stream) : stft_chunk<float2>(L, i0, k, scratch, stream);
@@ -472,9 +400,8 @@ int istft(const IstftLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t
     if (!L.in || !L.out || !L.win || !L.inv_env || !inv_ok(L)) return fail(DFFT_EINVAL, "istft: bad arguments");
     const size_t    ib = inv_item_bytes(L.m, L.dtype);
     const long long per = frames_per_sample(L.m, L.hop, L.frames);
-    long long       ni = chunk_items(ib, L.rows * L.frames, per);
-    if (scratch_bytes / ib < (size_t)ni) ni = (long long)(scratch_bytes / ib);
-    if (!scratch || ni < per) return fail(DFFT_EINVAL, "istft: scratch buffer too small");
+    const long long ni = fit_chunk_to_lease("istft", chunk_items(ib, L.rows * L.frames, per), ib, scratch, scratch_bytes, per);
+    if (ni < 1) return DFFT_EINVAL;
     const auto run = [&](long long r0, long long nr, long long f0, long long nf, long long t0, long long t1) {
         return L.dtype == F64 ? istft_chunk<double2>(L, r0, nr, f0, nf, t0, t1, scratch, stream)
                               : istft_chunk<float2>(L, r0, nr, f0, nf, t0, t1, scratch, stream);

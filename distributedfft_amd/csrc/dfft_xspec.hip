@@ -14,7 +14,7 @@
 // through Z[M] = Z[0]: X[0] = Re Z[0] + Im Z[0], and the thread that holds it also keeps the Nyquist bin X[M] = Re Z[0] - Im Z[0].
 // For even M the bin k = M/2 pairs with itself and the general formula holds.  After its rows the group stores its M + 1 sums times
 // 1/4, the imaginary parts of bins 0 and M as exact zeros: straight to `out` for one slice, else to partial[slice][channel][.] in the
-// scratch buffer, which rxspec_reduce_kernel sums in slice order.  No atomics: the result is the same bits from call to call.
+// scratch buffer, which slice_reduce (dfft_rows_common.hip) sums in slice order.  No atomics: the result is the same bits from call to call.
 // The auto-spectrum skips the second transform and adds |2 X[k]|^2 to the real parts alone (x_r g_i - x_i g_r of equal operands is not
 // an exact zero once the compiler contracts it into a multiply-add).
 //
@@ -23,16 +23,13 @@
 // load zeros.
 //
 // Composed form (every other accepted M, the instantiations rxspec_fused_ok leaves out, DFFT_RXSPEC_FUSED=0): per chunk of rows of at
-// most max(256 MiB, one row's) scratch -- rxspec_pad_kernel and launch_real_rows forward on both fields, rxspec_mac_kernel: one thread
+// most max(256 MiB, one row's) scratch -- pad_rows (dfft_rows_common.hip) and launch_real_rows forward on both fields, rxspec_mac_kernel: one thread
 // per (channel, bin) adds the chunk's rows of its channel to `out` in row order.  Deterministic as well.
 //
 // Compiled once per instantiation group (-DDFFT_INST_GROUP=g: the fused kernels of the tuned lengths of group g) and once with
-// -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher, the reduction and the kernels of the composed form).
-#include "dfft_fft_impl.h"
-#include "dfft_internal.h"
-#include "dfft_plans.h"
-#include "dfft_real.h"
-#include "dfft_rconv_impl.h"
+// -DDFFT_INST_GROUP=DFFT_NUM_INST_GROUPS (the dispatcher and the accumulating kernel of the composed form).
+#include "dfft_fused_host.h"
+#include "dfft_rows_common.h"
 #include "dfft_xspec.h"
 
 #include <algorithm>
@@ -58,7 +55,7 @@ struct RxspecFusedLaunch {
     const void* twh;   // e^{-2 pi i k / m}
 };
 
-// (M, dtype) whose instantiations would keep values in scratch memory (tools/rxspec_resources.py, profiles/2026-10-20_rxspec1d/
+// (M, dtype) whose instantiations would keep values in scratch memory (tools/fused_resources.py rxspec, profiles/2026-10-20_rxspec1d/
 // kernel_resources.txt) or measured slower than the composed form are not built: they run the composed form.
 constexpr bool rxspec_fused_ok(int M, bool f64) {
     if (M == 3125) return false;         // 25 points per thread: the forward kernel's exclusion, and three live arrays here
@@ -73,66 +70,14 @@ constexpr bool rxspec_fused_ok(int M, bool f64) {
 // accesses otherwise, and its 72 KiB tile allows one workgroup per CU by registers already, so the 64 KiB of slots cost no residency.
 constexpr bool rxspec_acc_lds(int M, bool f64) { return M == 4096 && f64; }
 
-// entry point of the tuned half-length M: defined (and explicitly instantiated) in the translation unit of M's group only
-template <bool ON, int M> struct RxspecInst {};
-template <int M> struct RxspecInst<true, M> {
-    static hipError_t run(const RxspecFusedLaunch& F, hipStream_t stream);
+// the family (dfft_fused_host.h); run<M>: defined in the translation unit of M's group only
+struct RxspecTag {
+    using Launch = RxspecFusedLaunch;
+    static constexpr bool ok(int M, bool f64) { return rxspec_fused_ok(M, f64); }
+    template <int M> static hipError_t run(const Launch& F, hipStream_t stream);
 };
 
 #if DFFT_INST_GROUP < DFFT_NUM_INST_GROUPS
-
-// The row at `ip` (n reals, zeros beyond; nothing is read of a row that is not `valid`) as the M complex values of a thread group
-template <class V, class P, bool VEC>
-__device__ __forceinline__ void rxspec_load(V (&v)[P::E], const typename real_of<V>::type* ip, bool valid, int n, int j) {
-    using RT = typename real_of<V>::type;
-    constexpr int E = P::E, T = P::T;
-    if constexpr (VEC) {  // n even: a two-real value lies wholly inside the row or wholly in the padding
-        const V* vp = reinterpret_cast<const V*>(ip);
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            const int kk = j + T * k;
-            v[k] = (valid && 2 * kk < n) ? vp[kk] : V{0, 0};
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            const int kk = j + T * k;
-            v[k] = V{(valid && 2 * kk < n) ? ip[2 * kk] : (RT)0, (valid && 2 * kk + 1 < n) ? ip[2 * kk + 1] : (RT)0};
-        }
-    }
-}
-
-// v: the row's M complex values -> 2 X[k] of the thread's bins k = j + T * (0 ... E-1); returns 2 X[M] in the thread of bin 0.
-// Ends behind a group barrier: every partner is read before the next transform's exchanges reuse the tile.
-template <class V, class P, class RG>
-__device__ __forceinline__ typename real_of<V>::type rxspec_bins(V (&v)[P::E], const typename VecTraits<V>::W* twr, V* lds,
-                                                                  const typename VecTraits<V>::W (&wh)[RG::TWH_REG ? P::E : 1],
-                                                                  const typename VecTraits<V>::W* __restrict__ twh, int j) {
-    using KG = typename RG::KG;
-    using W = typename VecTraits<V>::W;
-    using RT = typename real_of<V>::type;
-    constexpr int  E = P::E, T = P::T, M = P::N;
-    constexpr bool TWPOW = KG::TWMODE == TW_REG;
-    run_stages<V, P, 0, +1, 1, KG::PAD, KG::WAVE_LOCAL, KG::TWMODE, TWPOW, 1, 1, KG::NW, KG::LOCALX>(v, twr, lds, j, 0);
-    group_sync<KG::WAVE_LOCAL>();
-#pragma unroll
-    for (int k = 0; k < E; ++k) lds[lds_index<1, KG::PAD>(j + T * k, 0)] = v[k];
-    group_sync<KG::WAVE_LOCAL>();
-    RT nyq = (RT)0;
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-        const int kk = j + T * k;
-        const V   zm = lds[lds_index<1, KG::PAD>(kk == 0 ? 0 : M - kk, 0)];
-        const W   w = RG::TWH_REG ? wh[RG::TWH_REG ? k : 0] : twh[kk];
-        const V   xe{v[k].x + zm.x, v[k].y - zm.y};  // 2 Xe[k]
-        const V   xo{v[k].y + zm.y, zm.x - v[k].x};  // 2 Xo[k]
-        const V   t = cmul(xo, w);
-        if (kk == 0) nyq = xe.x - xo.x;              // 2 X[M] = 2 (Re Z[0] - Im Z[0])
-        v[k] = V{xe.x + t.x, xe.y + t.y};
-    }
-    group_sync<KG::WAVE_LOCAL>();
-    return nyq;
-}
 
 template <class V, class P, bool VEC>
 __global__ void __attribute__((amdgpu_flat_work_group_size(1, RconvGeom<V, P>::KG::THREADS)))
@@ -175,15 +120,15 @@ rxspec_rows_kernel(const typename real_of<V>::type* x, const typename real_of<V>
             const bool      live = i < count;
             const long long base = live ? ((long long)(b0 + i) * channels + c) * n : 0ll;  // 64-bit row bases
             V               v[E];
-            rxspec_load<V, P, VEC>(v, x + base, live, n, j);
-            const RT xn = rxspec_bins<V, P, RG>(v, twr, lds, wh, twh, j);
+            rrow_load<V, P, VEC>(v, x + base, live, n, j);
+            const RT xn = rrow_bins<V, P, RG>(v, twr, lds, wh, twh, j);
             RT       gn = xn;
             V        xr[E];
 #pragma unroll
             for (int k = 0; k < E; ++k) xr[k] = v[k];
             if (!autos) {  // (the same in every thread of the launch)
-                rxspec_load<V, P, VEC>(v, g + base, live, n, j);
-                gn = rxspec_bins<V, P, RG>(v, twr, lds, wh, twh, j);
+                rrow_load<V, P, VEC>(v, g + base, live, n, j);
+                gn = rrow_bins<V, P, RG>(v, twr, lds, wh, twh, j);
             }
 #pragma unroll
             for (int k = 0; k < E; ++k) {  // conj(X) G; the auto-spectrum's imaginary parts stay exact zeros
@@ -236,38 +181,15 @@ template <class V, int M> hipError_t rxspec_run_typed(const RxspecFusedLaunch& F
     if constexpr (rxspec_fused_ok(M, sizeof(V) == 16)) return F.vec ? launch_rxspec_plan<V, P, true>(F, stream) : launch_rxspec_plan<V, P, false>(F, stream);
     return hipErrorInvalidValue;  // not built (rxspec_fused_ok): the dispatcher does not come here
 }
-template <int M> hipError_t RxspecInst<true, M>::run(const RxspecFusedLaunch& F, hipStream_t stream) {
+template <int M> hipError_t RxspecTag::run(const RxspecFusedLaunch& F, hipStream_t stream) {
     if (F.dtype == F64) return rxspec_run_typed<double2, M>(F, stream);
     if (F.dtype == F32) return rxspec_run_typed<float2, M>(F, stream);
     return hipErrorInvalidValue;
 }
-#define DFFT_RXSPEC_INST(N, GRP, E, ...) template struct RxspecInst<(GRP == DFFT_INST_GROUP), N>;
-DFFT_PLAN_TABLE(DFFT_RXSPEC_INST)
-#undef DFFT_RXSPEC_INST
+DFFT_FUSED_INSTANTIATE(RxspecTag)
 
-#else  // the dispatcher, the reduction and the kernels of the composed form
+#else  // the dispatcher and the accumulating kernel of the composed form
 
-// out[e] = partial[0][e] + partial[1][e] + ... in slice order, e < ce = channels * (M + 1)
-template <class V>
-__global__ void __launch_bounds__(256) rxspec_reduce_kernel(const V* __restrict__ partial, V* __restrict__ out, long long ce, unsigned slices) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < ce; e += (long long)gridDim.x * 256) {
-        V acc = partial[e];
-        for (unsigned s = 1; s < slices; ++s) {
-            const V p = partial[(long long)s * ce + e];
-            acc.x += p.x;
-            acc.y += p.y;
-        }
-        out[e] = acc;
-    }
-}
-// padded rows: p[r][i] = x[r][i] (i < n), 0 (n <= i < m)
-template <class RT>
-__global__ void __launch_bounds__(256) rxspec_pad_kernel(const RT* __restrict__ in, RT* __restrict__ p, long long n, long long m, long long total) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long r = e / m, i = e - r * m;
-        p[e] = i < n ? in[r * n + i] : (RT)0;
-    }
-}
 // out[c][k] (+)= sum over the chunk's rows r of channel c, in row order, of conj(xb[r][k]) gb[r][k]; `first`: the chunk starts the sum.
 // Row r of the chunk is row row0 + r of the fields.  autos: gb is xb, and the sum is of |xb|^2 with exact-zero imaginary parts.
 template <class V>
@@ -295,32 +217,10 @@ __global__ void __launch_bounds__(256) rxspec_mac_kernel(const V* xb, const V* g
 
 namespace {
 
-constexpr size_t    kRxspecScratchCap = 256ull << 20;
-constexpr long long kRxspecGroupsPerPart = 512;  // resident workgroups of a 256-CU part at two per CU ...
-constexpr long long kRxspecMaxGroupFactor = 8;   // ... times the thread groups of a workgroup, at most 8: the target item count
-constexpr long long kRxspecMinRows = 8;          // rows of a slice, at least (a slice costs M + 1 stored and re-read bins)
-
-unsigned rxspec_grid(long long total) { return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16)); }
-
-// thread groups per workgroup of the fused kernel of half-length M (RconvGeom::G; 1 for an untuned M), and whether it is built
-int groups_per_workgroup(long long M) {
-    switch (M) {
-#define DFFT_RXSPEC_G(N, GRP, E, ...) \
-    case N: return RconvGeom<double2, PlanFor<N>::type>::G;
-        DFFT_PLAN_TABLE(DFFT_RXSPEC_G)
-#undef DFFT_RXSPEC_G
-        default: return 1;
-    }
-}
-bool tuned_half(long long M, int dtype) {
-    switch (M) {
-#define DFFT_RXSPEC_TUNED(N, GRP, E, ...) \
-    case N: return rxspec_fused_ok(N, dtype == F64);
-        DFFT_PLAN_TABLE(DFFT_RXSPEC_TUNED)
-#undef DFFT_RXSPEC_TUNED
-        default: return false;
-    }
-}
+// the cut into slices (slice_count): the target item count takes at most 8 thread groups of a workgroup, and a slice holds at least
+// 8 rows (it costs M + 1 stored and re-read bins)
+constexpr long long kRxspecMaxGroupFactor = 8;
+constexpr long long kRxspecMinRows = 8;
 
 bool shape_ok(const RxspecLaunch& L) {
     return L.n >= 1 && L.m >= L.n && real_length_supported(L.m) && L.channels >= 1 && L.batch >= 1 && (L.dtype == F64 || L.dtype == F32) &&
@@ -328,34 +228,14 @@ bool shape_ok(const RxspecLaunch& L) {
 }
 
 // one row of the composed form: its m/2 + 1 bins of either field and its m padded reals (shared by the two fields)
-size_t    row_bytes(long long m, int dtype) { return 2 * (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
-long long chunk_rows(long long m, int dtype, long long rows) {
-    const size_t rb = row_bytes(m, dtype);
-    return std::max(1ll, std::min(rows, (long long)(std::max(kRxspecScratchCap, rb) / rb)));
-}
+size_t row_bytes(long long m, int dtype) { return 2 * (size_t)(m / 2 + 1) * elem_bytes(dtype) + (size_t)m * (elem_bytes(dtype) / 2); }
 
-template <class V> hipError_t pad_and_transform(const void* field, long long row0, long long nr, long long n, long long m, int dtype, void* pad, V* bins, hipStream_t stream) {
+template <class V> int pad_and_transform(const void* field, long long row0, long long nr, long long n, long long m, int dtype, void* pad, V* bins, hipStream_t stream) {
     using RT = typename real_of<V>::type;
-    const long long nb = m / 2 + 1;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rxspec_pad_kernel<RT>, dim3(rxspec_grid(nr * m)), dim3(256), 0, stream, (const RT*)field + row0 * n, (RT*)pad, n, m, nr * m);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    RealLaunch R;
-    std::memset(&R, 0, sizeof(R));
-    R.dtype = dtype;
-    R.n2 = (int)m;
-    R.rows = nr;
-    R.rows_per_plane = nr;
-    R.rpitch = m;
-    R.rplane = nr * m;
-    R.cpitch = nb;
-    R.cplane = nr * nb;
-    R.scale = 1.0;
-    R.dir = +1;
-    R.in = pad;
-    R.out = bins;
-    return launch_real_rows(R, stream);
+    if (int rc = pad_rows((const RT*)field + row0 * n, pad, n, m, nr, dtype, stream)) return rc;
+    const hipError_t e = launch_real_rows(contiguous_real_rows(dtype, m, nr, +1, 1.0, pad, bins), stream);
+    if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rxspec (pad, R2C rows): ") + hipGetErrorString(e));
+    return DFFT_OK;
 }
 
 template <class V> int rxspec_chunk(const RxspecLaunch& L, long long row0, long long nr, void* scratch, hipStream_t stream) {
@@ -364,10 +244,10 @@ template <class V> int rxspec_chunk(const RxspecLaunch& L, long long row0, long 
     V*              xb = (V*)scratch;         // [nr][nb]
     V*              gb = xb + nr * nb;        // [nr][nb]
     void*           pad = (void*)(gb + nr * nb);  // [nr][m] reals, behind a multiple of sizeof(V) bytes
-    hipError_t      e = pad_and_transform<V>(L.x, row0, nr, L.n, L.m, L.dtype, pad, xb, stream);
-    if (e == hipSuccess && !autos) e = pad_and_transform<V>(L.g, row0, nr, L.n, L.m, L.dtype, pad, gb, stream);
-    if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rxspec (pad, R2C rows): ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(rxspec_mac_kernel<V>, dim3(rxspec_grid(L.channels * nb)), dim3(256), 0, stream, (const V*)xb, (const V*)(autos ? xb : gb), (V*)L.out, nb,
+    if (int rc = pad_and_transform<V>(L.x, row0, nr, L.n, L.m, L.dtype, pad, xb, stream)) return rc;
+    if (!autos)
+        if (int rc = pad_and_transform<V>(L.g, row0, nr, L.n, L.m, L.dtype, pad, gb, stream)) return rc;
+    hipLaunchKernelGGL(rxspec_mac_kernel<V>, dim3(elementwise_grid(L.channels * nb)), dim3(256), 0, stream, (const V*)xb, (const V*)(autos ? xb : gb), (V*)L.out, nb,
                        row0, nr, L.channels, row0 == 0 ? 1 : 0, autos ? 1 : 0);
     DFFT_HIP_TRY(hipGetLastError());
     return DFFT_OK;
@@ -375,10 +255,7 @@ template <class V> int rxspec_chunk(const RxspecLaunch& L, long long row0, long 
 
 }  // namespace
 
-bool rxspec_fused_env() {
-    const char* e = getenv("DFFT_RXSPEC_FUSED");
-    return !(e && *e == '0');
-}
+bool rxspec_fused_env() { return env_switch_on("DFFT_RXSPEC_FUSED"); }
 
 bool rxspec_vec(const void* x, const void* g, long long n, int dtype) {
     return n % 2 == 0 && (uintptr_t)x % elem_bytes(dtype) == 0 && (uintptr_t)g % elem_bytes(dtype) == 0;
@@ -387,15 +264,14 @@ bool rxspec_vec(const void* x, const void* g, long long n, int dtype) {
 bool rxspec_fused(long long n, long long m, int dtype, bool vec) {
     (void)vec;
     if (n < 1 || m < n || !real_length_supported(m) || (dtype != F64 && dtype != F32)) return false;
-    return tuned_half(m / 2, dtype);
+    return tuned_built<RxspecTag>(m / 2, dtype == F64);
 }
 
 long long rxspec_slices(long long m, long long channels, long long batch, int dtype) {
     if (m < 2 || !real_length_supported(m) || channels < 1 || batch < 1 || (dtype != F64 && dtype != F32) || channels >= (1ll << 31) ||
         batch >= (1ll << 31) || batch * channels >= (1ll << 31))
         return 0;
-    const long long target = kRxspecGroupsPerPart * std::min<long long>(groups_per_workgroup(m / 2), kRxspecMaxGroupFactor);
-    return std::max(1ll, std::min(target / channels, batch / kRxspecMinRows));
+    return slice_count(groups_per_workgroup(m / 2), kRxspecMaxGroupFactor, channels, batch, kRxspecMinRows);
 }
 
 size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on) {
@@ -404,7 +280,7 @@ size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on) {
         const long long slices = rxspec_slices(L.m, L.channels, L.batch, L.dtype);
         return slices > 1 ? (size_t)slices * L.channels * (L.m / 2 + 1) * elem_bytes(L.dtype) : 0;
     }
-    return (size_t)chunk_rows(L.m, L.dtype, L.batch * L.channels) * row_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels) * row_bytes(L.m, L.dtype);
 }
 
 int rxspec(const RxspecLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
@@ -430,32 +306,14 @@ int rxspec(const RxspecLaunch& L, bool fused_on, void* scratch, size_t scratch_b
         F.dest = slices > 1 ? scratch : L.out;
         if (int rc = get_twiddles((int)(L.m / 2), L.dtype, &F.tw)) return rc;
         if (int rc = get_twiddles((int)L.m, L.dtype, &F.twh)) return rc;
-        hipError_t e = hipErrorInvalidValue;
-        switch (L.m / 2) {
-#define DFFT_RXSPEC_CASE(N, GRP, E, ...) \
-    case N: e = RxspecInst<true, N>::run(F, stream); break;
-            DFFT_PLAN_TABLE(DFFT_RXSPEC_CASE)
-#undef DFFT_RXSPEC_CASE
-            default: break;
-        }
+        const hipError_t e = run_tuned<RxspecTag>(L.m / 2, F, stream);
         if (e != hipSuccess) return fail(DFFT_EHIP, std::string("rxspec (fused): ") + hipGetErrorString(e));
-        if (slices > 1) {
-            const long long ce = L.channels * nb;
-            if (L.dtype == F64)
-                hipLaunchKernelGGL(rxspec_reduce_kernel<double2>, dim3(rxspec_grid(ce)), dim3(256), 0, stream, (const double2*)scratch, (double2*)L.out, ce,
-                                   (unsigned)slices);
-            else
-                hipLaunchKernelGGL(rxspec_reduce_kernel<float2>, dim3(rxspec_grid(ce)), dim3(256), 0, stream, (const float2*)scratch, (float2*)L.out, ce,
-                                   (unsigned)slices);
-            DFFT_HIP_TRY(hipGetLastError());
-        }
-        return DFFT_OK;
+        return slices > 1 ? slice_reduce(scratch, L.out, L.channels * nb, slices, L.dtype, stream) : DFFT_OK;
     }
     // chunks of rows whose padded rows and bins fit the scratch buffer
-    const size_t rb = row_bytes(L.m, L.dtype);
-    long long    nr = chunk_rows(L.m, L.dtype, rows);
-    if (scratch_bytes / rb < (size_t)nr) nr = (long long)(scratch_bytes / rb);
-    if (!scratch || nr < 1) return fail(DFFT_EINVAL, "rxspec: scratch buffer too small");
+    const size_t    rb = row_bytes(L.m, L.dtype);
+    const long long nr = fit_chunk_to_lease("rxspec", chunk_units(rb, rows), rb, scratch, scratch_bytes);
+    if (nr < 1) return DFFT_EINVAL;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);
         const int       rc = L.dtype == F64 ? rxspec_chunk<double2>(L, r0, k, scratch, stream) : rxspec_chunk<float2>(L, r0, k, scratch, stream);

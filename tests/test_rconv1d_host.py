@@ -3,7 +3,6 @@ is queried, dfft_rconv1d_length, the route and scratch rules, a numpy model of t
 cross-compilation of the dispatcher unit, the committed resource inventory of the fused kernels, and the CPU yardstick that the GPU
 bound of tests/test_gpu_rconv1d.py is held against."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_cases as RC
 
 try:
@@ -25,7 +25,7 @@ INVENTORY = ROOT / "profiles" / "2026-10-19_rconv1d" / "kernel_resources.txt"
 SYMBOLS = ("dfft_rconv1d", "dfft_rconv1d_fused_applies", "dfft_rconv1d_scratch_bytes", "dfft_rconv1d_length")
 X, Y, HP = 0x10000000, 0x20000000, 0x30000000
 F64, F32, CPLX, REAL = 0, 1, 0, 1
-# (M, dtype) that tools/rconv_resources.py found spilling: the composed route (rconv_fused_ok of dfft_rconv.hip)
+# (M, dtype) that tools/fused_resources.py rconv found spilling: the composed route (rconv_fused_ok of dfft_rconv.hip)
 ROUTED = {(3125, F64), (3125, F32), (1536, F64)}
 
 
@@ -257,15 +257,10 @@ def test_dispatcher_unit_cross_compiles(tmp_path):
 
 # ---- resource inventory -----------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
-    """profiles/2026-10-19_rconv1d/kernel_resources.txt (tools/rconv_resources.py) must carry the sha256 of the sources in the tree and
+    """profiles/2026-10-19_rconv1d/kernel_resources.txt (tools/fused_resources.py rconv) must carry the sha256 of the sources in the tree and
     list every fused instantiation -- tuned M x fp64 / fp32 x complex / real filter x two-real / per-real accesses, less the ones
     rconv_fused_ok sends to the composed route, which it names -- with zero scratch."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_rconv.hip", "dfft_rconv.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/rconv_resources.py profiles/2026-10-19_rconv1d/kernel_resources.txt"
+    text = FI.current_text("rconv")
     fused = [ln for ln in text.splitlines() if ln.startswith("rconv_rows_kernel ")]
     m = re.search(r"^# composed-route \(M, type, filter, form\): (.*)$", text, re.M)
     assert m, "the inventory names the instantiations rconv_fused_ok sends to the composed route"
@@ -280,7 +275,8 @@ def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
         seen.add((int(g.group(2)), g.group(1), g.group(3), g.group(4)))
     assert seen == want
     assert len(fused) == len(want)
-    helpers = [ln for ln in text.splitlines() if ln.startswith(("rconv_pad_", "rconv_mul_", "rconv_trunc_"))]
+    # the multiply kernel of the unit, and the pad and truncate kernels of the common unit
+    helpers = [ln for ln in text.splitlines() if ln.startswith("rconv_mul_")] + FI.common_lines("pad_rows_", "trunc_rows_")
     assert len(helpers) == 8
     for ln in fused + helpers:
         assert re.search(r"scratch=(\d+)", ln).group(1) == "0", ln

@@ -2,7 +2,6 @@
 against numpy's irfft(rfft(x, m) * H, m)[:n], dfft_rconv1d_long_length and the split, the refusals that are decided before the device is
 queried, the scratch rule, the build units and the committed resource inventory of the kernels."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -10,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import fused_inventory as FI
 import rconv1d_long_cases as LC
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -19,7 +19,7 @@ SYMBOLS = ("dfft_rconv1d_long", "dfft_rconv1d_long_length", "dfft_rconv1d_long_s
            "dfft_rconv1d_long_fused_applies", "dfft_rconv1d_long_scratch_bytes")
 X, Y, HP = 0x10000000, 0x20000000, 0x30000000
 F64, F32, CPLX, REAL = 0, 1, 0, 1
-# (N, dtype) that tools/lconv_resources.py found spilling or tools/lconv_bench.py slower: the composed route (lconv_fused_ok of dfft_lconv.hip)
+# (N, dtype) that tools/fused_resources.py lconv found spilling or tools/lconv_bench.py slower: the composed route (lconv_fused_ok of dfft_lconv.hip)
 ROUTED = set()
 
 
@@ -236,15 +236,10 @@ def test_build_units():
 
 # ---- resource inventory -----------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
-    """profiles/2026-10-20_rconv1d_long/kernel_resources.txt (tools/lconv_resources.py) must carry the sha256 of the sources in the tree
+    """profiles/2026-10-20_rconv1d_long/kernel_resources.txt (tools/fused_resources.py lconv) must carry the sha256 of the sources in the tree
     and list every instantiation the library routes fused -- factor length x fp64 / fp32 x (pass A, pass C: two-real / per-real accesses;
     Mid: complex / real filter), less the (N, type) lconv_fused_ok sends to the composed route, which it names -- with zero scratch."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_lconv.hip", "dfft_lconv.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/lconv_resources.py profiles/2026-10-20_rconv1d_long/kernel_resources.txt"
+    text = FI.current_text("lconv")
     m = re.search(r"^# composed-route \(N, type\): (.*)$", text, re.M)
     assert m, "the inventory names the (N, type) lconv_fused_ok sends to the composed route"
     routed = {(int(n), F64 if t == "f64" else F32) for n, t in re.findall(r"\((\d+), (f64|f32)\)", m.group(1))}
@@ -259,7 +254,8 @@ def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
         assert g, ln
         seen.add((g.group(1), int(g.group(3)), g.group(2), g.group(4)))
     assert seen == want and len(fused) == len(want) == 6 * (len(LC.FACTORS) * 2 - len(routed)) - 4
-    helpers = [ln for ln in text.splitlines() if ln.startswith(("lconv_filter_", "lconv_pad_", "lconv_mul_", "lconv_trunc_"))]
+    # the filter and multiply kernels of the unit, and the pad and truncate kernels of the common unit
+    helpers = [ln for ln in text.splitlines() if ln.startswith(("lconv_filter_", "lconv_mul_"))] + FI.common_lines("pad_rows_", "trunc_rows_")
     assert len(helpers) == 11
     for ln in fused + helpers:
         assert re.search(r"scratch=(\d+)", ln).group(1) == "0", ln

@@ -3,7 +3,6 @@ the device is queried, the route and scratch rules, the block chooser, a numpy m
 store window) arithmetic, the reference against numpy.convolve, the cross-compilation of the new unit, the committed resource inventory
 of its kernels, and the CPU yardstick that the GPU bound of tests/test_gpu_rconv1d_os.py is held against."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_cases as RC
 import rconv1d_os_cases as OC
 
@@ -326,15 +326,10 @@ def test_new_unit_cross_compiles(tmp_path):
 
 # ---- resource inventories ---------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_block_kernel_spills():
-    """profiles/2026-10-20_rconv1d_os/kernel_resources.txt (tools/osconv_resources.py) must carry the sha256 of the sources in the tree
+    """profiles/2026-10-20_rconv1d_os/kernel_resources.txt (tools/fused_resources.py osconv) must carry the sha256 of the sources in the tree
     and list every block-kernel instantiation -- tuned M x fp64 / fp32 x complex / real filter x two-real / per-real accesses, less the
     ones on the composed route, which it names -- with zero scratch."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_osconv.hip", "dfft_osconv.h", "dfft_rconv_impl.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/osconv_resources.py profiles/2026-10-20_rconv1d_os/kernel_resources.txt"
+    text = FI.current_text("osconv")
     fused = [ln for ln in text.splitlines() if ln.startswith("osconv_blocks_kernel ")]
     m = re.search(r"^# composed-route \(M, type, filter, form\): (.*)$", text, re.M)
     assert m
@@ -364,11 +359,7 @@ def test_inventory_belongs_to_the_sources_and_no_block_kernel_spills():
 def test_row_kernel_takes_the_shared_types_and_its_inventory_was_regenerated():
     """dfft_rconv.hip takes RconvGeom / RconvFilter from dfft_rconv_impl.h, which the block kernel shares; its inventory was regenerated
     for the new sources (tests/test_rconv1d_host.py holds its contents)."""
-    text = OLD_INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_rconv.hip", "dfft_rconv.h"):
-        h.update((CSRC / name).read_bytes())
-    assert re.match(r"# sources sha256 ([0-9a-f]{64}) ", text).group(1) == h.hexdigest()
+    FI.current_text("rconv")   # (asserts that the inventory carries the hash of the sources in the tree)
     assert '#include "dfft_rconv_impl.h"' in (CSRC / "dfft_rconv.hip").read_text()
     assert "struct RconvGeom" not in (CSRC / "dfft_rconv.hip").read_text() and "struct RconvGeom" in (CSRC / "dfft_rconv_impl.h").read_text()
 

@@ -3,7 +3,6 @@ device is queried, the slice, route and scratch rules against their restatement 
 inventory of the fused kernels, the normalisation of api.csd / api.welch / api.coherence on a numpy model of api.rcsd1d, and the CPU
 yardstick that the GPU bound of tests/test_gpu_rcsd1d.py is held against."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_cases as RC
 import rcsd1d_cases as WC
 
@@ -229,15 +229,10 @@ def test_units_of_the_build():
 
 # ---- resource inventory -----------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
-    """profiles/2026-10-20_rcsd1d/kernel_resources.txt (tools/rcsd_resources.py) must carry the sha256 of the sources in the tree and
+    """profiles/2026-10-20_rcsd1d/kernel_resources.txt (tools/fused_resources.py rcsd) must carry the sha256 of the sources in the tree and
     list every fused instantiation -- tuned M x fp64 / fp32 x two-real / per-real accesses x auto / cross kernel, less the ones
     rcsd_fused_ok sends to the composed route, which it names -- with zero scratch; dfft_rcsd1d_fused_applies agrees with it."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_csd.hip", "dfft_csd.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/rcsd_resources.py profiles/2026-10-20_rcsd1d/kernel_resources.txt"
+    text = FI.current_text("rcsd")
     fused = [ln for ln in text.splitlines() if ln.startswith("rcsd_frames_kernel ")]
     m = re.search(r"^# composed-route \(M, type, form\): (.*)$", text, re.M)
     assert m, "the inventory names the instantiations rcsd_fused_ok sends to the composed route"
@@ -254,7 +249,8 @@ def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
         assert g, ln
         seen.add((int(g.group(2)), g.group(1), g.group(3)))
     assert seen == want and len(fused) == len(want)
-    helpers = [ln for ln in text.splitlines() if ln.startswith(("rcsd_reduce_", "rcsd_gather_", "rcsd_mac_"))]
+    # the gather and accumulating kernels of the unit, and the reduction kernel of the common unit
+    helpers = [ln for ln in text.splitlines() if ln.startswith(("rcsd_gather_", "rcsd_mac_"))] + FI.common_lines("slice_reduce_")
     assert len(helpers) == 6
     for ln in fused + helpers:
         assert re.search(r"scratch=(\d+)", ln).group(1) == "0", ln

@@ -4,7 +4,6 @@ is queried, the slice rule against a brute-force restatement, the route and scra
 against torch's CPU autograd, the cross-compilation of the dispatcher unit, the committed resource inventory of the fused kernels, and
 the CPU yardstick that the GPU bound of tests/test_gpu_rxspec1d.py is held against."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_cases as RC
 import rxspec1d_cases as XC
 
@@ -319,15 +319,10 @@ def test_dispatcher_unit_cross_compiles(tmp_path):
 
 # ---- resource inventory -----------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
-    """profiles/2026-10-20_rxspec1d/kernel_resources.txt (tools/rxspec_resources.py) must carry the sha256 of the sources in the tree and
+    """profiles/2026-10-20_rxspec1d/kernel_resources.txt (tools/fused_resources.py rxspec) must carry the sha256 of the sources in the tree and
     list every fused instantiation -- tuned M x fp64 / fp32 x two-real / per-real accesses, less the ones rxspec_fused_ok sends to the
     composed route, which it names -- with zero scratch; dfft_rxspec1d_fused_applies agrees with it."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_xspec.hip", "dfft_xspec.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/rxspec_resources.py profiles/2026-10-20_rxspec1d/kernel_resources.txt"
+    text = FI.current_text("rxspec")
     fused = [ln for ln in text.splitlines() if ln.startswith("rxspec_rows_kernel ")]
     m = re.search(r"^# composed-route \(M, type, form\): (.*)$", text, re.M)
     assert m, "the inventory names the instantiations rxspec_fused_ok sends to the composed route"
@@ -342,7 +337,8 @@ def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
         assert g, ln
         seen.add((int(g.group(2)), g.group(1), g.group(3)))
     assert seen == want and len(fused) == len(want)
-    helpers = [ln for ln in text.splitlines() if ln.startswith(("rxspec_reduce_", "rxspec_pad_", "rxspec_mac_"))]
+    # the accumulating kernel of the unit, and the reduction and pad kernels of the common unit
+    helpers = [ln for ln in text.splitlines() if ln.startswith("rxspec_mac_")] + FI.common_lines("slice_reduce_", "pad_rows_")
     assert len(helpers) == 6
     for ln in fused + helpers:
         assert re.search(r"scratch=(\d+)", ln).group(1) == "0", ln

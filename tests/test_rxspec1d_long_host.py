@@ -3,7 +3,6 @@ against numpy.fft, the gradient formulas of rconv1d_long / fftconv1d_long agains
 the library, the refusals that are decided before the device is queried, the build units, the committed resource inventory of the
 kernels, and the CPU yardstick that the bound of tests/test_gpu_rxspec1d_long.py is made from."""
 import ctypes as C
-import hashlib
 import math
 import re
 import subprocess
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_long_cases as LC
 import rxspec1d_long_cases as LX
 
@@ -278,16 +278,11 @@ def test_dispatcher_unit_cross_compiles_and_build_units(tmp_path):
 
 # ---- resource inventory -----------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
-    """profiles/2026-10-20_rxspec1d_long/kernel_resources.txt (tools/lxspec_resources.py) must carry the sha256 of the sources in the
+    """profiles/2026-10-20_rxspec1d_long/kernel_resources.txt (tools/fused_resources.py lxspec) must carry the sha256 of the sources in the
     tree and list every fused instantiation -- the accumulating Mid kernel of the 17 factor lengths above 64 x fp64 / fp32, less the
     (N2, type) lxspec_fused_ok sends to the composed route, which it names; pass A of the 18 factor lengths x fp64 / fp32 x two-real /
     per-real accesses -- with zero scratch; dfft_rxspec1d_long_fused_applies agrees with it."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_lxspec.hip", "dfft_lxspec.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/lxspec_resources.py profiles/2026-10-20_rxspec1d_long/kernel_resources.txt"
+    text = FI.current_text("lxspec")
     m = re.search(r"^# composed-route \(N2, type\): (.*)$", text, re.M)
     assert m, "the inventory names the (N2, type) lxspec_fused_ok sends to the composed route"
     routed = set(re.findall(r"\((\d+), (f64|f32)\)", m.group(1)))
@@ -310,7 +305,8 @@ def test_inventory_belongs_to_the_sources_and_no_fused_kernel_spills():
         seen_a.add((int(g.group(2)), g.group(1), g.group(3)))
     assert seen_mid == want_mid and len(mid) == len(want_mid) == 17 * 2 - len(routed)
     assert seen_a == want_a and len(pa) == len(want_a)
-    helpers = [ln for ln in text.splitlines() if ln.startswith(("lxspec_reduce_", "lxspec_pad_", "lxspec_mac_"))]
+    # the reduction and accumulating kernels of the unit, and the pad kernel of the common unit
+    helpers = [ln for ln in text.splitlines() if ln.startswith(("lxspec_reduce_", "lxspec_mac_"))] + FI.common_lines("pad_rows_")
     assert len(helpers) == 6
     for ln in mid + pa + helpers:
         assert re.search(r"scratch=(\d+)", ln).group(1) == "0", ln

@@ -2,7 +2,6 @@
 force, the refusals that are decided before the device is queried, the route and scratch rules, the cross-compilation of the new unit,
 the committed resource inventory of its kernels, and the references of tests/stft_cases.py against torch.stft / torch.istft on the CPU."""
 import ctypes as C
-import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -10,6 +9,7 @@ from pathlib import Path
 import numpy as np
 
 import accuracy_ref as A
+import fused_inventory as FI
 import rconv1d_cases as RC
 import stft_cases as SC
 
@@ -263,15 +263,10 @@ def test_new_unit_cross_compiles(tmp_path):
 
 # ---- the resource inventory -------------------------------------------------------------------------------------------------------------
 def test_inventory_belongs_to_the_sources_and_no_frame_kernel_spills():
-    """profiles/2026-10-20_stft/kernel_resources.txt (tools/stft_resources.py) must carry the sha256 of the sources in the tree and list
+    """profiles/2026-10-20_stft/kernel_resources.txt (tools/fused_resources.py stft) must carry the sha256 of the sources in the tree and list
     every frame-kernel instantiation -- tuned M x fp64 / fp32 x complex / power x two-real / per-real loads, less the ones on the
     composed route, which it names -- with zero scratch; the routed lengths are the ones stft_fused_ok names and the library routes."""
-    text = INVENTORY.read_text()
-    h = hashlib.sha256()
-    for name in ("dfft_stft.hip", "dfft_stft.h"):
-        h.update((CSRC / name).read_bytes())
-    m = re.match(r"# sources sha256 ([0-9a-f]{64}) ", text)
-    assert m and m.group(1) == h.hexdigest(), "regenerate with: python tools/stft_resources.py profiles/2026-10-20_stft/kernel_resources.txt"
+    text = FI.current_text("stft")
     fused = [ln for ln in text.splitlines() if ln.startswith("stft_frames_kernel ")]
     m = re.search(r"^# composed-route \(M, type, out, form\), stft_fused_ok: (.*)$", text, re.M)
     assert m

@@ -48,20 +48,24 @@ PLAN = plan_lengths()
 
 # ---- which entries a family instantiates ------------------------------------------------------------------------------------------------
 # family -> (source file, instantiation macro).  The macro's line reads "template struct XInst<(GRP == DFFT_INST_GROUP [&& gate]), N>":
-# the host test reads the gate from there and evaluates it with GATES.
+# the host test reads the gate from there and evaluates it with GATES.  The families of the shared scaffold (dfft_fused_host.h) have one
+# macro, DFFT_FUSED_INST, which each unit expands through DFFT_FUSED_INSTANTIATE(<its tag>): FUSED_UNITS names the unit and the tag.
+FUSED = ("dfft_fused_host.h", "DFFT_FUSED_INST")
 INSTANTIATION = {
     "real_rows": ("dfft_real.hip", "DFFT_REAL_INST"),
     "real_pair": ("dfft_real_pair.hip", "DFFT_PAIR_INST"),
-    "real_cols": ("dfft_real_cols.hip", "DFFT_COLS_INST"),
-    "r2r":       ("dfft_r2r.hip", "DFFT_R2R_INST"),
+    "real_cols": FUSED,
+    "r2r":       FUSED,
     "bluestein": ("dfft_bluestein.hip", "DFFT_BS_INST"),
-    "rconv":     ("dfft_rconv.hip", "DFFT_RCONV_INST"),
-    "osconv":    ("dfft_osconv.hip", "DFFT_OSCONV_INST"),
-    "stft":      ("dfft_stft.hip", "DFFT_STFT_INST"),
+    "rconv":     FUSED,
+    "osconv":    FUSED,
+    "stft":      FUSED,
     # not swept here (the conv modules run all of their lengths), but held to the same reading of the source
     "conv_x":       ("dfft_conv.hip", "DFFT_XC_INST"),
     "conv_x_multi": ("dfft_conv_multi.hip", "DFFT_XM_INST"),
 }
+FUSED_UNITS = {"real_cols": ("dfft_real_cols.hip", "ColsTag"), "r2r": ("dfft_r2r.hip", "R2rTag"), "rconv": ("dfft_rconv.hip", "RconvTag"),
+               "osconv": ("dfft_osconv.hip", "OsconvTag"), "stft": ("dfft_stft.hip", "StftTag")}
 
 
 def source_constant(name, file):
@@ -88,9 +92,12 @@ GATES = {
 def instantiation_gate(family):
     """The gate text of the family's instantiation macro ("" where every entry is instantiated)"""
     file, macro = INSTANTIATION[family]
-    line = re.search(r"#define " + macro + r"\(N, GRP, E, \.\.\.\) template struct \w+<\(GRP == DFFT_INST_GROUP(?: && ([^)]*(?:\([^)]*\))?[^)]*))?\), N>;",
+    line = re.search(r"#define " + macro + r"\(N, GRP, E, \.\.\.\) template struct \w+<(?:\w+, )?\(GRP == DFFT_INST_GROUP(?: && ([^)]*(?:\([^)]*\))?[^)]*))?\), N>;",
                      (CSRC / file).read_text())
     assert line, (family, "the instantiation macro is not where the sweep reads it")
+    if INSTANTIATION[family] == FUSED:   # ... and the unit expands it, once, for its own tag, in its instantiation groups
+        unit, tag = FUSED_UNITS[family]
+        assert len(re.findall(r"^DFFT_FUSED_INSTANTIATE\(" + tag + r"\)$", (CSRC / unit).read_text(), re.M)) == 1, (family, unit)
     return (line.group(1) or "").strip()
 
 
