@@ -76,10 +76,11 @@ struct RealRowsPass {
     bool               copy;      // form 1 C2R with n/2 untuned: the bins go through scratch first
     BluesteinTablesPtr t;         // forms 2 / 3 with a Bluestein n
     bool               bs_fused;
+    size_t             cap;       // chunk_cap_env() of the call
     size_t             need;      // scratch bytes
 };
 // sizes_only: tables that carry n, M and the dtype alone stand in for the cached ones -- the lease queries, which touch no device
-static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, RealRowsPass* R,
+static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bool in_is_scratch, size_t cap, RealRowsPass* R,
                              const BluesteinTables* sizes_only = nullptr) {
     const size_t    cs = elem_bytes(dtype);
     const long long nh = n / 2 + 1;
@@ -91,6 +92,7 @@ static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bo
     R->form = real_form(n);
     R->t.reset();
     R->bs_fused = true;
+    R->cap = cap;
     R->copy = false;
     R->chunk = max_rows;
     R->need = 0;
@@ -108,7 +110,7 @@ static int real_rows_prepare(long long n, long long rows, int dtype, int dir, bo
     if (length_kind(n) == 3 && !sizes_only)
         if (int rc = bluestein_tables(n, dtype, dir, &R->t)) return rc;
     R->bs_fused = bluestein_fused_env();
-    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), length_kind(n) == 3 && sizes_only ? sizes_only : R->t.get(), R->bs_fused);
+    R->need = real_pair_scratch_bytes(n, dtype, std::min(rows, max_rows), length_kind(n) == 3 && sizes_only ? sizes_only : R->t.get(), R->bs_fused, cap);
     return DFFT_OK;
 }
 static int real_rows_run(const RealRowsPass& R, const void* in, void* out, long long rows, void* scr, hipStream_t st) {
@@ -155,7 +157,7 @@ static int real_rows_run(const RealRowsPass& R, const void* in, void* out, long 
             P.rplane = m * n;
             P.cpitch = nh;
             P.cplane = m * nh;
-            rc = real_pair_rows(P, R.t.get(), R.bs_fused, scr, R.need, st);
+            rc = real_pair_rows(P, R.t.get(), R.bs_fused, R.cap, scr, R.need, st);
         }
     }
     return rc;
@@ -170,7 +172,7 @@ struct AnyPass {
     bool               bs_fused;
     size_t             need;
 };
-static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, AnyPass* A, const BluesteinTables* sizes_only = nullptr) {
+static int any_prepare(long long n, long long s, long long batch, int dtype, int dir, size_t cap, AnyPass* A, const BluesteinTables* sizes_only = nullptr) {
     A->n = n;
     A->s = s;
     A->dtype = dtype;
@@ -182,7 +184,7 @@ static int any_prepare(long long n, long long s, long long batch, int dtype, int
     if (A->kind == 3) {
         if (!sizes_only)
             if (int rc = bluestein_tables(n, dtype, dir, &A->t)) return rc;
-        A->need = bluestein_scratch_bytes(sizes_only ? *sizes_only : *A->t, s, batch, A->bs_fused);
+        A->need = bluestein_scratch_bytes(sizes_only ? *sizes_only : *A->t, s, batch, A->bs_fused, cap);
     }
     return DFFT_OK;
 }
@@ -190,6 +192,14 @@ static int any_run(const AnyPass& A, const void* in, void* out, long long batch,
     if (A.kind == 3) return bluestein_fft(*A.t, in, out, A.s, batch, 1.0, A.bs_fused, scr, A.need, st);
     if (A.kind == 2) return long_fft(in, out, A.n, A.s, batch, A.dtype, A.dir, 1.0, scr, st);
     return A.s == 1 ? dfft_fft1d_rows((void*)in, out, A.n, batch, A.dtype, A.dir, st) : dfft_fft1d_cols((void*)in, out, A.n, A.s, batch, A.dtype, A.dir, st);
+}
+
+// Rows per chunk of the composed long routes (dfft_rconv1d_long, dfft_rxspec1d_long): rows of rb bytes within max(cap, one row's), and
+// -- the padded rows are of real form 3, so rows 2p and 2p + 1 of the call share their transforms -- whole pairs unless the chunk is the
+// whole call: a chunk of an odd number of rows would pair every later row with its other neighbour.
+static long long long_composed_chunk_rows(size_t rb, long long rows, size_t cap) {
+    const long long nr = chunk_units(rb, rows, cap, 2);
+    return nr < rows ? nr - (nr & 1) : nr;
 }
 
 static void sizes_only_tables(BluesteinTables* T, long long n, int dtype, int dir) {
@@ -222,7 +232,7 @@ unsigned long long dfft_rfft1d_scratch_bytes(long long n, long long batch, int d
     BluesteinTables T;
     sizes_only_tables(&T, n, dtype, direction);
     RealRowsPass R;
-    if (real_rows_prepare(n, batch, dtype, direction, false, &R, &T)) return 0;
+    if (real_rows_prepare(n, batch, dtype, direction, false, chunk_cap_env(), &R, &T)) return 0;
     return R.need;
 }
 unsigned long long dfft_rfft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype, int direction) {
@@ -234,11 +244,12 @@ unsigned long long dfft_rfft2d_batch_scratch_bytes(long long n1, long long n2, l
     BluesteinTables T2, T1;
     sizes_only_tables(&T2, n2, dtype, direction);
     sizes_only_tables(&T1, n1, dtype, direction);
+    const size_t cap = chunk_cap_env();
     RealRowsPass R;
-    if (real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, &R, &T2)) return 0;
+    if (real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, cap, &R, &T2)) return 0;
     if (fwd) return std::max<unsigned long long>(R.need, dfft_fft1d_any_scratch_bytes(n1, nh, cp, dtype));  // two leases, one after the other
     AnyPass A;
-    if (any_prepare(n1, nh, cp, dtype, direction, &A, &T1)) return 0;
+    if (any_prepare(n1, nh, cp, dtype, direction, cap, &A, &T1)) return 0;
     return (unsigned long long)cp * cplane_b + std::max(R.need, A.need);
 }
 unsigned long long dfft_fft2d_batch_scratch_bytes(long long n1, long long n2, long long batch, int dtype) {
@@ -447,7 +458,7 @@ int dfft_rfft1d(void* in, void* out, long long n, long long batch, int dtype, in
     if (batch == 0) return DFFT_OK;
     const hipStream_t st = (hipStream_t)stream;
     RealRowsPass      R;
-    if (int rc = real_rows_prepare(n, batch, dtype, direction, false, &R)) return rc;
+    if (int rc = real_rows_prepare(n, batch, dtype, direction, false, chunk_cap_env(), &R)) return rc;
     ScratchLease lease;
     if (R.need && !lease.acquire(R.need, st)) return fail(DFFT_EHIP, "dfft_rfft1d: cannot allocate the scratch buffer");
     return real_rows_run(R, in, out, batch, lease.get(), st);
@@ -479,7 +490,8 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
     if (length_kind(n) == 3)
         if (int rc = bluestein_tables(n, dtype, direction, &t)) return rc;
     const bool       bs_fused = bluestein_fused_env();
-    const size_t     need = real_cols_scratch_bytes(n, s, batch, dtype, t.get(), bs_fused);
+    const size_t     cap = chunk_cap_env();
+    const size_t     need = real_cols_scratch_bytes(n, s, batch, dtype, t.get(), bs_fused, cap);
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rfft1d_strided: cannot allocate the scratch buffer");
     RealColsLaunch L;
@@ -491,7 +503,7 @@ int dfft_rfft1d_strided(void* in, void* out, long long n, long long s, long long
     L.dir = direction;
     L.in = in;
     L.out = out;
-    return real_cols(L, t.get(), bs_fused, lease.get(), need, st);
+    return real_cols(L, t.get(), bs_fused, cap, lease.get(), need, st);
 }
 
 // Real-to-real transforms (DCT / DST, types II and III) along the middle axis of [batch][n][s] (dfft_r2r.hip)
@@ -515,8 +527,9 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
     if (int rc = r2r_table(n, dtype, &w)) return rc;
     if (length_kind(n) == 3)
         if (int rc = bluestein_tables(n, dtype, three ? DFFT_BACKWARD : DFFT_FORWARD, &t)) return rc;
-    const bool bs_fused = bluestein_fused_env();
-    R2rLaunch  L;
+    const bool   bs_fused = bluestein_fused_env();
+    const size_t cap = chunk_cap_env();
+    R2rLaunch    L;
     std::memset(&L, 0, sizeof(L));
     L.dtype = dtype;
     L.kind = kind;
@@ -525,10 +538,10 @@ int dfft_r2r1d_strided(void* in, void* out, long long n, long long s, long long 
     L.batch = batch;
     L.in = in;
     L.out = out;
-    const size_t     need = r2r_scratch_bytes(L, fused_on, t.get(), bs_fused);
+    const size_t     need = r2r_scratch_bytes(L, fused_on, t.get(), bs_fused, cap);
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_r2r1d_strided: cannot allocate the scratch buffer");
-    return r2r(L, *w, fused_on, t.get(), bs_fused, lease.get(), need, st);
+    return r2r(L, *w, fused_on, t.get(), bs_fused, cap, lease.get(), need, st);
 }
 
 // Batched 1-D real FFT convolution of the rows of reals [batch][channels][n] with the spectra h [channels][m/2 + 1] (dfft_rconv.hip)
@@ -551,6 +564,7 @@ int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long lon
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d: no HIP device visible (no CPU fallback)");
     const hipStream_t st = (hipStream_t)stream;
     const bool        fused_on = rconv_fused_env();
+    const size_t      cap = chunk_cap_env();
     RconvLaunch       L;
     std::memset(&L, 0, sizeof(L));
     L.dtype = dtype;
@@ -562,10 +576,10 @@ int dfft_rconv1d(const void* in, void* out, const void* h, long long n, long lon
     L.in = in;
     L.out = out;
     L.h = h;
-    const size_t need = rconv_scratch_bytes(L, fused_on);
+    const size_t need = rconv_scratch_bytes(L, fused_on, cap);
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d: cannot allocate the scratch buffer");
-    return rconv(L, fused_on, lease.get(), need, st);
+    return rconv(L, fused_on, cap, lease.get(), need, st);
 }
 
 // Overlap-save 1-D real FFT convolution: rows of reals [batch][channels][n] of any length, filtered in blocks of m reals of which the
@@ -590,6 +604,7 @@ int dfft_rconv1d_os(const void* in, void* out, const void* h, long long n, long 
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d_os: no HIP device visible (no CPU fallback)");
     const hipStream_t st = (hipStream_t)stream;
     const bool        fused_on = rconv_fused_env();
+    const size_t      cap = chunk_cap_env();
     OsconvLaunch      L;
     std::memset(&L, 0, sizeof(L));
     L.dtype = dtype;
@@ -603,10 +618,10 @@ int dfft_rconv1d_os(const void* in, void* out, const void* h, long long n, long 
     L.in = in;
     L.out = out;
     L.h = h;
-    const size_t need = osconv_scratch_bytes(L, fused_on);
+    const size_t need = osconv_scratch_bytes(L, fused_on, cap);
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d_os: cannot allocate the scratch buffer");
-    return osconv(L, fused_on, lease.get(), need, st);
+    return osconv(L, fused_on, cap, lease.get(), need, st);
 }
 
 // Long 1-D real FFT convolution (dfft_lconv.hip): the padded lengths beyond dfft_rconv1d's, m/2 = N1 * N2
@@ -631,7 +646,7 @@ unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, lon
     if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || channels >= (1ll << 31) || batch >= (1ll << 31) ||
         batch * channels >= (1ll << 31))
         return 0;
-    return lconv_scratch_bytes(m, dtype, batch * channels);
+    return lconv_scratch_bytes(m, dtype, batch * channels, chunk_cap_env());
 }
 
 int dfft_rconv1d_long_filter(const void* h, void* hp, long long m, long long channels, int dtype, int filter_kind, void* stream) {
@@ -662,6 +677,7 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
         return fail(DFFT_EINVAL, "dfft_rconv1d_long: the filter overlaps out");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rconv1d_long: no HIP device visible (no CPU fallback)");
     const hipStream_t st = (hipStream_t)stream;
+    const size_t      cap = chunk_cap_env();
     ScratchLease      lease;
     if (lconv_fused_env() && lconv_fused(m, dtype)) {
         LconvLaunch L;
@@ -675,17 +691,17 @@ int dfft_rconv1d_long(void* in, void* out, const void* hp, long long n, long lon
         L.in = in;
         L.out = out;
         L.hp = hp;
-        const size_t need = lconv_scratch_bytes(m, dtype, rows);
+        const size_t need = lconv_scratch_bytes(m, dtype, rows, cap);
         if (!lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rconv1d_long: cannot allocate the scratch buffer");
-        return lconv_run(L, lease.get(), need, st);
+        return lconv_run(L, cap, lease.get(), need, st);
     }
-    // composed route, per chunk of rows of at most max(256 MiB, one row's) bins and padded rows: pad, the real rows of length m as
+    // composed route, per chunk of whole row pairs of at most max(256 MiB, one pair's) bins and padded rows: pad, the real rows of length m as
     // dfft_rfft1d runs them, multiply by H / m, the inverse rows, truncate -- on ONE lease (bins, padded rows, the transforms' own scratch)
     const size_t    rb = (size_t)nh * cs + (size_t)m * rs;
-    const long long nr = chunk_units(rb, rows);
+    const long long nr = long_composed_chunk_rows(rb, rows, cap);
     RealRowsPass    Rf, Rb;
-    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
-    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_BACKWARD, true, &Rb)) return rc;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, cap, &Rf)) return rc;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_BACKWARD, true, cap, &Rb)) return rc;
     const size_t data_b = ((size_t)nr * rb + 255) / 256 * 256;
     if (!lease.acquire(data_b + std::max(Rf.need, Rb.need), st)) return fail(DFFT_EHIP, "dfft_rconv1d_long: cannot allocate the scratch buffer");
     char* bins = (char*)lease.get();          // [nr][nh] complex
@@ -711,12 +727,12 @@ int dfft_rxspec1d_long_fused_applies(long long m, int dtype) { return valid_dtyp
 
 long long dfft_rxspec1d_long_slices(long long m, long long channels, long long batch, int dtype) {
     if (!valid_dtype(dtype) || m < 1 || channels < 1 || batch < 1 || !lxspec_rows_ok(channels, batch) || !lconv_split(m, nullptr, nullptr)) return 0;
-    return lxspec_slices(m, channels, lxspec_chunk_rows(m, dtype, batch * channels));
+    return lxspec_slices(m, channels, lxspec_chunk_rows(m, dtype, batch * channels, chunk_cap_env()));
 }
 
 unsigned long long dfft_rxspec1d_long_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
     if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || !lxspec_rows_ok(channels, batch)) return 0;
-    return lxspec_scratch_bytes(m, dtype, channels, batch * channels);
+    return lxspec_scratch_bytes(m, dtype, channels, batch * channels, chunk_cap_env());
 }
 
 int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, long long m, long long channels, long long batch, int dtype, int order,
@@ -732,6 +748,7 @@ int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, lon
         return fail(DFFT_EINVAL, "dfft_rxspec1d_long: out overlaps x or g");
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rxspec1d_long: no HIP device visible (no CPU fallback)");
     const hipStream_t st = (hipStream_t)stream;
+    const size_t      cap = chunk_cap_env();
     ScratchLease      lease;
     if (lxspec_fused_env() && lxspec_fused(m, dtype)) {
         LxspecLaunch L;
@@ -745,17 +762,17 @@ int dfft_rxspec1d_long(const void* x, const void* g, void* out, long long n, lon
         L.x = x;
         L.g = g;
         L.out = out;
-        const size_t need = lxspec_scratch_bytes(m, dtype, channels, rows);
+        const size_t need = lxspec_scratch_bytes(m, dtype, channels, rows, cap);
         if (!lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rxspec1d_long: cannot allocate the scratch buffer");
-        return lxspec_run(L, lease.get(), need, st);
+        return lxspec_run(L, cap, lease.get(), need, st);
     }
-    // composed route, per chunk of rows of at most max(256 MiB, one row's) bins of both fields and padded rows: pad, the real rows of
+    // composed route, per chunk of whole row pairs of at most max(256 MiB, one pair's) bins of both fields and padded rows: pad, the real rows of
     // length m as dfft_rfft1d runs them, on both fields, and the kernel that adds each channel's rows to out in row order -- on ONE lease
     const bool      autos = x == g;
     const size_t    rb = 2 * (size_t)nh * cs + (size_t)m * rs;
-    const long long nr = chunk_units(rb, rows);
+    const long long nr = long_composed_chunk_rows(rb, rows, cap);
     RealRowsPass    Rf;
-    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, &Rf)) return rc;
+    if (int rc = real_rows_prepare(m, nr, dtype, DFFT_FORWARD, false, cap, &Rf)) return rc;
     const size_t data_b = ((size_t)nr * rb + 255) / 256 * 256;
     if (!lease.acquire(data_b + Rf.need, st)) return fail(DFFT_EHIP, "dfft_rxspec1d_long: cannot allocate the scratch buffer");
     char* xb = (char*)lease.get();           // [nr][nh] complex
@@ -793,8 +810,9 @@ int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long
     if (batch == 0) return DFFT_OK;
     const hipStream_t st = (hipStream_t)stream;
     const long long   cp = cache_plane_group(batch, (long long)cplane_b);  // planes per group
-    RealRowsPass R;
-    if (int rc = real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, &R)) return rc;
+    const size_t      cap = chunk_cap_env();
+    RealRowsPass      R;
+    if (int rc = real_rows_prepare(n2, cp * n1, dtype, direction, !fwd, cap, &R)) return rc;
     if (fwd) {
         for (long long p0 = 0; p0 < batch; p0 += cp) {
             const long long  np = std::min(cp, batch - p0);
@@ -809,7 +827,7 @@ int dfft_rfft2d_batch(void* in, void* out, long long n1, long long n2, long long
         return DFFT_OK;
     }
     AnyPass A;
-    if (int rc = any_prepare(n1, nh, cp, dtype, direction, &A)) return rc;
+    if (int rc = any_prepare(n1, nh, cp, dtype, direction, cap, &A)) return rc;
     const size_t     gb = (size_t)cp * cplane_b;  // the bins of one plane group
     const size_t     inner = std::max(R.need, A.need);
     ScratchLease lease;  // ONE lease across the loop, sized for both steps of a group (the lease is not re-entrant)

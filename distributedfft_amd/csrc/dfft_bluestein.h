@@ -41,7 +41,7 @@ bool bluestein_fused_env();
 bool bluestein_runs_fused(long long n, long long s, bool fused);
 // Scratch bytes a call of bluestein_fft on [batch][n][s] needs (0 for the fused form); batch chunks keep it at most
 // max(256 MiB, what one transform needs).
-size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused);
+size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused, size_t cap);
 // Length-n transforms along the middle axis of data[batch][n][s], unnormalised, times `scale` (0 = 1).  in == out is allowed.
 // `scratch` holds scratch_bytes >= bluestein_scratch_bytes(T, s, 1, fused) bytes (the batch is run in chunks that fit it) and does not
 // alias in / out.  Enqueues on `stream` only; allocates nothing.

@@ -476,11 +476,10 @@ bool bluestein_runs_fused(long long n, long long s, bool fused) {
 }
 static bool runs_fused(const BluesteinTables& T, long long s, bool fused) { return bluestein_runs_fused(T.n, s, fused); }
 
-size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused) {
+size_t bluestein_scratch_bytes(const BluesteinTables& T, long long s, long long batch, bool fused, size_t cap) {
     if (runs_fused(T, s, fused) || batch <= 0 || s <= 0) return 0;
-    const size_t    per = per_transform_bytes(T, s);
-    const long long fit = std::max<long long>(1, (long long)(std::max(kScratchCap, per) / per));
-    return (size_t)std::min(batch, fit) * per;
+    const size_t per = per_transform_bytes(T, s);
+    return (size_t)chunk_units(per, batch, cap) * per;
 }
 
 int bluestein_fft(const BluesteinTables& T, const void* in, void* out, long long s, long long batch, double scale, bool fused, void* scratch,

@@ -241,14 +241,14 @@ unsigned long long dfft_fft1d_any_scratch_bytes(long long n, long long s, long l
     if (!bluestein_extent_ok(n, s, dtype)) return 0;  // refused before any lease
     BluesteinTables T;
     scratch_tables(&T, n, dtype, DFFT_FORWARD);
-    return bluestein_scratch_bytes(T, s, batch, bluestein_fused_env());
+    return bluestein_scratch_bytes(T, s, batch, bluestein_fused_env(), chunk_cap_env());
 }
 unsigned long long dfft_rfft1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype) {
     const int kind = length_kind(n);
     if (!valid_dtype(dtype) || s < 2 || batch < 1 || kind == 0) return 0;
     BluesteinTables T;
     scratch_tables(&T, n, dtype, DFFT_FORWARD);
-    return real_cols_scratch_bytes(n, s, batch, dtype, kind == 3 ? &T : nullptr, bluestein_fused_env());
+    return real_cols_scratch_bytes(n, s, batch, dtype, kind == 3 ? &T : nullptr, bluestein_fused_env(), chunk_cap_env());
 }
 unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype, int kind, int vec) {
     const int lk = length_kind(n);
@@ -263,7 +263,7 @@ unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, lo
     L.s = s;
     L.batch = batch;
     L.in = L.out = (void*)(uintptr_t)(vec ? 64 : elem_bytes(dtype) / 2);  // r2r_vec looks at the alignment only
-    return r2r_scratch_bytes(L, r2r_fused_env(), lk == 3 ? &T : nullptr, bluestein_fused_env());
+    return r2r_scratch_bytes(L, r2r_fused_env(), lk == 3 ? &T : nullptr, bluestein_fused_env(), chunk_cap_env());
 }
 
 unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
@@ -277,7 +277,7 @@ unsigned long long dfft_rconv1d_scratch_bytes(long long n, long long m, long lon
     L.m = m;
     L.channels = channels;
     L.batch = batch;
-    return rconv_scratch_bytes(L, rconv_fused_env());  // (the route depends on neither the filter kind nor the alignment)
+    return rconv_scratch_bytes(L, rconv_fused_env(), chunk_cap_env());  // (the route depends on neither the filter kind nor the alignment)
 }
 
 unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, long long discard, long long channels, long long batch, int dtype) {
@@ -291,7 +291,7 @@ unsigned long long dfft_rconv1d_os_scratch_bytes(long long n_out, long long m, l
     L.discard = discard;
     L.channels = channels;
     L.batch = batch;
-    return osconv_scratch_bytes(L, rconv_fused_env());  // (0 for refused sizes; the route depends on neither the filter kind nor the alignment)
+    return osconv_scratch_bytes(L, rconv_fused_env(), chunk_cap_env());  // (0 for refused sizes; the route depends on neither the filter kind nor the alignment)
 }
 
 int dfft_proper_device_count(const long long N[3], int ini_devices_in_rank, int nranks, int rank, int real_devices,

@@ -22,24 +22,11 @@ inline unsigned elementwise_grid(long long total) {
     return (unsigned)std::max(1ll, std::min((total + 255) / 256, (long long)device_info().cus * 16));
 }
 
-// scratch of one chunk of a composed form, at most (one unit's bytes where a unit is larger)
-constexpr size_t kScratchCap = 256ull << 20;
-
-// units (rows, items) of `unit_bytes` each per chunk: what fits `cap`, at least one and at least `at_least`, at most all of them
-inline long long chunk_units(size_t unit_bytes, long long units, size_t cap = kScratchCap, long long at_least = 1) {
+// units (rows, items) of `unit_bytes` each per chunk: what fits `cap` (chunk_cap_env, read once by the entry point), at least one and at
+// least `at_least`, at most all of them
+inline long long chunk_units(size_t unit_bytes, long long units, size_t cap, long long at_least = 1) {
     const long long fit = (long long)(std::max(cap, unit_bytes) / unit_bytes);
     return std::max(1ll, std::min(units, std::max(fit, at_least)));
-}
-
-// the cap of chunk_units: 256 MiB, or the positive value of the environment variable `name` (read per call; the tests' way to make
-// several chunks of a small problem)
-inline size_t chunk_cap_env(const char* name) {
-    const char* e = getenv(name);
-    if (e && *e) {
-        const long long v = atoll(e);
-        if (v > 0) return (size_t)v;
-    }
-    return kScratchCap;
 }
 
 // `chunk` units cut down to what the lease holds; 0, behind fail("<who>: scratch buffer too small"), where that is fewer than `at_least`

@@ -1,6 +1,7 @@
 // dfft_internal.h -- shared host-side declarations of libdfft_mi355x (not installed).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -25,6 +26,23 @@ void trace_on_error(int code, const std::string& msg);
     } while (0)
 
 inline size_t elem_bytes(int dtype) { return dtype == DFFT_F64 ? 16 : 8; }
+
+// Scratch of one chunk of a route that works through scratch: at most this (one unit's bytes where a unit is larger) ...
+constexpr size_t kScratchCap = 256ull << 20;
+// ... or the positive value of the environment variable `family` (where a family has a name of its own), else of
+// DFFT_SCRATCH_CHUNK_BYTES: the tests' way to make several chunks of a small problem.  Reads the environment, so an entry point calls
+// it ONCE per call and hands the value down (a lease query and the call it describes then cut alike, and so do nested chunkings);
+// a plan calls it when it is created and keeps the value.
+inline size_t chunk_cap_env(const char* family = nullptr) {
+    for (const char* name : {family, "DFFT_SCRATCH_CHUNK_BYTES"}) {
+        const char* e = name ? getenv(name) : nullptr;
+        if (e && *e) {
+            const long long v = atoll(e);
+            if (v > 0) return (size_t)v;
+        }
+    }
+    return kScratchCap;
+}
 
 // Slab decomposition of one axis: ceil split, the last device takes the remainder
 // (fft_mpi_3d_api.cpp:84-91).

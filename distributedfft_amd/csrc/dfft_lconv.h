@@ -39,13 +39,13 @@ bool lconv_fused_env();
 // slower than the composed route.  Depends on (m, dtype) alone.
 bool lconv_fused(long long m, int dtype);
 // Rows per chunk of the pipeline (their m/2 complex of scratch each within max(256 MiB, one row's)) and the scratch of such a chunk
-long long lconv_chunk_rows(long long m, int dtype, long long rows);
-size_t    lconv_scratch_bytes(long long m, int dtype, long long rows);
+long long lconv_chunk_rows(long long m, int dtype, long long rows, size_t cap);
+size_t    lconv_scratch_bytes(long long m, int dtype, long long rows, size_t cap);
 // The pipeline of L on `scratch` (lconv_scratch_bytes(L.m, L.dtype, rows) bytes, aliasing none of in, out, hp): per chunk of rows pass A
 // (N1-point columns of the row seen as [N1][N2] complex, times W_M^{k1 j2}, into scratch), Mid (N2-point forward, pair / multiply /
 // merge, N2-point inverse, per pair of scratch rows, in place) and pass C (times W_M^{-k1 j2}, N1-point inverse columns, the first n
 // reals into `out`).  Enqueues on `stream` only; allocates nothing once the twiddle tables of (device, m, dtype) exist.
-int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t stream);
+int lconv_run(const LconvLaunch& L, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
 // hp[c][k1 N2 + k2] = h[c][k1 + N1 k2], hp[c][M] = h[c][M]: `count` = channels * (M + 1) elements of `esize` bytes (8 or 16: the real
 // or complex type of F64; 4 or 8 of F32)

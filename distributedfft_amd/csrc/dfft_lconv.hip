@@ -503,13 +503,13 @@ bool lconv_fused(long long m, int dtype) {
     return tuned_built<LconvTag>(n1, dtype == F64) && tuned_built<LconvTag>(n2, dtype == F64);
 }
 
-long long lconv_chunk_rows(long long m, int dtype, long long rows) { return chunk_units((size_t)(m / 2) * elem_bytes(dtype), rows); }
-size_t lconv_scratch_bytes(long long m, int dtype, long long rows) {
+long long lconv_chunk_rows(long long m, int dtype, long long rows, size_t cap) { return chunk_units((size_t)(m / 2) * elem_bytes(dtype), rows, cap); }
+size_t lconv_scratch_bytes(long long m, int dtype, long long rows, size_t cap) {
     if (rows < 1 || !lconv_split(m, nullptr, nullptr)) return 0;
-    return (size_t)lconv_chunk_rows(m, dtype, rows) * (size_t)(m / 2) * elem_bytes(dtype);
+    return (size_t)lconv_chunk_rows(m, dtype, rows, cap) * (size_t)(m / 2) * elem_bytes(dtype);
 }
 
-int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int lconv_run(const LconvLaunch& L, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     int n1 = 0, n2 = 0;
     if (L.n < 1 || L.m < L.n || !lconv_split(L.m, &n1, &n2) || L.channels < 1 || L.batch < 1 || (L.dtype != F64 && L.dtype != F32) ||
         (L.filter_kind != RCONV_FILTER_COMPLEX && L.filter_kind != RCONV_FILTER_REAL) || !L.in || !L.out || !L.hp)
@@ -518,7 +518,7 @@ int lconv_run(const LconvLaunch& L, void* scratch, size_t scratch_bytes, hipStre
     const long long rows = L.batch * L.channels;
     if (rows >= (1ll << 31)) return fail(DFFT_EINVAL, "lconv: 2^31 or more rows");
     const size_t rb = (size_t)(L.m / 2) * elem_bytes(L.dtype), rs = elem_bytes(L.dtype) / 2;
-    const long long nr = fit_chunk_to_lease("lconv", lconv_chunk_rows(L.m, L.dtype, rows), rb, scratch, scratch_bytes);
+    const long long nr = fit_chunk_to_lease("lconv", lconv_chunk_rows(L.m, L.dtype, rows, cap), rb, scratch, scratch_bytes);
     if (nr < 1) return DFFT_EINVAL;
     LconvTables T;
     if (int rc = lconv_tables(L.m, n1, n2, L.dtype, &T)) return rc;

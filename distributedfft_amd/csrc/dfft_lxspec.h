@@ -21,7 +21,7 @@ struct LxspecLaunch {
     void*       out;
 };
 
-// Fixed constants of the cuts (never the device): see lxspec_slices (lxspec_chunk_rows: kScratchCap of dfft_fused_host.h)
+// Fixed constants of the cuts (never the device): see lxspec_slices (lxspec_chunk_rows: the cap of chunk_cap_env)
 constexpr long long kLxspecTargetItems = 2048;  // (slice, channel, row pair) items worth cutting the batch for
 constexpr long long kLxspecMinSteps = 8;        // rows of a channel in a slice, at least
 
@@ -31,18 +31,18 @@ bool lxspec_fused_env();
 bool lxspec_fused(long long m, int dtype);
 // Rows per chunk of the fused route: the batch * channels rows are cut, in order, into chunks whose pass-A results (m/2 complex per row
 // and field, two fields counted also for the auto-spectrum) fit max(256 MiB, one row's).
-long long lxspec_chunk_rows(long long m, int dtype, long long rows);
+long long lxspec_chunk_rows(long long m, int dtype, long long rows, size_t cap);
 // Slices of a chunk of `rows` rows: a channel has at most steps = ceil(rows / channels) rows in the chunk, and these steps are cut into
 //     slices = max(1, min(kLxspecTargetItems / (channels * ceil(N1 / 2)), steps / kLxspecMinSteps))
 // contiguous ranges, the first steps % slices of them one step longer.  0 for refused sizes.
 long long lxspec_slices(long long m, long long channels, long long rows);
 // Scratch of the fused route: chunk rows * 2 * (m/2) complex, plus the partial sums [slices of the first chunk][channels][m/2 + 1].
-size_t lxspec_scratch_bytes(long long m, int dtype, long long channels, long long rows);
+size_t lxspec_scratch_bytes(long long m, int dtype, long long channels, long long rows, size_t cap);
 // The fused route of L on `scratch` (lxspec_scratch_bytes bytes, aliasing none of x, g, out): per chunk of rows pass A on both fields
 // (one for the auto-spectrum), the accumulating Mid kernel into the partial sums, and the reduction over the slices that writes (first
 // chunk) or adds to (later chunks) `out` in the requested order.  A call of one chunk and one slice in order 1 stores straight to out.
 // Sums rows of a slice in order, slices in order, chunks in order: no atomics.  Enqueues on `stream` only.
-int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t stream);
+int lxspec_run(const LxspecLaunch& L, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
 // The accumulation of the composed route behind the real transforms of length m (dfft_batch.cpp runs those, behind pad_rows of
 // dfft_rows_common.h): out[c][.] (+)= the sum over the chunk's rows of channel c, in row order, of conj(xb) gb (row r of the chunk is row row0 + r of

@@ -477,7 +477,7 @@ bool lxspec_fused(long long m, int dtype) {
     return tuned_built<LxspecTag>(n2, dtype == F64);
 }
 
-long long lxspec_chunk_rows(long long m, int dtype, long long rows) { return chunk_units(2 * (size_t)(m / 2) * elem_bytes(dtype), rows); }
+long long lxspec_chunk_rows(long long m, int dtype, long long rows, size_t cap) { return chunk_units(2 * (size_t)(m / 2) * elem_bytes(dtype), rows, cap); }
 
 long long lxspec_slices(long long m, long long channels, long long rows) {
     int n1 = 0, n2 = 0;
@@ -486,13 +486,13 @@ long long lxspec_slices(long long m, long long channels, long long rows) {
     return std::max(1ll, std::min(kLxspecTargetItems / (channels * ((n1 + 1) / 2)), steps / kLxspecMinSteps));
 }
 
-size_t lxspec_scratch_bytes(long long m, int dtype, long long channels, long long rows) {
+size_t lxspec_scratch_bytes(long long m, int dtype, long long channels, long long rows, size_t cap) {
     if (!rows_ok(channels, rows) || !lconv_split(m, nullptr, nullptr) || (dtype != F64 && dtype != F32)) return 0;
-    const long long nr = lxspec_chunk_rows(m, dtype, rows);
+    const long long nr = lxspec_chunk_rows(m, dtype, rows, cap);
     return ((size_t)nr * 2 * (size_t)(m / 2) + (size_t)lxspec_slices(m, channels, nr) * (size_t)channels * (size_t)(m / 2 + 1)) * elem_bytes(dtype);
 }
 
-int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int lxspec_run(const LxspecLaunch& L, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     int n1 = 0, n2 = 0;
     if (L.n < 1 || L.m < L.n || !lconv_split(L.m, &n1, &n2) || L.channels < 1 || L.batch < 1 || (L.dtype != F64 && L.dtype != F32) ||
         (L.order != 0 && L.order != 1) || !L.x || !L.g || !L.out)
@@ -501,8 +501,8 @@ int lxspec_run(const LxspecLaunch& L, void* scratch, size_t scratch_bytes, hipSt
     const long long rows = L.batch * L.channels, M = L.m / 2;
     if (L.channels >= (1ll << 31) || L.batch >= (1ll << 31) || rows >= (1ll << 31)) return fail(DFFT_EINVAL, "lxspec: 2^31 or more rows");
     const size_t    cs = elem_bytes(L.dtype), rs = cs / 2;
-    const long long nr = lxspec_chunk_rows(L.m, L.dtype, rows);
-    if (!scratch || scratch_bytes < lxspec_scratch_bytes(L.m, L.dtype, L.channels, rows)) return fail(DFFT_EINVAL, "lxspec: scratch buffer too small");
+    const long long nr = lxspec_chunk_rows(L.m, L.dtype, rows, cap);
+    if (!scratch || scratch_bytes < lxspec_scratch_bytes(L.m, L.dtype, L.channels, rows, cap)) return fail(DFFT_EINVAL, "lxspec: scratch buffer too small");
     if (L.channels * ((n1 + 1) / 2) >= (1ll << 31)) return fail(DFFT_EUNSUPPORTED, "lxspec: channels * ceil(N1 / 2) = 2^31 or more items");
     LxspecTables T;
     if (int rc = lxspec_tables(L.m, n1, n2, L.dtype, &T)) return rc;

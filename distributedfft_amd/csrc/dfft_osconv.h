@@ -31,11 +31,11 @@ bool osconv_vec(const void* in, const void* out, long long n, long long n_out, l
 bool osconv_fused(long long m, int dtype);
 // Scratch bytes osconv needs: 0 for the fused kernel, else the gathered blocks and the bins of one chunk of items (an item is one
 // block of one row) of at most max(256 MiB, one item's).
-size_t osconv_scratch_bytes(const OsconvLaunch& L, bool fused_on);
+size_t osconv_scratch_bytes(const OsconvLaunch& L, bool fused_on, size_t cap);
 // The convolution of L: the fused kernel, or -- per chunk of items -- gather kernel, R2C rows (launch_real_rows), multiply kernel (H / m,
 // in place on the bins), C2R rows, scatter kernel into `out`.  `scratch` holds scratch_bytes >= one item's bytes and aliases none of
 // in, out, h.  Enqueues on `stream` only; allocates nothing (the twiddle tables of m/2 and m are cached per device).  DFFT_OK or DFFT_E*.
-int osconv(const OsconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream);
+int osconv(const OsconvLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // The block for `taps` taps and n_out results per row: discard = taps - 1 rounded up to even, and the accepted m > discard with the
 // smallest ceil(n_out / (m - discard)) * t(m) over the table of per-block times in dfft_osconv.hip; one block where one fits.
 // false: taps outside [1, 8191], n_out < 1 or a bad dtype.

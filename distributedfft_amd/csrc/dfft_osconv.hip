@@ -339,13 +339,13 @@ bool osconv_fused(long long m, int dtype) {
     return tuned_built<OsconvTag>(m / 2, dtype == F64);
 }
 
-size_t osconv_scratch_bytes(const OsconvLaunch& L, bool fused_on) {
+size_t osconv_scratch_bytes(const OsconvLaunch& L, bool fused_on, size_t cap) {
     if ((L.dtype != F64 && L.dtype != F32) || !sizes_ok(L)) return 0;
     if (fused_on && osconv_fused(L.m, L.dtype)) return 0;
-    return (size_t)chunk_units(item_bytes(L.m, L.dtype), L.batch * L.channels * osconv_blocks(L.n_out, L.m, L.discard)) * item_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(item_bytes(L.m, L.dtype), L.batch * L.channels * osconv_blocks(L.n_out, L.m, L.discard), cap) * item_bytes(L.m, L.dtype);
 }
 
-int osconv(const OsconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int osconv(const OsconvLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     if ((L.dtype != F64 && L.dtype != F32) || (L.filter_kind != RCONV_FILTER_COMPLEX && L.filter_kind != RCONV_FILTER_REAL) || !L.in || !L.out || !L.h ||
         !sizes_ok(L))
         return fail(DFFT_EINVAL, "rconv_os: bad arguments");
@@ -374,7 +374,7 @@ int osconv(const OsconvLaunch& L, bool fused_on, void* scratch, size_t scratch_b
     }
     // chunks of items whose gathered blocks and bins fit the scratch buffer
     const size_t    ib = item_bytes(L.m, L.dtype);
-    const long long ni = fit_chunk_to_lease("rconv_os", chunk_units(ib, items), ib, scratch, scratch_bytes);
+    const long long ni = fit_chunk_to_lease("rconv_os", chunk_units(ib, items, cap), ib, scratch, scratch_bytes);
     if (ni < 1) return DFFT_EINVAL;
     for (long long i0 = 0; i0 < items; i0 += ni) {
         const long long k = std::min(ni, items - i0);

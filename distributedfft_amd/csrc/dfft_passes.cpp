@@ -50,7 +50,7 @@ int bluestein_pass(const void* in, void* out, long long n, long long s, long lon
     int                rc = bluestein_tables(n, dtype, dir, &t);
     if (rc) return rc;
     const bool   fused = bluestein_fused_env();
-    const size_t need = bluestein_scratch_bytes(*t, s, batch, fused);
+    const size_t need = bluestein_scratch_bytes(*t, s, batch, fused, chunk_cap_env());
     ScratchLease lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "Bluestein pass: cannot allocate the scratch buffer");
     return bluestein_fft(*t, in, out, s, batch, scale, fused, lease.get(), need, st);

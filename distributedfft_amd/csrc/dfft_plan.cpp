@@ -1033,6 +1033,7 @@ int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2
         // (N2 wide, xs planes), X rows of the un-fused X pass (ys * N2)
         p->chunk_planes = 0;
         p->bs.fused = bluestein_fused_env();
+        const size_t cap = chunk_cap_env();  // read here only: the passes of every execute fit their chunks to the bytes sized with it
         const long long passes[3][3] = {{n0, 1, p->ys * n2}, {n1, n2, p->xs}, {n2, 1, p->xs * n1}};  // (n, s, batch) per axis
         size_t          need = 0;
         for (const auto& ps : passes) {
@@ -1040,7 +1041,7 @@ int plan_create_impl(dfft_plan_t* plan, long long n0, long long n1, long long n2
             BluesteinTablesPtr t;
             DFFT_TRY(bluestein_tables(ps[0], dtype, direction, &t));
             p->bs.tables.push_back(t);
-            need = std::max(need, bluestein_scratch_bytes(*t, ps[1], ps[2], p->bs.fused));
+            need = std::max(need, bluestein_scratch_bytes(*t, ps[1], ps[2], p->bs.fused, cap));
         }
         if (need) {
             e = hipMalloc(&p->bs.scratch, need);

@@ -197,6 +197,7 @@ struct dfft_plan_s {
     int                     real_form = 1;
     dfft::BluesteinTablesPtr rtab;
     bool                    rfused = true;  // DFFT_BLUESTEIN_FUSED when the plan was created
+    size_t                  rcap = dfft::kScratchCap;  // chunk_cap_env() when the plan was created: what sized rscratch cuts every execute
     void*                   rscratch = nullptr;
     size_t                  rscratch_bytes = 0;
     // spectral-filter plans (dfft_plan_create_conv).  The handle the caller holds has `conv` set and owns two HALF plans: a forward plan

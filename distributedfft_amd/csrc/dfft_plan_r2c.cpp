@@ -25,7 +25,7 @@ static int real_rows(dfft_plan_s* p, const void* in, void* out, int dir, long lo
         R.rplane = n1 * p->n2r;
         R.cpitch = p->cl.pitch;
         R.cplane = p->cl.plane;
-        return real_pair_rows(R, p->rtab.get(), p->rfused, p->rscratch, p->rscratch_bytes, p->stream);
+        return real_pair_rows(R, p->rtab.get(), p->rfused, p->rcap, p->rscratch, p->rscratch_bytes, p->stream);
     }
     RealLaunch      L;
     std::memset(&L, 0, sizeof(L));
@@ -180,9 +180,10 @@ int create_r2c(dfft_plan_t* plan, long long n0, long long n1, long long n2, int 
     if (form != 1) {
         // the two-for-one rows: Bluestein tables (n2 of kind 3) and the scratch of one cache chunk of rows
         p->rfused = bluestein_fused_env();
+        p->rcap = chunk_cap_env();
         if (length_kind(n2) == 3) DFFT_TRY(bluestein_tables(n2, dtype, direction, &p->rtab));
         const long long rows = (p->chunk_planes > 0 ? p->chunk_planes : p->xs) * n1;
-        p->rscratch_bytes = real_pair_scratch_bytes(n2, dtype, rows, p->rtab.get(), p->rfused);
+        p->rscratch_bytes = real_pair_scratch_bytes(n2, dtype, rows, p->rtab.get(), p->rfused, p->rcap);
         if (p->rscratch_bytes && (e = hipMalloc(&p->rscratch, p->rscratch_bytes)) != hipSuccess)
             return fail(DFFT_EHIP, fn + ": scratch of the real rows: " + hipGetErrorString(e));
     }

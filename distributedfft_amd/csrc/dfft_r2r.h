@@ -51,12 +51,12 @@ bool r2r_fused(long long n, long long s, int dtype, int kind, bool vec);
 // Scratch bytes r2r needs: 0 for the fused forms, else the packed pairs of one batch chunk (at most max(256 MiB, one item's or pair's))
 // plus the scratch of the n-point transform on that chunk (four-step: as much again; Bluestein: bluestein_scratch_bytes).
 // `T`: the Bluestein tables of (n, dtype, +1 for type II / -1 for type III) when n is a Bluestein length, else nullptr.
-size_t r2r_scratch_bytes(const R2rLaunch& L, bool fused_on, const BluesteinTables* T, bool bluestein_fused);
+size_t r2r_scratch_bytes(const R2rLaunch& L, bool fused_on, const BluesteinTables* T, bool bluestein_fused, size_t cap);
 // The transform of L: the fused kernel, or -- per batch chunk -- pre kernel (permute or pre-twiddle, pack pairs into scratch), the n-point
 // complex transform on the scratch (the C2C row / column launch, long_fft or bluestein_fft with T), post kernel into `out`.  `scratch`
 // holds scratch_bytes >= r2r_scratch_bytes(L with batch 1, ...) bytes and aliases neither in nor out.  Enqueues on `stream` only; allocates
 // nothing.  DFFT_OK or DFFT_E*.
-int r2r(const R2rLaunch& L, const R2rTable& W, bool fused_on, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
+int r2r(const R2rLaunch& L, const R2rTable& W, bool fused_on, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes,
         hipStream_t stream);
 
 }  // namespace dfft

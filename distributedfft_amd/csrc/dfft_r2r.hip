@@ -449,13 +449,13 @@ long long r2r_units(long long s, long long batch) { return s == 1 ? (batch + 1) 
 long long r2r_sp(long long s) { return s == 1 ? 1 : (s + 1) / 2; }
 
 // units per chunk of the composed route (their packed pairs within max(256 MiB, one unit's)), and the scratch such a chunk needs
-long long r2r_chunk_units(long long n, long long sp, int dtype, long long units) {
+long long r2r_chunk_units(long long n, long long sp, int dtype, long long units, size_t cap) {
     const size_t zb = (size_t)n * sp * elem_bytes(dtype);
-    return chunk_units(zb, units);
+    return chunk_units(zb, units, cap);
 }
-size_t chunk_bytes(long long n, long long sp, int dtype, long long nu, const BluesteinTables* T, bool bs_fused) {
+size_t chunk_bytes(long long n, long long sp, int dtype, long long nu, const BluesteinTables* T, bool bs_fused, size_t cap) {
     const size_t zb = (size_t)nu * n * sp * elem_bytes(dtype);
-    if (T) return zb + bluestein_scratch_bytes(*T, sp, nu, bs_fused);
+    if (T) return zb + bluestein_scratch_bytes(*T, sp, nu, bs_fused, cap);
     return n > 4096 ? 2 * zb : zb;  // four-step: long_fft's scratch as large as its data
 }
 
@@ -589,15 +589,15 @@ bool r2r_vec(const void* in, const void* out, long long s, int dtype) {
     return s > 1 && s % 2 == 0 && (uintptr_t)in % elem_bytes(dtype) == 0 && (uintptr_t)out % elem_bytes(dtype) == 0;
 }
 
-size_t r2r_scratch_bytes(const R2rLaunch& L, bool fused_on, const BluesteinTables* T, bool bluestein_fused) {
+size_t r2r_scratch_bytes(const R2rLaunch& L, bool fused_on, const BluesteinTables* T, bool bluestein_fused, size_t cap) {
     const long long n = L.n, s = L.s, batch = L.batch;
     const int       dtype = L.dtype;
     if (n < 1 || s < 1 || batch <= 0 || (fused_on && r2r_fused(n, s, dtype, L.kind, r2r_vec(L.in, L.out, s, dtype)))) return 0;
     const long long sp = r2r_sp(s);
-    return chunk_bytes(n, sp, dtype, r2r_chunk_units(n, sp, dtype, r2r_units(s, batch)), T, bluestein_fused);
+    return chunk_bytes(n, sp, dtype, r2r_chunk_units(n, sp, dtype, r2r_units(s, batch), cap), T, bluestein_fused, cap);
 }
 
-int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
+int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes,
         hipStream_t stream) {
     if (L.n < 1 || L.s < 1 || L.batch < 0 || L.kind < R2R_DCT2 || L.kind > R2R_DST3 || (L.dtype != F64 && L.dtype != F32) || !L.in || !L.out)
         return fail(DFFT_EINVAL, "r2r: bad arguments");
@@ -627,9 +627,9 @@ int r2r(const R2rLaunch& L, const R2rTable& Wt, bool fused_on, const BluesteinTa
     }
     // batch chunks whose packed pairs and transform scratch fit the scratch buffer
     const long long sp = r2r_sp(L.s), units = r2r_units(L.s, L.batch);
-    long long       nu = r2r_chunk_units(L.n, sp, L.dtype, units);
-    while (nu > 1 && chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused) > scratch_bytes) nu = (nu + 1) / 2;
-    if (!scratch || chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused) > scratch_bytes) return fail(DFFT_EINVAL, "r2r: scratch buffer too small");
+    long long       nu = r2r_chunk_units(L.n, sp, L.dtype, units, cap);
+    while (nu > 1 && chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused, cap) > scratch_bytes) nu = (nu + 1) / 2;
+    if (!scratch || chunk_bytes(L.n, sp, L.dtype, nu, T, bluestein_fused, cap) > scratch_bytes) return fail(DFFT_EINVAL, "r2r: scratch buffer too small");
     const size_t zb = (size_t)nu * L.n * sp * elem_bytes(L.dtype);
     void*        inner = (char*)scratch + zb;
     const size_t inner_bytes = scratch_bytes - zb;

@@ -34,11 +34,11 @@ bool rconv_vec(const void* in, const void* out, long long n, int dtype);
 bool rconv_fused(long long n, long long m, int dtype, int filter_kind, bool vec);
 // Scratch bytes rconv needs: 0 for the fused kernel, else the padded rows and the bins of one batch chunk of at most
 // max(256 MiB, one row's).
-size_t rconv_scratch_bytes(const RconvLaunch& L, bool fused_on);
+size_t rconv_scratch_bytes(const RconvLaunch& L, bool fused_on, size_t cap);
 // The convolution of L: the fused kernel, or -- per chunk of rows -- pad kernel, R2C rows (launch_real_rows), multiply kernel (H / m, in
 // place on the bins), C2R rows, truncate kernel into `out`.  `scratch` holds scratch_bytes >= rconv_scratch_bytes(L with one row)
 // bytes and aliases none of in, out, h.  Enqueues on `stream` only; allocates nothing (the twiddle tables of m/2 and m are cached per
 // device).  DFFT_OK or DFFT_E*.
-int rconv(const RconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream);
+int rconv(const RconvLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
 }  // namespace dfft

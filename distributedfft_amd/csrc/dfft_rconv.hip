@@ -270,13 +270,13 @@ bool rconv_fused(long long n, long long m, int dtype, int filter_kind, bool vec)
     return tuned_built<RconvTag>(m / 2, dtype == F64);
 }
 
-size_t rconv_scratch_bytes(const RconvLaunch& L, bool fused_on) {
+size_t rconv_scratch_bytes(const RconvLaunch& L, bool fused_on, size_t cap) {
     if (L.n < 1 || L.m < L.n || !real_length_supported(L.m) || L.channels < 1 || L.batch < 1) return 0;
     if (fused_on && rconv_fused(L.n, L.m, L.dtype, L.filter_kind, rconv_vec(L.in, L.out, L.n, L.dtype))) return 0;
-    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels) * row_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels, cap) * row_bytes(L.m, L.dtype);
 }
 
-int rconv(const RconvLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int rconv(const RconvLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     if (L.n < 1 || L.m < L.n || !real_length_supported(L.m) || L.channels < 1 || L.batch < 1 || (L.dtype != F64 && L.dtype != F32) ||
         (L.filter_kind != RCONV_FILTER_COMPLEX && L.filter_kind != RCONV_FILTER_REAL) || !L.in || !L.out || !L.h)
         return fail(DFFT_EINVAL, "rconv: bad arguments");
@@ -304,7 +304,7 @@ int rconv(const RconvLaunch& L, bool fused_on, void* scratch, size_t scratch_byt
     }
     // chunks of rows whose padded rows and bins fit the scratch buffer
     const size_t    rb = row_bytes(L.m, L.dtype);
-    const long long nr = fit_chunk_to_lease("rconv", chunk_units(rb, rows), rb, scratch, scratch_bytes);
+    const long long nr = fit_chunk_to_lease("rconv", chunk_units(rb, rows, cap), rb, scratch, scratch_bytes);
     if (nr < 1) return DFFT_EINVAL;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);

@@ -30,13 +30,13 @@ bool real_cols_fused(long long n, long long s, int dtype);
 // Scratch bytes real_cols needs: 0 for the fused form, else the packed column pairs of one batch chunk (at most max(256 MiB, one batch
 // item's)) plus the scratch of the n-point transform on that chunk (four-step: as much again; Bluestein: bluestein_scratch_bytes).
 // `T`: the Bluestein tables of (n, dtype, dir) when n is a Bluestein length, else nullptr.
-size_t real_cols_scratch_bytes(long long n, long long s, long long batch, int dtype, const BluesteinTables* T, bool bluestein_fused);
+size_t real_cols_scratch_bytes(long long n, long long s, long long batch, int dtype, const BluesteinTables* T, bool bluestein_fused, size_t cap);
 // The transform of L: the fused kernel, or -- per batch chunk -- pack (skipped where s is even and `in` is aligned to a complex element),
 // the n-point complex transform down the column pairs (the C2C column launch, long_fft or bluestein_fft with T), split (R2C); merge,
 // inverse transform, unpack (C2R; the transform stores straight into `out` where s is even and `out` is aligned).  `scratch` holds
 // scratch_bytes >= real_cols_scratch_bytes(n, s, 1, dtype, T, bluestein_fused) bytes and does not alias in / out; `in` is never
 // written.  Enqueues on `stream` only; allocates nothing.  DFFT_OK or DFFT_E*.
-int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
+int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes,
               hipStream_t stream);
 
 }  // namespace dfft

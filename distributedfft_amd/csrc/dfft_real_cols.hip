@@ -367,13 +367,13 @@ namespace {
 bool tuned_length(long long n) { return tuned_built<ColsTag>(n); }
 
 // batch items per chunk of the multi-pass form (their packed pairs within max(256 MiB, one item's)), and the scratch such a chunk needs
-long long chunk_items(long long n, long long sp, int dtype, long long batch) {
+long long chunk_items(long long n, long long sp, int dtype, long long batch, size_t cap) {
     const size_t zb = (size_t)n * sp * elem_bytes(dtype);
-    return chunk_units(zb, batch);
+    return chunk_units(zb, batch, cap);
 }
-size_t chunk_bytes(long long n, long long sp, int dtype, long long nb, const BluesteinTables* T, bool bs_fused) {
+size_t chunk_bytes(long long n, long long sp, int dtype, long long nb, const BluesteinTables* T, bool bs_fused, size_t cap) {
     const size_t zb = (size_t)nb * n * sp * elem_bytes(dtype);
-    if (T) return zb + bluestein_scratch_bytes(*T, sp, nb, bs_fused);
+    if (T) return zb + bluestein_scratch_bytes(*T, sp, nb, bs_fused, cap);
     return n > 4096 ? 2 * zb : zb;  // four-step: long_fft's scratch as large as its data
 }
 
@@ -440,13 +440,13 @@ bool real_cols_fused(long long n, long long s, int dtype) {
     return tuned_length(n) && s >= 1 && n * s < (1ll << 31) && !multi_pass_faster(n, s, dtype);
 }
 
-size_t real_cols_scratch_bytes(long long n, long long s, long long batch, int dtype, const BluesteinTables* T, bool bluestein_fused) {
+size_t real_cols_scratch_bytes(long long n, long long s, long long batch, int dtype, const BluesteinTables* T, bool bluestein_fused, size_t cap) {
     if (n < 1 || s < 1 || batch <= 0 || real_cols_fused(n, s, dtype)) return 0;
     const long long sp = (s + 1) / 2;
-    return chunk_bytes(n, sp, dtype, chunk_items(n, sp, dtype, batch), T, bluestein_fused);
+    return chunk_bytes(n, sp, dtype, chunk_items(n, sp, dtype, batch, cap), T, bluestein_fused, cap);
 }
 
-int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     if (L.n < 1 || L.s < 1 || L.batch < 0 || (L.dir != 1 && L.dir != -1) || (L.dtype != F64 && L.dtype != F32) || !L.in || !L.out)
         return fail(DFFT_EINVAL, "real columns: bad arguments");
     if (L.batch == 0) return DFFT_OK;
@@ -472,9 +472,9 @@ int real_cols(const RealColsLaunch& L, const BluesteinTables* T, bool bluestein_
     }
     // batch chunks whose packed pairs and transform scratch fit the scratch buffer
     const long long sp = (L.s + 1) / 2;
-    long long       nb = chunk_items(L.n, sp, L.dtype, L.batch);
-    while (nb > 1 && chunk_bytes(L.n, sp, L.dtype, nb, T, bluestein_fused) > scratch_bytes) nb = (nb + 1) / 2;
-    if (!scratch || chunk_bytes(L.n, sp, L.dtype, nb, T, bluestein_fused) > scratch_bytes) return fail(DFFT_EINVAL, "real columns: scratch buffer too small");
+    long long       nb = chunk_items(L.n, sp, L.dtype, L.batch, cap);
+    while (nb > 1 && chunk_bytes(L.n, sp, L.dtype, nb, T, bluestein_fused, cap) > scratch_bytes) nb = (nb + 1) / 2;
+    if (!scratch || chunk_bytes(L.n, sp, L.dtype, nb, T, bluestein_fused, cap) > scratch_bytes) return fail(DFFT_EINVAL, "real columns: scratch buffer too small");
     const size_t zb = (size_t)nb * L.n * sp * elem_bytes(L.dtype);
     void*        inner = (char*)scratch + zb;
     const size_t inner_bytes = scratch_bytes - zb;

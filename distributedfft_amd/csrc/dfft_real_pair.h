@@ -32,11 +32,11 @@ bool real_pair_fused(long long n);
 // Scratch bytes real_pair_rows needs for `rows` rows: 0 for the fused form, else the packed pairs of one batch chunk (at most
 // max(256 MiB, one pair's)) plus the scratch of the n-point transform on that chunk (four-step: as much again; Bluestein:
 // bluestein_scratch_bytes).  `T`: the Bluestein tables of (n, dtype, dir) when n is a Bluestein length, else nullptr.
-size_t real_pair_scratch_bytes(long long n, int dtype, long long rows, const BluesteinTables* T, bool bluestein_fused);
+size_t real_pair_scratch_bytes(long long n, int dtype, long long rows, const BluesteinTables* T, bool bluestein_fused, size_t cap);
 // The rows of L: the fused kernel, or -- per batch chunk -- pack, the n-point complex transform (single-pass, long_fft or bluestein_fft
 // with T), split (R2C); merge, inverse transform, unpack (C2R).  `scratch` holds scratch_bytes >= real_pair_scratch_bytes(n, dtype, 2, T,
 // fused) bytes and does not alias in / out; `in` is never written.  Enqueues on `stream` only; allocates nothing.  DFFT_OK or DFFT_E*.
-int real_pair_rows(const RealPairLaunch& L, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
+int real_pair_rows(const RealPairLaunch& L, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes,
                    hipStream_t stream);
 
 }  // namespace dfft

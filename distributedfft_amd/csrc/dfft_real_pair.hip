@@ -272,13 +272,13 @@ __global__ void __launch_bounds__(256) c2r_pair_unpack_kernel(const V* __restric
 namespace {
 
 // packed pairs per batch chunk (at most max(256 MiB, one pair's) of them), and the scratch such a chunk needs
-long long chunk_pairs(long long n, int dtype, long long pairs) {
+long long chunk_pairs(long long n, int dtype, long long pairs, size_t cap) {
     const size_t zb = (size_t)n * elem_bytes(dtype);
-    return chunk_units(zb, pairs);
+    return chunk_units(zb, pairs, cap);
 }
-size_t chunk_bytes(long long n, int dtype, long long np, const BluesteinTables* T, bool fused) {
+size_t chunk_bytes(long long n, int dtype, long long np, const BluesteinTables* T, bool fused, size_t cap) {
     const size_t zb = (size_t)np * n * elem_bytes(dtype);
-    if (T) return zb + bluestein_scratch_bytes(*T, 1, np, fused);
+    if (T) return zb + bluestein_scratch_bytes(*T, 1, np, fused, cap);
     return n > 4096 ? 2 * zb : zb;  // four-step: long_fft's scratch as large as its data
 }
 
@@ -347,12 +347,12 @@ bool real_pair_fused(long long n) {
     }
 }
 
-size_t real_pair_scratch_bytes(long long n, int dtype, long long rows, const BluesteinTables* T, bool bluestein_fused) {
+size_t real_pair_scratch_bytes(long long n, int dtype, long long rows, const BluesteinTables* T, bool bluestein_fused, size_t cap) {
     if (n < 1 || rows <= 0 || real_pair_fused(n)) return 0;
-    return chunk_bytes(n, dtype, chunk_pairs(n, dtype, (rows + 1) / 2), T, bluestein_fused);
+    return chunk_bytes(n, dtype, chunk_pairs(n, dtype, (rows + 1) / 2, cap), T, bluestein_fused, cap);
 }
 
-int real_pair_rows(const RealPairLaunch& L, const BluesteinTables* T, bool bluestein_fused, void* scratch, size_t scratch_bytes,
+int real_pair_rows(const RealPairLaunch& L, const BluesteinTables* T, bool bluestein_fused, size_t cap, void* scratch, size_t scratch_bytes,
                    hipStream_t stream) {
     if (L.n < 1 || (L.dir != 1 && L.dir != -1) || (L.dtype != F64 && L.dtype != F32) || !L.in || !L.out)
         return fail(DFFT_EINVAL, "real pair rows: bad arguments");
@@ -379,9 +379,9 @@ int real_pair_rows(const RealPairLaunch& L, const BluesteinTables* T, bool blues
         if (!long_split(L.n, &a, &b)) return fail(DFFT_EINVAL, "real pair rows: length " + std::to_string(L.n) + " needs Bluestein tables");
     }
     // batch chunks of whole pairs that fit the scratch
-    long long np = chunk_pairs(L.n, L.dtype, (L.rows + 1) / 2);
-    while (np > 1 && chunk_bytes(L.n, L.dtype, np, T, bluestein_fused) > scratch_bytes) np = (np + 1) / 2;
-    if (!scratch || chunk_bytes(L.n, L.dtype, np, T, bluestein_fused) > scratch_bytes) return fail(DFFT_EINVAL, "real pair rows: scratch buffer too small");
+    long long np = chunk_pairs(L.n, L.dtype, (L.rows + 1) / 2, cap);
+    while (np > 1 && chunk_bytes(L.n, L.dtype, np, T, bluestein_fused, cap) > scratch_bytes) np = (np + 1) / 2;
+    if (!scratch || chunk_bytes(L.n, L.dtype, np, T, bluestein_fused, cap) > scratch_bytes) return fail(DFFT_EINVAL, "real pair rows: scratch buffer too small");
     const size_t zb = (size_t)np * L.n * elem_bytes(L.dtype);
     void*        inner = (char*)scratch + zb;
     const size_t inner_bytes = scratch_bytes - zb;

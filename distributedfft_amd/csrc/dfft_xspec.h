@@ -30,11 +30,11 @@ bool rxspec_fused(long long n, long long m, int dtype, bool vec);
 long long rxspec_slices(long long m, long long channels, long long batch, int dtype);
 // Scratch bytes rxspec needs.  Fused: the partial sums [slices][channels][m/2 + 1] (0 for one slice).  Composed: the padded rows and
 // the bins of both fields for one chunk of rows of at most max(256 MiB, one row's).
-size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on);
+size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on, size_t cap);
 // The cross-spectrum of L: the fused kernel (and, for more than one slice, the kernel that sums the slices in order), or -- per chunk
 // of rows -- pad kernel on both fields, R2C rows (launch_real_rows) on both, and a kernel that adds each channel's rows to `out` in row
 // order.  `scratch` holds scratch_bytes >= rxspec_scratch_bytes(L) bytes (composed: at least one row's) and aliases none of x, g, out.
 // Enqueues on `stream` only; allocates nothing (twiddle tables are cached per device).  DFFT_OK or DFFT_E*.
-int rxspec(const RxspecLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream);
+int rxspec(const RxspecLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
 }  // namespace dfft

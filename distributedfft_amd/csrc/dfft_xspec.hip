@@ -274,16 +274,16 @@ long long rxspec_slices(long long m, long long channels, long long batch, int dt
     return slice_count(groups_per_workgroup(m / 2), kRxspecMaxGroupFactor, channels, batch, kRxspecMinRows);
 }
 
-size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on) {
+size_t rxspec_scratch_bytes(const RxspecLaunch& L, bool fused_on, size_t cap) {
     if (!shape_ok(L)) return 0;
     if (fused_on && rxspec_fused(L.n, L.m, L.dtype, rxspec_vec(L.x, L.g, L.n, L.dtype))) {
         const long long slices = rxspec_slices(L.m, L.channels, L.batch, L.dtype);
         return slices > 1 ? (size_t)slices * L.channels * (L.m / 2 + 1) * elem_bytes(L.dtype) : 0;
     }
-    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels) * row_bytes(L.m, L.dtype);
+    return (size_t)chunk_units(row_bytes(L.m, L.dtype), L.batch * L.channels, cap) * row_bytes(L.m, L.dtype);
 }
 
-int rxspec(const RxspecLaunch& L, bool fused_on, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+int rxspec(const RxspecLaunch& L, bool fused_on, size_t cap, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     if (!shape_ok(L) || !L.x || !L.g || !L.out) return fail(DFFT_EINVAL, "rxspec: bad arguments");
     const long long rows = L.batch * L.channels, nb = L.m / 2 + 1;
     const bool      vec = rxspec_vec(L.x, L.g, L.n, L.dtype);
@@ -312,7 +312,7 @@ int rxspec(const RxspecLaunch& L, bool fused_on, void* scratch, size_t scratch_b
     }
     // chunks of rows whose padded rows and bins fit the scratch buffer
     const size_t    rb = row_bytes(L.m, L.dtype);
-    const long long nr = fit_chunk_to_lease("rxspec", chunk_units(rb, rows), rb, scratch, scratch_bytes);
+    const long long nr = fit_chunk_to_lease("rxspec", chunk_units(rb, rows, cap), rb, scratch, scratch_bytes);
     if (nr < 1) return DFFT_EINVAL;
     for (long long r0 = 0; r0 < rows; r0 += nr) {
         const long long k = std::min(nr, rows - r0);

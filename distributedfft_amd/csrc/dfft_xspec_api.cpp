@@ -41,7 +41,7 @@ long long dfft_rxspec1d_slices(long long m, long long channels, long long batch,
 unsigned long long dfft_rxspec1d_scratch_bytes(long long n, long long m, long long channels, long long batch, int dtype) {
     if (!valid_dtype(dtype) || n < 1 || m < n || channels < 1 || batch < 1 || real_form(m) != 1 || !rows_ok(channels, batch)) return 0;
     // (the route depends on neither the alignment nor on whether g is x)
-    return rxspec_scratch_bytes(make_launch(nullptr, nullptr, nullptr, n, m, channels, batch, dtype), rxspec_fused_env());
+    return rxspec_scratch_bytes(make_launch(nullptr, nullptr, nullptr, n, m, channels, batch, dtype), rxspec_fused_env(), chunk_cap_env());
 }
 
 // Cross-spectrum of the rows of reals x, g [batch][channels][n], zero-padded to m, summed over the batch into out [channels][m/2 + 1]
@@ -59,11 +59,12 @@ int dfft_rxspec1d(const void* x, const void* g, void* out, long long n, long lon
     if (dfft_device_count() < 1) return fail(DFFT_ENOGPU, "dfft_rxspec1d: no HIP device visible (no CPU fallback)");
     const hipStream_t  st = (hipStream_t)stream;
     const bool         fused_on = rxspec_fused_env();
+    const size_t       cap = chunk_cap_env();
     const RxspecLaunch L = make_launch(x, g, out, n, m, channels, batch, dtype);
-    const size_t       need = rxspec_scratch_bytes(L, fused_on);
+    const size_t       need = rxspec_scratch_bytes(L, fused_on, cap);
     ScratchLease       lease;
     if (need && !lease.acquire(need, st)) return fail(DFFT_EHIP, "dfft_rxspec1d: cannot allocate the scratch buffer");
-    return rxspec(L, fused_on, lease.get(), need, st);
+    return rxspec(L, fused_on, cap, lease.get(), need, st);
 }
 
 }  // extern "C"

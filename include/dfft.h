@@ -399,7 +399,17 @@ int dfft_r2r_fused_applies(long long n, long long s, int dtype, int kind, int ve
 /* Scratch bytes the call leases from the per-(device, stream) buffer dfft_trim frees (0: none, or a call beyond the supported extent,
  * which leases nothing; no device is queried).  Batch chunks keep
  * the Bluestein multi-pass, real-column and r2r composed routes at max(256 MiB, one item's) of packed data plus the inner transform's own
- * scratch; a four-step dfft_fft1d_any takes as much as its data. */
+ * scratch; a four-step dfft_fft1d_any takes as much as its data.
+ *
+ * THE CHUNK CAP.  Every "max(256 MiB, one row's / item's / pair's)" in this header is max(cap, one unit's): the cap is 256 MiB unless the
+ * environment variable DFFT_SCRATCH_CHUNK_BYTES holds a positive number of bytes (unset, empty or non-positive: 256 MiB).  It is a test
+ * and measurement switch -- it makes several chunks of a small problem -- and changes no result beyond the order in which the accumulating
+ * routes (dfft_rxspec1d_long, fused) add their chunks.  dfft_stft1d / dfft_istft1d and dfft_rcsd1d look at DFFT_STFT_CHUNK_BYTES and
+ * DFFT_RCSD_CHUNK_BYTES first, then at the general name.  A chunk never holds fewer than one unit, nor fewer than a route's own minimum.
+ * A plan-less call and each *_scratch_bytes query read the cap ONCE per call, so a query made under the environment of the call it
+ * describes announces that call's lease, and nested chunkings (an r2r or paired-row chunk with Bluestein chunks inside, the long routes'
+ * rows) cut by one value.  A PLAN reads the cap when it is CREATED: its any-length real rows and Bluestein axes size their plan-owned
+ * scratch by it and every execute cuts by that scratch, whatever the variable holds then.  Results of plans do not depend on it. */
 unsigned long long dfft_fft1d_any_scratch_bytes(long long n, long long s, long long batch, int dtype);
 unsigned long long dfft_rfft1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype);
 unsigned long long dfft_r2r1d_strided_scratch_bytes(long long n, long long s, long long batch, int dtype, int kind, int vec);
@@ -573,7 +583,9 @@ int dfft_rconv1d_os_block(long long taps, long long n_out, int dtype, long long*
  * memory.  Chunks hold at most max(256 MiB, one row's) scratch from the per-(device, stream) buffer dfft_trim frees; a call allocates
  * nothing once that and the small twiddle tables of (device, m, dtype) are warm.  The splits whose kernels would spill or measured slower,
  * and every m under DFFT_RCONV_LONG_FUSED=0 (read per call), run pad -> the real rows of length m as dfft_rfft1d runs them -> multiply ->
- * inverse rows -> truncate.  dfft_rconv1d_long_fused_applies tells the route; dfft_rconv1d_long_scratch_bytes the lease of the three-launch
+ * inverse rows -> truncate, in chunks of WHOLE ROW PAIRS (an even number of rows, at least two, unless the chunk is the whole call) within
+ * max(256 MiB, one pair's) bins and padded rows, so that rows 2p and 2p + 1 are partners wherever the chunks are cut.
+ * dfft_rconv1d_long_fused_applies tells the route; dfft_rconv1d_long_scratch_bytes the lease of the three-launch
  * route: min(rows, rows per chunk) * M complex (0 for sizes that are refused; the composed route leases its bins, padded rows and the
  * transforms' own scratch instead).  Both, the length and the split are host arithmetic. */
 long long dfft_rconv1d_long_length(long long at_least);
@@ -606,8 +618,9 @@ unsigned long long dfft_rconv1d_long_scratch_bytes(long long n, long long m, lon
  * So every bit of the result is the same from call to call.  A call of one chunk and one slice in order 1 stores straight to out.
  * The splits whose accumulating kernel would keep values in scratch memory (csrc/dfft_lxspec.hip: lxspec_fused_ok), and every m under
  * DFFT_RXSPEC_LONG_FUSED=0 (read per call), run the composed route: pad -> the real rows of length m as dfft_rfft1d runs them, on both
- * fields -> a kernel that adds each channel's rows to out in row order; deterministic as well, in chunks of at most max(256 MiB, one
- * row's) bins and padded rows.  dfft_rxspec1d_long_fused_applies tells the route; dfft_rxspec1d_long_slices the slice count of the first
+ * fields -> a kernel that adds each channel's rows to out in row order; deterministic as well, in chunks of whole row pairs (as the
+ * composed route of dfft_rconv1d_long) of at most max(256 MiB, one pair's) bins and padded rows, and -- the rows being added in row
+ * order onto out -- the same bits wherever the chunks are cut.  dfft_rxspec1d_long_fused_applies tells the route; dfft_rxspec1d_long_slices the slice count of the first
  * (the largest) chunk; dfft_rxspec1d_long_scratch_bytes the lease of the fused route: (chunk rows * 2 * M + slices * channels * (M + 1))
  * complex (0 for sizes that are refused; the composed route leases its bins, padded rows and the transforms' own scratch instead).  All
  * three are host arithmetic.  Bluestein halves and strided rows are NOT built (the framed, windowed form is dfft_rcsd1d, m <= 8192). */

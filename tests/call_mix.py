@@ -9,9 +9,11 @@ the reference, the environment switches of its route, and whether it `leases` sc
 Cases, references and bounds are those of the families' own builders: accuracy_ref, rconv1d_cases, rconv1d_os_cases, rconv1d_long_cases,
 rxspec1d_cases, rxspec1d_long_cases, stft_cases, rcsd1d_cases.  Sizes are the smallest that still take the route.
 
+rconv1d, rconv1d_os and rxspec1d composed run in SEVERAL chunks too: their rule cuts at 256 MiB of scratch, beyond the 64 MiB this module
+allows itself, so the ops carry the general chunk cap DFFT_SCRATCH_CHUNK_BYTES in their environment, as the stft1d, istft1d and rcsd1d
+ops carry DFFT_STFT_CHUNK_BYTES / DFFT_RCSD_CHUNK_BYTES.  (Every other composed route's seams: tests/chunk_seams.py.)
+
 Left out, on purpose:
-  * rconv1d / rconv1d_os / rxspec1d composed in SEVERAL chunks: those families have no chunk switch, and their own rule cuts at 256 MiB
-    of scratch -- beyond the 64 MiB this module allows itself.  (stft1d, istft1d and rcsd1d have DFFT_*_CHUNK_BYTES and are registered.)
   * a dfft_rconv1d_long length whose fused kernels spill: there is none (dfft_lconv.hip, lconv_fused_ok is true for every factor), so the
     composed route is reached through DFFT_RCONV_LONG_FUSED=0 only.  dfft_rxspec1d_long does have such lengths (N2 = 384, fp64)."""
 import contextlib
@@ -230,9 +232,9 @@ def complex_1d(name, entry, family, n, shape, prec, direction=FWD, flag=LEASES, 
 
 
 # ---- real 1-D rows and strided columns ----------------------------------------------------------------------------------------------------
-def real_1d(name, family, n, s, prec, direction, flag, strided):
-    """dfft_rfft1d on [3][n] (strided=False) or dfft_rfft1d_strided on [2][n][s]"""
-    batch, code, nh = (2 if strided else 3), CODE[prec], n // 2 + 1
+def real_1d(name, family, n, s, prec, direction, flag, strided, batch=None, switches=None):
+    """dfft_rfft1d on [3][n] (strided=False) or dfft_rfft1d_strided on [2][n][s] (or on `batch` rows / items)"""
+    batch, code, nh = batch or (2 if strided else 3), CODE[prec], n // 2 + 1
 
     def build():
         if direction > 0:
@@ -258,11 +260,11 @@ def real_1d(name, family, n, s, prec, direction, flag, strided):
 
     bound, bname = _acc(family, prec)
     return Op(name, "dfft_rfft1d_strided" if strided else "dfft_rfft1d", prec, flag, build, call, need,
-              lambda got, ref: A.nu(got, ref, n, prec, (1,)), bound, bname, model, tables=True)
+              lambda got, ref: A.nu(got, ref, n, prec, (1,)), bound, bname, model, switches, tables=True)
 
 
-def r2r_1d(name, family, n, s, kind, prec, flag, switches=None):
-    batch, code, k = 2, CODE[prec], A.R2R_KINDS.index(kind)
+def r2r_1d(name, family, n, s, kind, prec, flag, switches=None, batch=2):
+    code, k = CODE[prec], A.R2R_KINDS.index(kind)
 
     def build():
         case = A.r2r_lines(n, batch, s, 6000 + n)
@@ -330,8 +332,8 @@ def _pad(x, m, prec):
     return xp
 
 
-def rconv1d(name, M, n, channels, kind, prec, flag, switches=None):
-    m, code, batch = 2 * M, CODE[prec], RC.batch_for(M, channels)
+def rconv1d(name, M, n, channels, kind, prec, flag, switches=None, batch=None):
+    m, code, batch = 2 * M, CODE[prec], batch or RC.batch_for(M, channels)
 
     def build():
         x, H, ref = RC.case(M, n, channels, batch, kind)
@@ -348,8 +350,8 @@ def rconv1d(name, M, n, channels, kind, prec, flag, switches=None):
               switches)
 
 
-def rconv1d_os(name, M, d, n, n_out, kind, prec, flag, switches=None):
-    m, code, channels, batch = 2 * M, CODE[prec], 3, 2
+def rconv1d_os(name, M, d, n, n_out, kind, prec, flag, switches=None, channels=3, batch=2):
+    m, code = 2 * M, CODE[prec]
 
     def build():
         x, H, ref = OC.case(M, d, n, n_out, channels, batch, kind)
@@ -369,23 +371,50 @@ def rconv1d_os(name, M, d, n, n_out, kind, prec, flag, switches=None):
               model, switches)
 
 
+def long_row_bytes(m, prec, fields):
+    """One row of the composed long routes: its bins of `fields` fields and its m padded reals"""
+    return fields * (m // 2 + 1) * ESIZE[prec] + m * (ESIZE[prec] // 2)
+
+
+def long_composed_chunk_rows(rb, rows, cap):
+    """dfft_batch.cpp long_composed_chunk_rows: rows of rb bytes within max(cap, one row's), never fewer than two, and whole pairs (an
+    even count) unless the chunk is the whole call -- rows 2p and 2p + 1 share their transforms"""
+    nr = max(1, min(rows, max(max(cap, rb) // rb, 2)))
+    return nr - (nr & 1) if nr < rows else nr
+
+
+def chunk_cap():
+    """The cap of the chunk rule as the library reads it per call: a positive DFFT_SCRATCH_CHUNK_BYTES, else 256 MiB"""
+    text = os.environ.get("DFFT_SCRATCH_CHUNK_BYTES", "")
+    try:
+        value = int(text)
+    except ValueError:
+        value = 0
+    return value if value > 0 else 256 << 20
+
+
 def _long_composed_need(lib, m, rows, prec, fields):
     """The lease of the composed routes of dfft_rconv1d_long (fields = 1) / dfft_rxspec1d_long (fields = 2) by the rule in
-    dfft_batch.cpp: the bins of `fields` fields and the padded rows of a chunk, rounded up to 256 bytes, plus the real rows' own scratch"""
-    cs = ESIZE[prec]
-    rb = fields * (m // 2 + 1) * cs + m * (cs // 2)
-    nr = max(1, min(rows, max(256 << 20, rb) // rb))
+    dfft_batch.cpp: the bins of `fields` fields and the padded rows of a chunk, rounded up to 256 bytes, plus the real rows' own scratch
+    (the entry points have no query of their own for this route; the real rows' query reads the same cap)"""
+    nr = long_composed_chunk_rows(long_row_bytes(m, prec, fields), rows, chunk_cap())
+    rb = long_row_bytes(m, prec, fields)
     inner = max(lib.dfft_rfft1d_scratch_bytes(m, nr, CODE[prec], d) for d in ((FWD, BWD) if fields == 1 else (FWD,)))
     return (nr * rb + 255) // 256 * 256 + inner
 
 
-def rconv1d_long(name, m, n, kind, prec, switches=None):
+def rconv1d_long(name, m, n, kind, prec, switches=None, rows=None):
+    """`rows` = (batch, channels): another row count than the accuracy sweep's, with rconv1d_cases' longdouble reference at length m"""
     code = CODE[prec]
-    batch, channels = LC.ACC_ROWS
-    n1, n2 = LC.SPLITS[m]
+    batch, channels = rows or LC.ACC_ROWS
+    n1, n2 = LC.SPLITS.get(m) or LC.split(m)
 
     def build():
-        x, H, ref = LC.acc_case(m, n, kind)
+        if rows:
+            x, H, _ = LC.case(m, n, channels, batch, kind)
+            ref = RC.reference(x, H, m)
+        else:
+            x, H, ref = LC.acc_case(m, n, kind)
         return {"x": _real(x, prec), "hp": _filter(LC.permute_filter(H, n1, n2), kind, prec), "h": _filter(H, kind, prec)}, x.shape, A.RDT[prec], ref
 
     def need(lib):
@@ -545,8 +574,14 @@ STFT_BASE = (64, 32, 64, 386, "hann")       # stft_cases' base case: M, hop, pad
 ISTFT_BASE = (64, 32, 64, 9, "hann")        # M, hop, pad, frames, window
 RCSD_M, RCSD_ROWS = 64, 3
 RXSPEC_M, RXSPEC_CHANNELS = 64, 3
+CHUNK_ENV = "DFFT_SCRATCH_CHUNK_BYTES"       # the general chunk cap, read once per call
 LONG_M = 16384                               # the smallest padded length of the long families: 64 x 128
 LONG_SPILL_M = XL.mid_length(384)            # dfft_rxspec1d_long: N2 = 384 spills in fp64 (rxspec1d_long_cases.ROUTED)
+
+
+def chunks_cap(prec):
+    """The cap of the several-chunk ops of rconv1d / rconv1d_os / rxspec1d: four rows of dfft_rconv1d at m = 72 (37 bins and 72 reals)"""
+    return 4 * (37 * ESIZE[prec] + 72 * ESIZE[prec] // 2)
 
 
 def ops_of(prec):
@@ -596,6 +631,13 @@ def ops_of(prec):
     out.append(rconv1d_os("osconv-64", 64, 32, 240, 272, "complex", prec, NO_LEASE))
     out.append(rconv1d_os("osconv-64-composed", 64, 33, 237, 237, "real", prec, LEASES, {"DFFT_RCONV_FUSED": 0}))
     out.append(rconv1d_os("osconv-36-untuned", 36, 10, 155, 165, "complex", prec, LEASES))
+    # the same two composed in several chunks, and dfft_rxspec1d with them (an untuned half: composed by itself), under ONE cap -- four
+    # rows of the convolution, so that host threads can share the environment: 21 rows in chunks of 4, 18 items in chunks of 4, 21 rows
+    # in chunks of 2
+    capped = {CHUNK_ENV: chunks_cap(prec)}
+    out.append(rconv1d("rconv-36-chunks", 36, 72, 3, "complex", prec, LEASES, capped, batch=7))
+    out.append(rconv1d_os("osconv-36-chunks", 36, 10, 155, 165, "complex", prec, LEASES, capped))
+    out.append(rxspec1d("rxspec-cross-chunks", 36, 72, 3, 7, False, prec, LEASES, capped))
     # dfft_stft1d: one launch, composed, composed in several chunks (five items each), the power form, an untuned half
     chunked = lambda kind: {"DFFT_STFT_FUSED": 0, "DFFT_STFT_CHUNK_BYTES": 5 * stft_item_bytes(128, prec, kind)}  # noqa: E731
     out.append(stft1d("stft-64", STFT_BASE, "reflect", "complex", prec, NO_LEASE))

@@ -542,7 +542,7 @@ def half_planes_base(n1, n2, K):
 
 
 # ---- mirrors of the library's chunk rules ---------------------------------------------------------------------------------------------------
-SCRATCH_CAP = 256 << 20                       # kScratchCap / kR2rScratchCap / kColsScratchCap
+SCRATCH_CAP = 256 << 20                       # kScratchCap: the default of every `cap` below (DFFT_SCRATCH_CHUNK_BYTES lowers it per call)
 CBYTES = {"f64": 16, "f32": 8}                # one complex element
 
 
@@ -551,14 +551,24 @@ def bluestein_per_transform_bytes(M, s, prec):
     return M * s * CBYTES[prec] * (2 if M > 4096 else 1)
 
 
-def bluestein_chunk(M, s, batch, prec):
+def cap_units(unit_bytes, units, cap=SCRATCH_CAP, at_least=1):
+    """dfft_fused_host.h chunk_units: the units of `unit_bytes` each per chunk -- what fits `cap`, at least one and at least `at_least`,
+    at most all of them"""
+    return max(1, min(units, max(max(cap, unit_bytes) // unit_bytes, at_least)))
+
+
+def chunk_sizes(units, per_chunk):
+    """the chunk loop: [units of each chunk], in order"""
+    return [min(per_chunk, units - u0) for u0 in range(0, units, per_chunk)]
+
+
+def bluestein_chunk(M, s, batch, prec, cap=SCRATCH_CAP):
     """batch items per chunk of the multi-pass form"""
-    per = bluestein_per_transform_bytes(M, s, prec)
-    return min(batch, max(1, max(SCRATCH_CAP, per) // per))
+    return cap_units(bluestein_per_transform_bytes(M, s, prec), batch, cap)
 
 
-def bluestein_scratch(M, s, batch, prec, fused):
-    return 0 if fused else bluestein_chunk(M, s, batch, prec) * bluestein_per_transform_bytes(M, s, prec)
+def bluestein_scratch(M, s, batch, prec, fused, cap=SCRATCH_CAP):
+    return 0 if fused else bluestein_chunk(M, s, batch, prec, cap) * bluestein_per_transform_bytes(M, s, prec)
 
 
 def pair_units(s, batch):
@@ -566,24 +576,30 @@ def pair_units(s, batch):
     return ((batch + 1) // 2, 1) if s == 1 else (batch, (s + 1) // 2)
 
 
-def chunk_units(n, sp, prec, units):
-    """units per chunk of the composed r2r route / items per chunk of the multi-pass real columns: packed pairs within max(256 MiB, one unit's)"""
-    zb = n * sp * CBYTES[prec]
-    return max(1, min(units, max(SCRATCH_CAP, zb) // zb))
+def chunk_units(n, sp, prec, units, cap=SCRATCH_CAP):
+    """units per chunk of the composed r2r route / items per chunk of the multi-pass real columns / pairs per chunk of the paired real
+    rows (sp = 1): packed pairs within max(cap, one unit's)"""
+    return cap_units(n * sp * CBYTES[prec], units, cap)
 
 
-def chunk_bytes(n, sp, prec, nu, M, bs_fused):
-    """scratch of one chunk: the packed pairs plus the inner transform's (M: the Bluestein padded length, 0 for kinds 1 and 2)"""
+def chunk_bytes(n, sp, prec, nu, M, bs_fused, cap=SCRATCH_CAP):
+    """scratch of one chunk: the packed pairs plus the inner transform's (M: the Bluestein padded length, 0 for kinds 1 and 2) -- the
+    inner Bluestein chunks are cut by the same cap"""
     zb = nu * n * sp * CBYTES[prec]
     if M:
-        return zb + bluestein_scratch(M, sp, nu, prec, bs_fused)
+        return zb + bluestein_scratch(M, sp, nu, prec, bs_fused, cap)
     return 2 * zb if n > 4096 else zb
 
 
-def composed_scratch(n, s, batch, prec, M, bs_fused, rows_pair=True):
+def composed_scratch(n, s, batch, prec, M, bs_fused, rows_pair=True, cap=SCRATCH_CAP):
     """r2r_scratch_bytes (rows_pair: s = 1 pairs rows) / real_cols_scratch_bytes (s > 1) of a call that does NOT run fused"""
     units, sp = pair_units(s, batch) if rows_pair else (batch, (s + 1) // 2)
-    return chunk_bytes(n, sp, prec, chunk_units(n, sp, prec, units), M, bs_fused)
+    return chunk_bytes(n, sp, prec, chunk_units(n, sp, prec, units, cap), M, bs_fused, cap)
+
+
+def real_pair_scratch(n, rows, prec, M, bs_fused, cap=SCRATCH_CAP):
+    """real_pair_scratch_bytes of rows that do NOT run fused (real forms 2 and 3 outside the odd tuned lengths): chunks of whole pairs"""
+    return chunk_bytes(n, 1, prec, chunk_units(n, 1, prec, (rows + 1) // 2, cap), M, bs_fused, cap)
 
 
 def ragged_batch(cu):

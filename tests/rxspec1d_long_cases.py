@@ -54,10 +54,10 @@ def klass(n, batch):
     return "chunks" if batch > 100 else ("n1" if n == 1 else "sweep")
 
 
-def chunk_rows(m, prec, rows):
+def chunk_rows(m, prec, rows, cap=SCRATCH_CAP):
     """Rows per chunk: the batch * channels rows are cut in order; a row costs m/2 complex for either field (two counted always)"""
     rb = 2 * (m // 2) * ESIZE[prec]
-    return max(1, min(rows, max(SCRATCH_CAP, rb) // rb))
+    return max(1, min(rows, max(cap, rb) // rb))
 
 
 def slices_rule(m, channels, rows):
@@ -67,20 +67,20 @@ def slices_rule(m, channels, rows):
     return max(1, min(TARGET_ITEMS // (channels * ((n1 + 1) // 2)), steps // MIN_STEPS))
 
 
-def call_slices(m, channels, batch, prec):
+def call_slices(m, channels, batch, prec, cap=SCRATCH_CAP):
     """dfft_rxspec1d_long_slices: the slices of the first (the largest) chunk"""
-    return slices_rule(m, channels, chunk_rows(m, prec, batch * channels))
+    return slices_rule(m, channels, chunk_rows(m, prec, batch * channels, cap))
 
 
-def scratch_bytes(m, channels, batch, prec):
+def scratch_bytes(m, channels, batch, prec, cap=SCRATCH_CAP):
     """dfft_rxspec1d_long_scratch_bytes: the pass-A results of a chunk and the partial sums of its slices"""
-    nr = chunk_rows(m, prec, batch * channels)
+    nr = chunk_rows(m, prec, batch * channels, cap)
     return (nr * 2 * (m // 2) + slices_rule(m, channels, nr) * channels * (m // 2 + 1)) * ESIZE[prec]
 
 
-def chunks(m, prec, rows):
+def chunks(m, prec, rows, cap=SCRATCH_CAP):
     """[(first row, rows)] of the chunks"""
-    nr = chunk_rows(m, prec, rows)
+    nr = chunk_rows(m, prec, rows, cap)
     return [(r0, min(nr, rows - r0)) for r0 in range(0, rows, nr)]
 
 

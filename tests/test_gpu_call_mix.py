@@ -351,14 +351,15 @@ def test_trim_from_a_second_thread(gpu):
 
 # ---- (e) host threads ---------------------------------------------------------------------------------------------------------------------
 def test_two_threads_on_one_stream(gpu):
-    """One thread loops a several-chunk composed rcsd1d, the other a several-chunk composed stft1d / istft1d pair and a composed
-    rconv1d_long, all on ONE stream: a lease has to cover every launch of its call.  The switches of all four are set once around the
+    """One thread loops a several-chunk composed rcsd1d and rconv1d, the other a several-chunk composed stft1d / istft1d pair, a composed
+    rconv1d_long and a several-chunk composed rconv1d_os and rxspec1d, all on ONE stream: a lease has to cover every launch of its call.  The switches of all four are set once around the
     whole test (host threads must not change the environment under each other) and the solo results are taken under the same switches:
     the composed rcsd1d runs its frames through the composed stft route then."""
     import torch
     by = CM.BY_NAME
-    first = [by["rcsd-cross-chunks-f64"]]
-    second = [by["stft-64-chunks-f64"], by["istft-64-chunks-f64"], by["lconv-16384-composed-f64"]]
+    first = [by["rcsd-cross-chunks-f64"], by["rconv-36-chunks-f64"]]
+    second = [by["stft-64-chunks-f64"], by["istft-64-chunks-f64"], by["lconv-16384-composed-f64"], by["osconv-36-chunks-f64"],
+              by["rxspec-cross-chunks-f64"]]
     switches = {}
     for op in first + second:
         for k, v in op.switches.items():

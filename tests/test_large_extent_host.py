@@ -541,7 +541,7 @@ def test_row_case_routes_and_the_refusals_just_over_their_guards(native_lib, mon
     DFFT_EUNSUPPORTED before asking for a device (the pointers, a small host array, are never used)."""
     from distributedfft_amd import _lib
     lib = native_lib
-    for name in ("DFFT_RCONV_FUSED", "DFFT_STFT_FUSED", "DFFT_RCONV_LONG_FUSED", "DFFT_STFT_CHUNK_BYTES"):
+    for name in ("DFFT_RCONV_FUSED", "DFFT_STFT_FUSED", "DFFT_RCONV_LONG_FUSED", "DFFT_STFT_CHUNK_BYTES", "DFFT_SCRATCH_CHUNK_BYTES"):
         monkeypatch.delenv(name, raising=False)
     P31 = 2 ** 31
     # dfft_rconv1d: a tuned half runs fused and leases nothing, M = 36 and DFFT_RCONV_FUSED=0 run composed on a 256 MiB chunk

@@ -182,6 +182,7 @@ def test_route_and_scratch_rules(monkeypatch):
     lib = _lib()
     monkeypatch.delenv("DFFT_RCSD_FUSED", raising=False)
     monkeypatch.delenv("DFFT_RCSD_CHUNK_BYTES", raising=False)
+    monkeypatch.delenv("DFFT_SCRATCH_CHUNK_BYTES", raising=False)
     tuned = set(RC.plan_points())
 
     def lease(m, items, dtype, cap=256 << 20):

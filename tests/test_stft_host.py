@@ -202,6 +202,7 @@ def test_route_and_scratch_rules(monkeypatch):
     lib = _lib()
     monkeypatch.delenv("DFFT_STFT_FUSED", raising=False)
     monkeypatch.delenv("DFFT_STFT_CHUNK_BYTES", raising=False)
+    monkeypatch.delenv("DFFT_SCRATCH_CHUNK_BYTES", raising=False)
     tuned = set(_tuned())
 
     def lease(ib, items, cap=256 << 20):
